@@ -12,7 +12,13 @@ does not shard without a per-step exchange (DESIGN.md "Multi-GPU"): `--gpus N` r
 (weak scaling, e.g. the reference's concurrent forward/backward propagators or an ensemble); value = bodies x
 steps summed over ranks / max-over-ranks time. No data-path collective.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+A plain run times exactly K steps (one K-step block between barrier + device sync) after the start-up, the clock
+pre-warm and the W warm-up steps, and prints the line. Everything else the benchmark measures or checks (the spread of
+repeated blocks, the long region, CPU baselines, parity against the oracle, the other evaluation orders and
+configurations, the strong-scaling legs of N > 1) runs only with `--full`. `--dump-outputs DIR` writes the state the
+timed steps ended in as DIR/<name>.npy (float64; inputs are seeded, so two builds compare output for output).
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -34,6 +40,27 @@ FLOP_PER_INTERACTION = 20.0
 HBM_PEAK_GBS = 8000.0                  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 FP64_VECTOR_PEAK_TFLOPS = 78.6         # MI355X vector FP64 (no MFMA on this path)
 FP32_VECTOR_PEAK_TFLOPS = 157.3        # MI355X vector FP32 (packed v_pk_fma_f32): the roof of --path f32-pairs' pair arithmetic
+DUMP_LIMIT_BYTES = 60 << 20            # --dump-outputs: under 64 MB in all, .npy headers included
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` ({name: array}) as DIR/<name>.npy in float64. Above `limit` bytes in all, each
+    array is cut to the same fraction of its rows, a fixed seeded sample (the row indices in DIR/<name>_rows.npy, float64)."""
+    import numpy as np
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit and a.ndim >= 1 and len(a) > 1:
+            row_bytes = a.nbytes // len(a) + 8                     # (+ its index)
+            keep = max(1, min(len(a), int(limit / total * a.nbytes / row_bytes)))     # its share of the limit
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), size=keep, replace=False))
+            np.save(out / f"{name}_rows.npy", rows.astype(np.float64))
+            a = a[rows]
+        np.save(out / f"{name}.npy", a)
+    return sorted(p.name for p in out.glob("*.npy"))
 
 
 def cpu_baseline(pos, vel, mu, steps):
@@ -147,18 +174,20 @@ def craft_main(args):
         sol = ea.NBodyPropagator.from_system(s).propagate(s.epoch + (args.craft_days + 40.0) * 86400.0)
         return ea.Ephemeris(sol, s.mu)
 
-    build_table()                                        # (the process's first kernel launches, code-object load: neither leg pays it)
-    t_eph0 = time.perf_counter()
-    eph_local = build_table()
-    eph_rebuild_s = time.perf_counter() - t_eph0
+    if args.full:                                        # (a plain run builds the broadcast table only)
+        build_table()                                    # (the process's first kernel launches, code-object load: neither leg pays it)
+        t_eph0 = time.perf_counter()
+        eph_local = build_table()
+        eph_rebuild_s = time.perf_counter() - t_eph0
     if dist is not None:
         dist.barrier()
     t_eph0 = time.perf_counter()
     eph, eph_parts = broadcast_ephemeris(build_table, dist, device="cuda" if backend_is_nccl else "cpu")
     eph_broadcast_s = time.perf_counter() - t_eph0
-    same_table = bool(np.array_equal(eph.export_image(), eph_local.export_image()))
-    assert same_table, "the broadcast table differs from the locally integrated one"
-    del eph_local
+    if args.full:
+        same_table = bool(np.array_equal(eph.export_image(), eph_local.export_image()))
+        assert same_table, "the broadcast table differs from the locally integrated one"
+        del eph_local
     from ephemeris_explorer_amd.workloads import craft_population, wave_divergence
     pos, vel, family = craft_population(args.population, args.craft, s, ship, order=args.population_order)
     lo, hi = shard_range(args.craft, rank, world)
@@ -210,9 +239,12 @@ def craft_main(args):
     barrier()
     elapsed = time.perf_counter() - t0
     assert table.shape == (args.craft, 7) and np.isfinite(table).all() and (table[:, 0] >= t_end).all()
+    if args.dump_outputs and rank == 0:                 # the last sweep's final (t, position, velocity) of every craft
+        dump_outputs(args.dump_outputs, {"craft_states": table})
     units, elapsed = reduce_timing(elapsed, steps_local, dist, device="cuda")
-    _, eph_rebuild_s = reduce_timing(eph_rebuild_s, 0, dist, device="cuda")
-    _, eph_broadcast_s = reduce_timing(eph_broadcast_s, 0, dist, device="cuda")
+    if args.full:
+        _, eph_rebuild_s = reduce_timing(eph_rebuild_s, 0, dist, device="cuda")
+        _, eph_broadcast_s = reduce_timing(eph_broadcast_s, 0, dist, device="cuda")
     if rank == 0:
         # per craft-attempt 13 evaluations x B bodies x (Horner + index + point mass) ~ 74 flop; 56 B knot
         # written per ACCEPTED step (the ephemeris rows stay in L1/L2)
@@ -245,14 +277,17 @@ def craft_main(args):
                                   "count": "13 stages x 32 bodies x 74 flop per attempt (SURVEY 8(d))"},
                          "note": "rank 0's shard; the sweep is f64-VALU bound (every ephemeris row is an L1 hit), see roofline.fp64"},
             "wall_over_kernel": elapsed / nsweeps / launch_s,
-            "ephemeris_rebuild_s": {"max_over_ranks": eph_rebuild_s, "days": args.craft_days + 40.0,
-                                    "what": "NBodyPropagator of the 32-body system to the sweep's horizon + 40 d and its device table, "
-                                            "done by EVERY rank (after one untimed build that pays the process's first launches)"},
-            "ephemeris_broadcast_s": {"max_over_ranks": eph_broadcast_s, "rank0_parts": eph_parts,
-                                      "what": "SURVEY 8(e): rank 0 builds the table once, eph_ephemeris_export -> one broadcast of the "
-                                              "image (RCCL for world > 1) -> eph_ephemeris_import on the other ranks; the sweep runs "
-                                              "against THIS table", "identical_to_the_local_rebuild": same_table},
         }
+        if args.full:
+            out["ephemeris_rebuild_s"] = {
+                "max_over_ranks": eph_rebuild_s, "days": args.craft_days + 40.0,
+                "what": "NBodyPropagator of the 32-body system to the sweep's horizon + 40 d and its device table, "
+                        "done by EVERY rank (after one untimed build that pays the process's first launches)"}
+            out["ephemeris_broadcast_s"] = {
+                "max_over_ranks": eph_broadcast_s, "rank0_parts": eph_parts,
+                "what": "SURVEY 8(e): rank 0 builds the table once, eph_ephemeris_export -> one broadcast of the "
+                        "image (RCCL for world > 1) -> eph_ephemeris_import on the other ranks; the sweep runs "
+                        "against THIS table", "identical_to_the_local_rebuild": same_table}
         out["fp64"] = dict(out["roofline"]["fp64"], bound="fp64_valu")
         # counters of the committed rocprofv3 passes of this kernel (scripts/prof_craft.sh), scaled by the attempts of THIS run;
         # dropped when the kernel's sources changed since they were taken
@@ -290,7 +325,7 @@ def craft_main(args):
                              "attempts_per_craft_min": float(att.min()), "attempts_per_craft_max": float(att.max()),
                              "steps_by_family": {str(f): float(st["steps"][family[lo:hi] == f].mean())
                                                  for f in sorted(set(family[lo:hi].tolist()))}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = craft_cpu_baseline(s, ship, pos, vel, t_end, args.craft_days)
         print(json.dumps(out), flush=True)
     if dist is not None:
@@ -564,7 +599,7 @@ def other_configs():
     try:
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
         r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--workload", "craft", "--steps", "5",
-                            "--no-other-configs"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+                            "--no-other-configs", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
                            text=True, timeout=float(os.environ.get("EPH_BENCH_CRAFT_TIMEOUT", "240")))
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1]
         d = json.loads(line)
@@ -624,10 +659,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--cpu-steps", type=int, default=60, help="oracle steps timed for cpu_baseline (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the spread of repeated blocks, the long region, CPU baselines, parity against the "
+                         "oracle, the other evaluation orders and configurations, the strong-scaling legs of N > 1 (off: the "
+                         "plain run times its K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they ended in as DIR/<name>.npy (float64, under 64 MB in all)")
+    ap.add_argument("--cpu-steps", type=int, default=60, help="oracle steps timed for cpu_baseline (rank 0, N=1; --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the companions of the default line (configs[1] in-process, the configs[3] sweep as a child process)")
+                    help="--full without the companions of the default line (configs[1] in-process, the configs[3] sweep as a "
+                         "child process)")
     ap.add_argument("--bodies", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--workload", choices=["nbody", "craft", "nbody-sharded"], default="nbody",
                     help="nbody (default, the BASELINE metric: per-rank replicas) | craft: the massless sweep of "
@@ -638,15 +680,15 @@ def main():
                     help="nbody-sharded exchange: rccl (ncclAllGather) | peer (direct writes into IPC-mapped peer "
                          "mailboxes, csrc/peer.hip) | host (staged through host memory; tests)")
     ap.add_argument("--blocks", type=int, default=0,
-                    help="how many times the K-step block is timed (0 = as many as make the timed region >= 50 ms, at "
-                         "least 3); ms_per_step is the MEDIAN block")
+                    help="--full: how many more times the K-step block is timed after the headline block for the spread "
+                         "(0 = as many as make that region >= 50 ms, at least 3)")
     ap.add_argument("--path", choices=["exact", "fast", "fast-rsq", "f32-pairs"], default="exact",
                     help="exact (default): the reference's summation order, bit-identical to the CPU path | fast: the "
                          "opt-in slice-parallel sums (EPH_PATH_FAST) -- a second, separately labelled line "
                          "(config.workload ..._fast) with its measured divergence from the reference order")
     ap.add_argument("--horizon", type=int, default=100000,
-                    help="parity horizon: max |dpos| vs the oracle's committed positions at every 10^k-th step up to this "
-                         "many steps (tests/golden/plummer4096_horizon.npz; 0 = skip)")
+                    help="--full parity horizon: max |dpos| vs the oracle's committed positions at every 10^k-th step up to "
+                         "this many steps (tests/golden/plummer4096_horizon.npz; 0 = skip)")
     ap.add_argument("--prewarm", type=float, default=1.0,
                     help="seconds of untimed load on a scratch clone before the warm-up steps, so the timed region runs at the "
                          "steady shader clock instead of the ramp from idle (0 = off)")
@@ -741,25 +783,38 @@ def main():
         g.sync()
 
     from ephemeris_explorer_amd.parallel import reduce_timing
-    blocks = timed_blocks(block, barrier, lambda t: reduce_timing(t, 0, dist, device="cuda")[1], blocks=args.blocks)
-    elapsed = blocks[len(blocks) // 2]                   # the median block: K steps
+
+    def agree(t):
+        return reduce_timing(t, 0, dist, device="cuda")[1]
+
+    # the headline: ONE block of exactly K steps between barrier + device sync
+    elapsed_local = timed_blocks(block, barrier, agree, blocks=1)[0]
+    ms_kernel, launches = g.kernel_time()               # (HIP events of the headline block only)
+    if args.dump_outputs:
+        p_out, v_out, t_out, _ = g.state()              # (a collective on a partition: every rank reads)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"positions": p_out, "velocities": v_out, "time": [t_out]})
     units_local = n * args.steps / world if sharded else n * args.steps
-    units, elapsed = reduce_timing(elapsed, units_local, dist, device="cuda")       # sum of units, MAX of time
-    _, t_min = reduce_timing(blocks[0], 0, dist, device="cuda")
-    _, t_max = reduce_timing(blocks[-1], 0, dist, device="cuda")
-    ms_kernel, launches = g.kernel_time()
-    # The contract's region is ONE K-step block between synchronisations; a 20-step block of this kernel is 0.8 ms, of which the
-    # launch ramp and the synchronisation are about 40 us (6 %). The same K steps ten times per synchronisation, once, beside it:
-    long_reps = 10
-    g.enable_timing(False)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(long_reps):
-        g.advance(args.steps)
-    g.sync()
-    barrier()
-    _, t_long = reduce_timing(time.perf_counter() - t0, 0, dist, device="cuda")
-    want_strong = world > 1 and not sharded and not fast and n == N_BODIES
+    units, elapsed = reduce_timing(elapsed_local, units_local, dist, device="cuda")       # sum of units, MAX of time
+    if args.full:
+        # the spread: the same K-step block timed again R times (R = --blocks, or as many as make >= 50 ms, at least 3),
+        # reported with the headline block as min / median / max
+        spread = sorted([elapsed_local] + timed_blocks(block, barrier, agree, blocks=args.blocks))
+        _, t_min = reduce_timing(spread[0], 0, dist, device="cuda")
+        _, t_med = reduce_timing(spread[len(spread) // 2], 0, dist, device="cuda")
+        _, t_max = reduce_timing(spread[-1], 0, dist, device="cuda")
+        # The contract's region is ONE K-step block between synchronisations; a 20-step block of this kernel is 0.8 ms, of which the
+        # launch ramp and the synchronisation are about 40 us (6 %). The same K steps ten times per synchronisation, once, beside it:
+        long_reps = 10
+        g.enable_timing(False)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(long_reps):
+            g.advance(args.steps)
+        g.sync()
+        barrier()
+        _, t_long = reduce_timing(time.perf_counter() - t0, 0, dist, device="cuda")
+    want_strong = args.full and world > 1 and not sharded and not fast and n == N_BODIES
     out = None
 
     if rank == 0:
@@ -789,13 +844,8 @@ def main():
             "metric": "body-steps/s", "value": value, "unit": "body-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "blocks": len(blocks), "ms_per_step_min": t_min / args.steps * 1e3, "ms_per_step_max": t_max / args.steps * 1e3,
-            "timing": f"the {args.steps}-step block timed {len(blocks)} times (barrier + device sync around each); "
-                      "value and ms_per_step are the median block",
-            "long_region": {"steps": long_reps * args.steps, "ms_per_step": t_long / (long_reps * args.steps) * 1e3,
-                            "value": units / (t_long / long_reps),
-                            "note": f"{long_reps} x the K-step block per synchronisation, one region: the block's ramp and "
-                                    "synchronisation amortised (value / ms_per_step above stay the contract's single block)"},
+            "timing": f"one block of exactly {args.steps} steps (barrier + device sync around it); value and ms_per_step are "
+                      "that block",
             "pair_variant": ea.pair_variant(),
             "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
             "dtype": ("f32 pair arithmetic, f64 accumulation and integrator (mixed)" if args.path == "f32-pairs" else "f64"),
@@ -854,54 +904,62 @@ def main():
                                                      "unit": "T lane-ops/s", "frac": lane_ops / 1e12 / (FP64_VECTOR_PEAK_TFLOPS / 2.0),
                                                      "valu_wave_insts_per_launch": valu_insts}
             out["fp64"]["valu_issue"] = out["roofline"]["fp64"]["valu_issue"]
-        if world == 1 and not args.no_cpu_baseline and n != N_BODIES and not sharded:
-            out["cpu_baseline"] = sharded_cpu_baseline(pos, mu, n)
-        if world == 1 and not args.no_cpu_baseline and n == N_BODIES and args.path != "f32-pairs":
-            base, o = cpu_baseline(pos, vel, mu, args.cpu_steps)
-            out["cpu_baseline"] = base
-            # parity beside the number: a fresh GPU run of the same steps vs the oracle
-            c = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
-            if fast:
-                c.set_path(fast_path)
-            nsteps = o.state()[3]                            # the oracle went on for the all-cores sample
-            c.advance(nsteps)
-            dp = np.abs(c.state()[0] - o.state()[0]).max()
-            out["parity"] = {"max_abs_dpos": float(dp), "steps": int(nsteps), "vs": "oracle (port)"}
-        if world == 1 and not args.no_cpu_baseline and sharded:
-            out["cpu_baseline"] = sharded_cpu_baseline(pos, mu, n)
-        if world == 1 and args.path == "f32-pairs":
-            # what the mixed path is to be judged against: the build's own exact f64 path on the same system
-            ex = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
-            mx = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
-            mx.set_path(fast_path)
-            done, dv = 0, {}
-            for k in (12 + 10, 12 + 100, 12 + 1000):
-                if n > 16384 and k > 12 + 100:
-                    break                                   # (an exact step of 65 536 bodies is 8 ms; keep the default run short)
-                ex.advance(k - done); mx.advance(k - done)
-                done = k
-                dv[str(k - 12)] = float(np.abs(mx.state()[0] - ex.state()[0]).max())
-            a_ex, a_mx = ex.acc(), mx.acc()
-            out["parity"] = {"vs": "this library's exact f64 path on the same system (the reference has no f32 path)",
-                             "max_abs_dpos_after_steady_steps": dv,
-                             "max_rel_dacc": float(np.abs(a_mx - a_ex).max() / np.abs(a_ex).max())}
-        fx = ROOT / "tests" / "golden" / "plummer4096_horizon.npz"
-        if world == 1 and n == N_BODIES and not sharded and args.horizon > 0 and fx.exists() and args.path != "f32-pairs":
-            # north_star: "positions within 1e-9 AU of the reference over 1e5 steps": max |dpos| against the oracle's
-            # committed positions (generator tests/golden/make_plummer_horizon.py) at every 10^k-th step
-            ref = np.load(fx)
-            c = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
-            if fast:
-                c.set_path(fast_path)
-            done, hz = 0, {}
-            for k in (int(x) for x in ref["checkpoints"]):
-                if k > args.horizon:
-                    break
-                c.advance(k - done)
-                done = k
-                hz[str(k)] = float(np.abs(c.state()[0] - ref[f"pos_{k}"]).max())
-            out.setdefault("parity", {})["horizon_max_abs_dpos"] = hz
-            out["parity"]["horizon_vs"] = "oracle positions, tests/golden/plummer4096_horizon.npz (N-body units: length scale 1)"
+        if args.full:
+            out.update(blocks=len(spread), ms_per_step_min=t_min / args.steps * 1e3, ms_per_step_median=t_med / args.steps * 1e3,
+                       ms_per_step_max=t_max / args.steps * 1e3)
+            out["timing"] += f"; the spread: the same block timed {len(spread)} times in all, min / median / max over them"
+            out["long_region"] = {"steps": long_reps * args.steps, "ms_per_step": t_long / (long_reps * args.steps) * 1e3,
+                                  "value": units / (t_long / long_reps),
+                                  "note": f"{long_reps} x the K-step block per synchronisation, one region: the block's ramp and "
+                                          "synchronisation amortised (value / ms_per_step above stay the contract's single block)"}
+            if world == 1 and not args.no_cpu_baseline and n != N_BODIES and not sharded:
+                out["cpu_baseline"] = sharded_cpu_baseline(pos, mu, n)
+            if world == 1 and not args.no_cpu_baseline and n == N_BODIES and args.path != "f32-pairs":
+                base, o = cpu_baseline(pos, vel, mu, args.cpu_steps)
+                out["cpu_baseline"] = base
+                # parity beside the number: a fresh GPU run of the same steps vs the oracle
+                c = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
+                if fast:
+                    c.set_path(fast_path)
+                nsteps = o.state()[3]                            # the oracle went on for the all-cores sample
+                c.advance(nsteps)
+                dp = np.abs(c.state()[0] - o.state()[0]).max()
+                out["parity"] = {"max_abs_dpos": float(dp), "steps": int(nsteps), "vs": "oracle (port)"}
+            if world == 1 and not args.no_cpu_baseline and sharded:
+                out["cpu_baseline"] = sharded_cpu_baseline(pos, mu, n)
+            if world == 1 and args.path == "f32-pairs":
+                # what the mixed path is to be judged against: the build's own exact f64 path on the same system
+                ex = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
+                mx = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
+                mx.set_path(fast_path)
+                done, dv = 0, {}
+                for k in (12 + 10, 12 + 100, 12 + 1000):
+                    if n > 16384 and k > 12 + 100:
+                        break                                   # (an exact step of 65 536 bodies is 8 ms; keep the default run short)
+                    ex.advance(k - done); mx.advance(k - done)
+                    done = k
+                    dv[str(k - 12)] = float(np.abs(mx.state()[0] - ex.state()[0]).max())
+                a_ex, a_mx = ex.acc(), mx.acc()
+                out["parity"] = {"vs": "this library's exact f64 path on the same system (the reference has no f32 path)",
+                                 "max_abs_dpos_after_steady_steps": dv,
+                                 "max_rel_dacc": float(np.abs(a_mx - a_ex).max() / np.abs(a_ex).max())}
+            fx = ROOT / "tests" / "golden" / "plummer4096_horizon.npz"
+            if world == 1 and n == N_BODIES and not sharded and args.horizon > 0 and fx.exists() and args.path != "f32-pairs":
+                # north_star: "positions within 1e-9 AU of the reference over 1e5 steps": max |dpos| against the oracle's
+                # committed positions (generator tests/golden/make_plummer_horizon.py) at every 10^k-th step
+                ref = np.load(fx)
+                c = ea.NBodyIntegration(pos, vel, mu, 0.0, H)
+                if fast:
+                    c.set_path(fast_path)
+                done, hz = 0, {}
+                for k in (int(x) for x in ref["checkpoints"]):
+                    if k > args.horizon:
+                        break
+                    c.advance(k - done)
+                    done = k
+                    hz[str(k)] = float(np.abs(c.state()[0] - ref[f"pos_{k}"]).max())
+                out.setdefault("parity", {})["horizon_max_abs_dpos"] = hz
+                out["parity"]["horizon_vs"] = "oracle positions, tests/golden/plummer4096_horizon.npz (N-body units: length scale 1)"
     if want_strong:
         # The strong-scaling leg runs AFTER the main line is complete and under a watchdog: a transport that hangs on hardware
         # it has never met (instead of raising) must not cost the run its number. On expiry rank 0 prints the line with the
@@ -947,9 +1005,9 @@ def main():
             out["sharded_4096"] = strong
             if c4 is not None:
                 out["configs4_f32_sharded"] = c4
-    if rank == 0 and world == 1 and n == N_BODIES and not sharded and not fast and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and n == N_BODIES and not sharded and not fast and not args.no_other_configs:
         out["other_variants"] = other_variants(pos, vel, mu)
-    if (rank == 0 and world == 1 and n == N_BODIES and not sharded and not fast and not args.no_cpu_baseline
+    if (args.full and rank == 0 and world == 1 and n == N_BODIES and not sharded and not fast and not args.no_cpu_baseline
             and not args.no_other_configs):
         out["other_configs"] = other_configs()
     if rank == 0:

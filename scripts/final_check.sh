@@ -8,5 +8,5 @@ T="timeout -k 5 -s KILL"
 $T 600 python -m pytest tests -m gpu -x -q > $OUT/pytest.txt 2>&1
 grep -E "passed|failed|error" $OUT/pytest.txt | tail -3
 $T 120 python -c 'import __graft_entry__ as g; g.smoke(); print("__SMOKE_OK__")' 2>&1 | tail -2 | tee $OUT/smoke.txt
-$T 150 python bench.py --workload craft --steps 5 > $OUT/bench_craft.json 2> $OUT/bench_craft.err
+$T 150 python bench.py --workload craft --steps 5 --full > $OUT/bench_craft.json 2> $OUT/bench_craft.err
 tail -c 600 $OUT/bench_craft.json

@@ -44,7 +44,7 @@ def _run(args, ranks):
 
 
 def test_default_line_single_gpu():
-    d = _run(["--steps", "10", "--warmup", "3", "--cpu-steps", "3", "--horizon", "100", "--prewarm", "0.2"], 1)
+    d = _run(["--steps", "10", "--warmup", "3", "--cpu-steps", "3", "--horizon", "100", "--prewarm", "0.2", "--full"], 1)
     assert d["n_gpus"] == 1 and d["steps"] == 10 and d["metric"] == "body-steps/s" and d["dtype"] == "f64"
     assert d["value"] > 1e6                                        # the north star's floor
     assert d["parity"]["max_abs_dpos"] == 0.0 and set(d["parity"]["horizon_max_abs_dpos"].values()) == {0.0}
@@ -55,6 +55,7 @@ def test_default_line_single_gpu():
     assert d["pair_variant"] == 0 and set(d["other_variants"]) == {"1", "2", "3", "4", "5", "6"}
     assert d["roofline"]["binding"] == "fp64_valu" and 0.05 < d["roofline"]["fp64"]["frac"] < 0.5
     assert d["long_region"]["steps"] == 100 and d["long_region"]["ms_per_step"] <= d["ms_per_step"] * 1.02
+    assert d["blocks"] >= 4 and d["ms_per_step_min"] <= d["ms_per_step"] <= d["ms_per_step_max"]    # the headline block + the spread's
     oc = d["other_configs"]
     assert oc["configs1_full_solar_system"]["bodies"] == 32 and 0.1 < oc["configs1_full_solar_system"]["us_per_step"] < 5.0
     assert oc["configs3_craft_sweep"]["value"] > 1e7 and "craft" in oc["configs3_craft_sweep"]["workload"]
@@ -72,6 +73,28 @@ def test_default_line_single_gpu():
         assert r["traffic_profile_commit"] and r["fp64"]["valu_issue"]["frac"] > 0.3
 
 
+def test_plain_line_times_its_steps_and_dumps_the_state_they_ended_in(gpu, tmp_path):
+    """Without --full the line is the headline alone (K timed steps, no companions); --dump-outputs writes the state after the
+    timed steps, bit for bit what the same start-up + warm-up + K steps give in this process."""
+    import numpy as np
+    from ephemeris_explorer_amd.workloads import plummer
+    d = _run(["--steps", "10", "--warmup", "3", "--prewarm", "0.2", "--dump-outputs", str(tmp_path)], 1)
+    assert d["steps"] == 10 and d["warmup"] == 3 and d["metric"] == "body-steps/s" and d["dtype"] == "f64"
+    assert d["value"] > 1e6 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 4096) < 1e-6 * 4096
+    assert d["roofline"]["launches"] == 10                         # exactly the K timed steps
+    for k in ("cpu_baseline", "parity", "long_region", "blocks", "other_variants", "other_configs"):
+        assert k not in d
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["positions.npy", "time.npy", "velocities.npy"]
+    pos, vel, mu = plummer(4096, seed=20260926)
+    g = gpu.NBodyIntegration(pos, vel, mu, 0.0, 1.0 / 1024.0)
+    for k in (12, 3, 10):                                          # start-up, warm-up, the timed block
+        g.advance(k)
+    p, v, t, _ = g.state()
+    dp, dv, dt = (np.load(tmp_path / f) for f in ("positions.npy", "velocities.npy", "time.npy"))
+    assert dp.dtype == dv.dtype == dt.dtype == np.float64
+    assert np.array_equal(dp, p) and np.array_equal(dv, v) and dt.tolist() == [t]
+
+
 def test_two_ranks_replicas():
     d = _run(["--steps", "10", "--warmup", "3", "--prewarm", "0"], 2)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 1e6
@@ -82,8 +105,8 @@ def test_gpus_flag_without_a_launcher_spawns_its_own_ranks():
     becomes the launcher (torch.distributed.run on 127.0.0.1) and still prints ONE JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["EPH_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--prewarm", "0"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--prewarm", "0",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -114,8 +137,8 @@ def test_a_strong_scaling_leg_that_never_returns_does_not_cost_the_line():
     the leg can finish; rank 0 still prints the one line (the leg marked as timed out) and the job ends with status 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(EPH_BENCH_BACKEND="gloo", EPH_BENCH_SHARDED_TIMEOUT="0")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--prewarm", "0"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--prewarm", "0",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -126,7 +149,7 @@ def test_a_strong_scaling_leg_that_never_returns_does_not_cost_the_line():
 @pytest.mark.parametrize("population", ["transfer", "mixed"])
 def test_two_ranks_craft_sweep_with_result_gather(population):
     d = _run(["--workload", "craft", "--craft", "4001", "--craft-days", "0.05", "--steps", "1", "--prewarm", "0",
-              "--population", population], 2)
+              "--population", population, "--full"], 2)
     assert d["n_gpus"] == 2 and d["metric"] == "craft-steps/s" and "all-gather" in d["config"]["exchange"]
     assert d["divergence"]["attempts_max_over_mean_per_wave"] >= 1.0
     assert (population == "mixed") == ("population" in d["config"]["workload"])
@@ -157,8 +180,8 @@ def test_configs4_leg_of_the_default_multi_rank_line():
     partitioned) against rank 0's single-device f32 run; on this one-GPU box the leg is asked for explicitly at a small size."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(EPH_BENCH_BACKEND="gloo", EPH_BENCH_CONFIGS4_BODIES="4096")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--prewarm", "0"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--prewarm", "0",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     c4 = d["configs4_f32_sharded"]

@@ -26,6 +26,21 @@ def test_timed_blocks_times_the_block_repeatedly_and_agrees_on_the_count():
     assert len(b.timed_blocks(lambda: None, lambda: None, lambda t: 1.0, blocks=5)) == 5  # --blocks overrides
 
 
+def test_dump_outputs_writes_float64_and_a_fixed_sample_above_the_limit(tmp_path):
+    b = _bench()
+    pos = np.arange(300.0).reshape(100, 3)
+    assert b.dump_outputs(tmp_path / "all", {"positions": pos, "time": [2.5]}) == ["positions.npy", "time.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "positions.npy"), pos) and np.load(tmp_path / "all" / "time.npy").tolist() == [2.5]
+    big = np.arange(4000, dtype=np.float32).reshape(1000, 4)
+    for d in ("s1", "s2"):
+        assert b.dump_outputs(tmp_path / d, {"states": big}, limit=8000) == ["states.npy", "states_rows.npy"]
+    s1, r1 = np.load(tmp_path / "s1" / "states.npy"), np.load(tmp_path / "s1" / "states_rows.npy")
+    assert s1.dtype == r1.dtype == np.float64 and s1.nbytes + r1.nbytes <= 8000 and len(s1) == len(r1) > 100
+    assert np.array_equal(s1, big[r1.astype(np.int64)]) and (np.diff(r1) > 0).all()
+    assert np.array_equal(s1, np.load(tmp_path / "s2" / "states.npy"))                  # the same sample every run
+    assert b.DUMP_LIMIT_BYTES < 64e6
+
+
 def test_wave_divergence():
     from ephemeris_explorer_amd.workloads import wave_divergence
     assert wave_divergence([7] * 640) == 1.0
