@@ -7,17 +7,17 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "libephemeris_amd.so"
-# the product's objects + debug_api.o: the eph_debug_* test hooks (csrc/eph_debug.h), for tests/ only -- the product never loads it
+# the product's objects + debug_api.o + debug_kernels.o: the eph_debug_* test hooks (csrc/eph_debug.h), for tests/ only -- the product never loads it
 HOOKS_LIB = HERE / "libephemeris_amd_testhooks.so"
-HOOKS_SOURCES = ["debug_api.cpp"]
+HOOKS_SOURCES = ["debug_api.cpp", "debug_kernels.hip"]
 N_PAIR_VARIANTS = 7      # csrc/pair_term.h: the evaluation orders of the unpinned point-mass term, all in the one library
 # compiled once per evaluation order (-DEPH_PAIR_VARIANT=k, every symbol in namespace eph::pv<k>; csrc/pair_ns.h)
 PAIR_SOURCES = ["step_wg.hip", "step_wave.hip", "step_small.hip", "fast.hip", "craft_sweep.hip"]
 # compiled once
-SOURCES = ["solout.hip", "craft.hip", "peer.hip", "dispatch.cpp", "mem.cpp", "coeffs.cpp", "nbody.cpp", "propagator.cpp", "shard.cpp", "api.cpp"]
+SOURCES = ["solout.hip", "craft.hip", "craft_events.hip", "ephemeris_table.hip", "evaluators.hip", "peer.hip", "dispatch.cpp", "mem.cpp", "coeffs.cpp", "nbody.cpp", "propagator.cpp", "shard.cpp", "api.cpp"]
 EXPORTS = CSRC / "exports.map"      # linker version script: only eph_* is a dynamic symbol
-HEADERS = ["exports.map", "eph_internal.h", "eph_debug.h", "host.h", "ieee_seq.h", "pair_term.h", "pair_ns.h", "pair_launchers.h", "force_common.h", "craft_device.h",
-           "coeff_tables.inc", "cr_pow_tables.inc", "craft_attempt.inc", "../../include/ephemeris_amd.h"]
+# every header of csrc/ (none can be forgotten: an object older than any of them is recompiled) + the public one
+HEADERS = sorted(p.name for pat in ("*.h", "*.inc", "exports.map") for p in CSRC.glob(pat)) + ["../../include/ephemeris_amd.h"]
 # -ffp-contract=off is REQUIRED for parity (HIP's default is fast contraction): the reference never fuses a*b+c.
 # -fvisibility=hidden: the library exports the extern "C" boundary of include/ephemeris_amd.h and nothing else
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",

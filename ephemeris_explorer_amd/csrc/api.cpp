@@ -47,7 +47,7 @@ struct eph_prop {
         return EPH_ERR_HIP;                             \
     }
 
-// the library is compiled with -fvisibility=hidden: the boundary below (and craft.hip's half of it) is ALL it exports
+// the library is compiled with -fvisibility=hidden: the boundary below (and the rest of it in craft.hip, craft_events.hip, ephemeris_table.hip, evaluators.hip) is ALL it exports
 #pragma GCC visibility push(default)
 extern "C" {
 

@@ -1,6 +1,6 @@
 /* eph_debug.h -- test and tuning hooks. NOT part of the drop-in boundary (include/ephemeris_amd.h): no trait of the reference
- * corresponds to them. Their extern "C" entry points are compiled in debug_api.cpp, which is linked into
- *   - libephemeris_amd_testhooks.so (the product's objects + debug_api.o; tests/hooks.py loads it), and
+ * corresponds to them. Their extern "C" entry points are compiled in debug_api.cpp (device halves: debug_kernels.hip), which is linked into
+ *   - libephemeris_amd_testhooks.so (the product's objects + debug_api.o + debug_kernels.o; tests/hooks.py loads it), and
  *   - tuning builds (scripts/build_exp.sh NAME -DEPH_EXPERIMENTS=1 ...),
  * never into libephemeris_amd.so. */
 #pragma once
@@ -36,7 +36,7 @@ int32_t eph_debug_wg_cycles(int64_t *out8);
 #endif
 
 #ifdef __cplusplus
-namespace eph {                 /* the device halves that live beside their kernels (craft.hip) */
+namespace eph {                 /* the device halves that live beside their kernels (debug_kernels.hip) */
 int debug_div_device(int64_t n, const double *a, const double *b, double *fast, double *ieee);
 int debug_rsq_device(int64_t n, const double *x, double *rsq, double *h);
 int debug_pow_device(int64_t n, const double *x, double y, double *out);

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Is the device code of two builds the same code? For every kernel (`.amdhsa_kernel` symbol) of two gfx950 assembly files, or of
+every compiled-once .hip unit of two source trees, compares the kernel descriptor block and the instruction text between the
+symbol's label and its `.Lfunc_end`, with `;` comments dropped and the function index in `.LBB<n>_` labels normalised (it changes
+when a kernel changes file; nothing else should). For a refactor that moves kernels between units.
+
+    compare_kernels.py A.s B.s
+    compare_kernels.py TREE_A TREE_B        # compiles SOURCES + HOOKS_SOURCES (*.hip) of each tree's build.py with its FLAGS
+
+Exit status 0: the same kernel names on both sides, every one identical. No GPU needed."""
+import re
+import runpy
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+
+def normalise(lines):
+    out = []
+    for ln in lines:
+        ln = re.sub(r"\.LBB\d+_", ".LBB_", ln.split(";", 1)[0]).strip()
+        if ln:
+            out.append(ln)
+    return out
+
+
+def kernels(path):
+    """{kernel symbol: (normalised descriptor block, normalised instruction text)} of one assembly file"""
+    lines = Path(path).read_text().split("\n")
+    desc, at = {}, {}
+    for i, ln in enumerate(lines):                          # `symbol:` at the start of a line, a comment may follow
+        m = re.match(r"([A-Za-z_$][\w$.]*):", ln)
+        if m:
+            at.setdefault(m.group(1), i)
+    for i, ln in enumerate(lines):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
+        if m:
+            end = next(j for j in range(i, len(lines)) if lines[j].strip() == ".end_amdhsa_kernel")
+            desc[m.group(1)] = normalise(lines[i:end + 1])
+    out = {}
+    for name, d in desc.items():
+        end = next(j for j in range(at[name], len(lines)) if re.match(r"\.Lfunc_end\d+:", lines[j]))
+        regs = [ln for ln in lines if re.match(rf"\s*\.set\s+{re.escape(name)}\.", ln)]      # the resource usage the descriptor refers to
+        out[name] = (d + normalise(regs), normalise(lines[at[name] + 1:end]))
+    return out
+
+
+def tree_kernels(tree, tmp):
+    """{kernel symbol: (unit, descriptor, text)} of the compiled-once .hip units of a source tree"""
+    b = runpy.run_path(str(Path(tree) / "ephemeris_explorer_amd" / "build.py"), run_name="build")
+    srcs = [s for s in b["SOURCES"] + b["HOOKS_SOURCES"] if s.endswith(".hip")]
+
+    def one(src):
+        out = Path(tmp) / (src[:-4] + ".s")
+        subprocess.run([b["hipcc"](), *b["FLAGS"], "--offload-device-only", "-S", "-x", "hip", str(b["CSRC"] / src), "-o", str(out)],
+                       check=True, stderr=subprocess.DEVNULL)
+        return {k: (src, *v) for k, v in kernels(out).items()}
+    found = {}
+    with ThreadPoolExecutor(8) as ex:
+        for part in ex.map(one, srcs):
+            assert not (set(part) & set(found)), "a kernel defined in two units"
+            found.update(part)
+    return found
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return {n: re.sub(r"\(.*", "", d).replace("void ", "") for n, d in zip(names, out)}
+
+
+def main(a, b):
+    if Path(a).is_dir():
+        with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
+            ka, kb = tree_kernels(a, ta), tree_kernels(b, tb)
+    else:
+        ka, kb = ({k: (Path(p).name, *v) for k, v in kernels(p).items()} for p in (a, b))
+    short = demangle(sorted(set(ka) | set(kb)))
+    bad = moved = 0
+    for k in sorted(set(ka) | set(kb), key=lambda k: short[k]):
+        if k not in ka or k not in kb:
+            print(f"ONLY IN {'A' if k in ka else 'B'}  {short[k]}  ({(ka.get(k) or kb.get(k))[0]})")
+            bad += 1
+            continue
+        same = ka[k][1:] == kb[k][1:]
+        bad += not same
+        moved += ka[k][0] != kb[k][0]
+        print(f"{'same' if same else 'DIFF'}  {short[k]:<44} {len(ka[k][2]):>6} lines  {ka[k][0]} -> {kb[k][0]}")
+    print(f"{len(set(ka) | set(kb))} kernels, {moved} in another unit, {bad} different or missing")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    sys.exit(main(sys.argv[1], sys.argv[2]))

@@ -1,5 +1,5 @@
 """The eph_debug_* test and tuning hooks (csrc/eph_debug.h). They are NOT in the product library: `load()` opens
-libephemeris_amd_testhooks.so (the product's objects + debug_api.o, built by ephemeris_explorer_amd.build) or, for the scripts that
+libephemeris_amd_testhooks.so (the product's objects + debug_api.o + debug_kernels.o, built by ephemeris_explorer_amd.build) or, for the scripts that
 read a tuning build's accounting, the library named by `path`. TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 from pathlib import Path
