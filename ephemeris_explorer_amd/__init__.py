@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "eph_ephemeris_is_valid_at", "eph_ephemeris_export", "eph_ephemeris_import", "eph_craft_batch_retry_failed",
     "eph_ephemeris_interpolation_errors", "eph_craft_batch_create", "eph_craft_batch_set_body_order", "eph_craft_batch_propagate", "eph_craft_batch_step_n",
     "eph_craft_batch_status", "eph_craft_batch_state", "eph_craft_batch_summary", "eph_craft_batch_knots", "eph_craft_batch_kernel_time",
-    "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
+    "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_eval", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
     "eph_craft_batch_destroy", "eph_hermite_eval", "eph_hermite_join", "eph_transitions_join", "eph_apsides_join", "eph_plot_points",
 ]
 
@@ -209,6 +209,7 @@ def _lib():
     L.eph_solution_between.argtypes = [vp, f64, f64, C.POINTER(vp)]
     L.eph_craft_batch_step_n.argtypes = [vp, C.c_uint32]
     L.eph_craft_batch_knot_slabs.argtypes = [vp, i32, i32, _dp, _dp]
+    L.eph_craft_batch_eval.argtypes = [vp, i64, _dp, i32, i32, _dp, _u8p]
     L.eph_craft_batch_reset_knots.argtypes = [vp]
     L.eph_craft_batch_reset_events.argtypes = [vp]
     L.eph_timeline_divergence_time.argtypes = [i64, _dp, _dp, _dp, _i32p, i64, _dp, _dp, _dp, _i32p, f64, _dp]
@@ -860,6 +861,27 @@ class SpacecraftBatch:
         _check(self._L.eph_craft_batch_knot_slabs(self._h, int(first_knot), int(n_knots), _p(t), _p(y)),
                "eph_craft_batch_knot_slabs")
         return t, y
+
+    def eval(self, at, reference_body=-1, raw=False):
+        """Where is every craft at the epochs `at`, relative to body `reference_body` of the ephemeris (table order; -1 =
+        inertial): EvaluateTrajectory::state_vector on every craft's knots, on the device (eph_craft_batch_eval).
+        `at` of shape (m,): the same epochs for every craft; (m, n): every craft its own. Returns
+        (pos[m, n, 3], vel[m, n, 3], inside[m, n]); raw=True: (y[m, 6, n], inside[m, n]), the device layout, no transpose.
+        Entries the reference answers None (outside the craft's knots or the body's spline) are zero with inside False."""
+        at = _f64(at)
+        if at.ndim == 0:
+            at = at.reshape(1)
+        if at.ndim not in (1, 2) or (at.ndim == 2 and at.shape[1] != self.n):
+            raise ValueError("SpacecraftBatch.eval: `at` has shape (m,) or (m, n)")
+        m = at.shape[0]
+        y = np.zeros((m, 6, self.n))
+        inside = np.zeros((m, self.n), dtype=np.uint8)
+        _check(self._L.eph_craft_batch_eval(self._h, m, _p(at), 1 if at.ndim == 2 else 0, int(reference_body), _p(y),
+                                            _p(inside, _u8p)), "eph_craft_batch_eval")
+        inside = inside.astype(bool)
+        if raw:
+            return y, inside
+        return (np.ascontiguousarray(y[:, :3].transpose(0, 2, 1)), np.ascontiguousarray(y[:, 3:].transpose(0, 2, 1)), inside)
 
     def reset_knots(self):
         """Keep only the newest knot of every craft (as knot 0) and clear KNOTS_FULL: the drain point of a long run."""

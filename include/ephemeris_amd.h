@@ -419,6 +419,25 @@ int32_t eph_craft_batch_clone(eph_craft_batch *b, eph_craft_batch **out);
  * through a temporary of the requested size on the device.) */
 int32_t eph_craft_batch_knot_slabs(eph_craft_batch *b, int32_t first_knot, int32_t n_knots, double *knot_t,
                                    double *knot_y);
+/* Where is every craft at epoch T, relative to body B: EvaluateTrajectory::state_vector of every craft's
+ * CubicHermiteSpline (ephemeris/src/trajectory.rs:766-797), optionally as RelativeTrajectory::state_vector against one
+ * body of the bound ephemeris (:326-334), at m epochs, evaluated on the device from the knot slabs.
+ * per_craft == 0: at[m], the same epochs for every craft, in any order; per_craft == 1: at[e * n + craft], every craft
+ * its own epochs. reference_body: -1 = none (inertial), otherwise a body index in the ephemeris's table order (as in
+ * eph_plot_request.reference_body; eph_craft_batch_set_body_order does not affect it).
+ * out_y[e][d][craft], d = x, y, z, vx, vy, vz (the layout of eph_craft_batch_knot_slabs), in craft order whatever order
+ * the craft were dealt to the lanes in; inside[e][craft] = 1 for Some, 0 for None (may be NULL); a None entry's six
+ * values are +0.0. The spline part is bit for bit what eph_hermite_eval computes on the craft's current knots
+ * 0 .. nknots - 1 (an epoch equal to a knot returns the knot's own state; None before the first and after the last knot,
+ * so after eph_craft_batch_reset_knots only the drained slab's span is covered). With a reference body its
+ * UniformSpline::state_vector from the LIVE table (bit-identical to eph_solution_eval) is evaluated first: None where
+ * the body's spline does not contain the epoch, otherwise position - ref_position, velocity - ref_velocity.
+ * Does not change the batch (state, knots, events, a pending retry and the FSAL stages are untouched); works on clones.
+ * m == 0 or an empty batch: EPH_OK, nothing written. EPH_ERR_BAD_ARGUMENT (nothing written): NULL batch, m < 0, NULL
+ * `at` or out_y with work to do, reference_body < -1 or >= n_bodies, per_craft not 0 / 1. The result is produced in
+ * passes over epochs of at most 256 MB each. */
+int32_t eph_craft_batch_eval(eph_craft_batch *b, int64_t m, const double *at, int32_t per_craft,
+                             int32_t reference_body, double *out_y, uint8_t *inside);
 /* Flight-plan restart (ephemeris_explorer/src/flight_plan.rs:263-303): Timeline::divergence_time_before
  * (ephemeris/src/propagators/spacecraft.rs:179-213) of the NEW burn list against the OLD one -- the start of the last
  * segment, earlier than `before`, up to which both timelines agree; the caller restarts a craft from the knot at

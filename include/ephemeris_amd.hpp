@@ -453,6 +453,27 @@ public:
         knots(craft, nk[static_cast<size_t>(craft)], sp.t, sp.position, sp.velocity);
         return sp;
     }
+    // EvaluateTrajectory::state_vector of EVERY craft's trajectory at the epochs `at` (trajectory.rs:766-797), with reference_body >= 0
+    // as RelativeTrajectory<&SpacecraftTrajectory, &Trajectory> against that body of the ephemeris (table order; :326-334), on the
+    // device. at.size() = m: the same epochs for every craft; per_craft: at[e * len() + craft], every craft its own.
+    // out[e * len() + craft] is the Some(state vector); inside[e * len() + craft] = 0 where the reference returns None (a zero entry).
+    void state_vectors_at(const std::vector<double> &at, std::vector<StateVector> &out, std::vector<uint8_t> &inside, int32_t reference_body = -1,
+                          bool per_craft = false) const {
+        const size_t n = static_cast<size_t>(n_);
+        if (per_craft && (n == 0 || at.size() % n != 0)) throw std::invalid_argument("SpacecraftBatch::state_vectors_at: one epoch row per craft");
+        const size_t m = per_craft ? at.size() / n : at.size();
+        std::vector<double> y(m * 6 * n);
+        inside.assign(m * n, 0);
+        detail::check(eph_craft_batch_eval(h_, static_cast<int64_t>(m), at.data(), per_craft ? 1 : 0, reference_body, y.data(), inside.data()),
+                      "eph_craft_batch_eval");
+        out.resize(m * n);
+        for (size_t e = 0; e < m; ++e)
+            for (size_t c = 0; c < n; ++c)
+                for (size_t d = 0; d < 3; ++d) {
+                    out[e * n + c].position[d] = y[(e * 6 + d) * n + c];
+                    out[e * n + c].velocity[d] = y[(e * 6 + 3 + d) * n + c];
+                }
+    }
     // problem.{time, state} and the controller's next step size of every craft
     void state(std::vector<double> &t, std::vector<DVec3> &position, std::vector<DVec3> &velocity, std::vector<double> *next_h = nullptr) const {
         const size_t n = static_cast<size_t>(n_);
