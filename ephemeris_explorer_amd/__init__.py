@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "eph_ephemeris_is_valid_at", "eph_ephemeris_export", "eph_ephemeris_import", "eph_craft_batch_retry_failed",
     "eph_ephemeris_interpolation_errors", "eph_craft_batch_create", "eph_craft_batch_set_body_order", "eph_craft_batch_propagate", "eph_craft_batch_step_n",
     "eph_craft_batch_status", "eph_craft_batch_state", "eph_craft_batch_summary", "eph_craft_batch_knots", "eph_craft_batch_kernel_time",
-    "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_eval", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
+    "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_eval", "eph_craft_batch_restart", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
     "eph_craft_batch_destroy", "eph_hermite_eval", "eph_hermite_join", "eph_transitions_join", "eph_apsides_join", "eph_plot_points",
 ]
 
@@ -210,6 +210,7 @@ def _lib():
     L.eph_craft_batch_step_n.argtypes = [vp, C.c_uint32]
     L.eph_craft_batch_knot_slabs.argtypes = [vp, i32, i32, _dp, _dp]
     L.eph_craft_batch_eval.argtypes = [vp, i64, _dp, i32, i32, _dp, _u8p]
+    L.eph_craft_batch_restart.argtypes = [vp, _u8p, _i64p, _dp, _dp, _dp, _i32p, _dp, C.POINTER(AdaptiveParams), _dp, _i32p]
     L.eph_craft_batch_reset_knots.argtypes = [vp]
     L.eph_craft_batch_reset_events.argtypes = [vp]
     L.eph_timeline_divergence_time.argtypes = [i64, _dp, _dp, _dp, _i32p, i64, _dp, _dp, _dp, _i32p, f64, _dp]
@@ -882,6 +883,41 @@ class SpacecraftBatch:
         if raw:
             return y, inside
         return (np.ascontiguousarray(y[:, :3].transpose(0, 2, 1)), np.ascontiguousarray(y[:, 3:].transpose(0, 2, 1)), inside)
+
+    UNSELECTED = np.iinfo(np.int32).min     # restart(): the outcome entry of a craft `which` did not select (never written)
+
+    def restart(self, burns, plan_end=None, params=None, which=None):
+        """Flight-plan restart in place (eph_craft_batch_restart): every selected craft continues from the knot where its new
+        flight plan `burns` (the constructor's per-craft lists) diverges from the old one, as the app's new propagator would.
+        plan_end: FlightPlan.end, a scalar or one per craft (None: +inf). params: new AdaptiveParams for the whole batch
+        (only with which=None). which: a boolean mask or craft indices (None: all). Returns (restart_epoch[n], outcome[n]);
+        an unselected craft's entries are NaN and UNSELECTED."""
+        if len(burns) != self.n:
+            raise ValueError("SpacecraftBatch.restart: one burn list per craft")
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        flat = []
+        for i, bl in enumerate(burns):
+            flat.extend(bl)
+            off[i + 1] = len(flat)
+        _, bs, be, ba, br = _burn_arrays(flat)
+        pe = None if plan_end is None else _f64(np.broadcast_to(np.asarray(plan_end, dtype=np.float64), (self.n,)))
+        sel = None
+        if which is not None:
+            w = np.asarray(which)
+            sel = np.zeros(self.n, dtype=np.uint8)
+            if w.dtype == bool:
+                sel[:] = w.reshape(self.n)
+            else:
+                sel[w.astype(np.int64)] = 1
+        epoch = np.full(self.n, np.nan)
+        outcome = np.full(self.n, self.UNSELECTED, dtype=np.int32)
+        _check(self._L.eph_craft_batch_restart(self._h, None if sel is None else _p(sel, _u8p), _p(off, _i64p), _p(bs), _p(be), _p(ba),
+                                               _p(br, _i32p), None if pe is None else _p(pe),
+                                               None if params is None else C.byref(params), _p(epoch), _p(outcome, _i32p)),
+               "eph_craft_batch_restart")
+        if params is not None:
+            self.params = params
+        return epoch, outcome
 
     def reset_knots(self):
         """Keep only the newest knot of every craft (as knot 0) and clear KNOTS_FULL: the drain point of a long run."""

@@ -302,8 +302,8 @@ static bool craft_time_scales_differ(const eph_ephemeris &e, long long n, const 
 
 // Timeline::new  ephemeris/src/propagators/spacecraft.rs:129-152: stable sort by start, coast segments in the gaps,
 // from Epoch::MIN to Epoch::MAX; appended to `segs`
-static void timeline_new(long long nburns, const double *burn_start, const double *burn_end, const double *burn_acc,
-                         const int32_t *burn_ref, std::vector<SegmentDev> &segs) {
+void eph::timeline_new(long long nburns, const double *burn_start, const double *burn_end, const double *burn_acc,
+                       const int32_t *burn_ref, std::vector<SegmentDev> &segs) {
     const double EMIN = -1.7976931348623157e308, EMAX = 1.7976931348623157e308;   // Epoch::MIN / MAX
     std::vector<long long> order;
     for (long long q = 0; q < nburns; ++q) order.push_back(q);
@@ -398,7 +398,8 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
             (st = b->status.alloc(nn)) || (st = b->nknots.alloc(nn)) || (st = b->seg_off.alloc(n + 1)) ||
             (st = b->segs.alloc(std::max<size_t>(segs.size(), 1))) || (st = b->knot_t.alloc(nn * max_knots)) ||
             (st = b->knot_y.alloc(6 * nn * max_knots)) || (st = b->rk_dev.alloc(1)) || (st = b->queue.alloc(1)) ||
-            (st = b->summary.alloc(nn)))               // (here, not at the first eph_craft_batch_summary: keeps hipMalloc out of a sweep)
+            (st = b->summary.alloc(nn)) ||             // (here, not at the first eph_craft_batch_summary: keeps hipMalloc out of a sweep)
+            (st = b->t_start.alloc(nn)))
             return st;
         EPH_HIP(hipMemcpy(b->rk_dev.p, &b->rk, sizeof(ErkCoeffs), hipMemcpyHostToDevice));
         if (n > 0) {
@@ -408,6 +409,7 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
             std::vector<int> ones(n, 1), zeros(n, 0);
             EPH_HIP(hipMemcpy(b->time.p, t0, sizeof(double) * n, hipMemcpyHostToDevice));
             EPH_HIP(hipMemcpy(b->last_knot.p, t0, sizeof(double) * n, hipMemcpyHostToDevice));
+            EPH_HIP(hipMemcpy(b->t_start.p, t0, sizeof(double) * n, hipMemcpyHostToDevice));
             EPH_HIP(hipMemcpy(b->y.p, ysoa.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice));
             EPH_HIP(hipMemcpy(b->klast.p, ysoa.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice));
             EPH_HIP(hipMemcpy(b->kfirst.p, ysoa.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice));   // from_problem: k = [state; STAGES]
@@ -426,6 +428,8 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
             b->heterogeneous = craft_time_scales_differ(*e, n, t0, pos);
             if (!craft_wave_form(n) && (st = craft_sort(b.get()))) return st;
         }
+        b->h_seg_off = std::move(seg_off);
+        b->h_segs = std::move(segs);
         *out = b.release();
         return EPH_OK;
     } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
@@ -682,9 +686,12 @@ int32_t eph_craft_batch_clone(eph_craft_batch *b, eph_craft_batch **out) {
             (st = clone_buf(b->ntr, c->ntr, s)) || (st = clone_buf(b->nap, c->nap, s)) ||
             (st = clone_buf(b->ev_status, c->ev_status, s)) || (st = clone_buf(b->tr_body, c->tr_body, s)) ||
             (st = clone_buf(b->ap_body, c->ap_body, s)) || (st = clone_buf(b->ap_kind, c->ap_kind, s)) ||
-            (st = clone_buf(b->perm, c->perm, s)) || (st = clone_buf(b->slot_of, c->slot_of, s)) || (st = clone_buf(b->bodies_ordered, c->bodies_ordered, s)) || (st = clone_buf(b->body_order_dev, c->body_order_dev, s)) || (st = c->queue.alloc(1)))
+            (st = clone_buf(b->perm, c->perm, s)) || (st = clone_buf(b->slot_of, c->slot_of, s)) || (st = clone_buf(b->bodies_ordered, c->bodies_ordered, s)) || (st = clone_buf(b->body_order_dev, c->body_order_dev, s)) || (st = c->queue.alloc(1)) ||
+            (st = clone_buf(b->t_start, c->t_start, s)))
             return st;
         c->h_slot = b->h_slot;
+        c->h_seg_off = b->h_seg_off;
+        c->h_segs = b->h_segs;
         EPH_HIP(hipStreamSynchronize(s));
         *out = c.release();
         return EPH_OK;

@@ -21,6 +21,9 @@ struct eph_craft_batch {
     eph::DevBuf<int> cur_seg, status, nknots;
     eph::DevBuf<long long> seg_off;
     eph::DevBuf<eph::SegmentDev> segs;
+    std::vector<long long> h_seg_off;         // host mirror of seg_off / segs (eph_craft_batch_restart rebuilds the CSR from it)
+    std::vector<eph::SegmentDev> h_segs;
+    eph::DevBuf<double> t_start;              // creation epoch per craft: the trajectory start of the restart rule (knot 0 moves on a drain)
     eph::DevBuf<eph::ErkCoeffs> rk_dev;
     eph::DevBuf<eph_craft_record> summary;    // eph_craft_batch_summary's device-side records (a clone's: on first use)
     eph::DevBuf<unsigned long long> queue;    // k_craft_queue's work queue (one counter)
@@ -51,4 +54,7 @@ struct eph_craft_batch {
 namespace eph {
 bool craft_wave_form(long long n_craft);                  // craft.hip: one wave per craft (few spacecraft) or one thread
 int craft_events_search(eph_craft_batch *b, hipStream_t s);   // craft_events.hip: the event search on the steps a sweep just took
+// craft.hip: Timeline::new (spacecraft.rs:129-152) of one craft's burns, appended to `segs` (create, restart, divergence time)
+void timeline_new(long long nburns, const double *burn_start, const double *burn_end, const double *burn_acc, const int32_t *burn_ref,
+                  std::vector<SegmentDev> &segs);
 }  // namespace eph

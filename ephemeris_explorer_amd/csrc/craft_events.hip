@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "craft_batch.h"
+#include "craft_events.h"
 
 namespace eph {
 
@@ -19,22 +20,6 @@ namespace eph {
 // One thread per craft walks its new segments in order (the transition list is sequential state). Bodies are
 // visited in body order (the reference iterates an EntityHashMap, whose order is unspecified).
 // ------------------------------------------------------------------------------------------------------
-struct EventArgs {
-    long long n_craft;
-    int n_bodies;
-    const BodyEntry *bodies;
-    const double *coeffs;
-    const int *ncoef;
-    const double *soi;            // [n_bodies] sphere radii (inf for the root)
-    const int *nknots;
-    const double *knot_t, *knot_y;
-    int *ev_seg;                  // next segment (knot pair k, k+1) to examine; -1 = new_solution not yet run
-    int *ntr, *nap, *ev_status;
-    double *tr_time; int *tr_body;                              // [max_tr][n]
-    double *ap_time, *ap_dist; int *ap_body, *ap_kind;          // [max_ap][n]
-    int max_tr, max_ap;
-    const int *slot_of;           // craft -> its column in the knot slabs (null: identity)
-};
 struct Hermite { double b0; V3 a0, a1, a2, a3; };
 __device__ __forceinline__ V3 hermite_pos(const Hermite &h, double t) {      // CubicHermite::eval  trajectory.rs:681-688
     const double dt = t - h.b0;
@@ -43,22 +28,6 @@ __device__ __forceinline__ V3 hermite_pos(const Hermite &h, double t) {      // 
 __device__ __forceinline__ V3 hermite_vel(const Hermite &h, double t) {      // eval_derivative :690-697
     const double dt = t - h.b0;
     return add(scale(add(scale(scale(h.a3, dt), 3.0), scale(h.a2, 2.0)), dt), h.a1);
-}
-__device__ __forceinline__ bool ev_body_pos(const EventArgs &a, int b, double t, V3 &out) {
-    const BodyEntry be = a.bodies[b];
-    long long idx;
-    double tau;
-    if (!spline_locate(be, t, idx, tau)) return false;
-    const double *co = a.coeffs + (be.coeff_off + idx) * kDiv * 3;
-    const int nc = a.ncoef[be.coeff_off + idx];
-    V3 bp = {0.0, 0.0, 0.0};
-    for (int k = nc - 1; k >= 0; --k) {
-        bp.x = bp.x * tau + co[k * 3 + 0];
-        bp.y = bp.y * tau + co[k * 3 + 1];
-        bp.z = bp.z * tau + co[k * 3 + 2];
-    }
-    out = bp;
-    return true;
 }
 __device__ __forceinline__ bool ev_body_sv(const EventArgs &a, int b, double t, V3 &pos, V3 &vel) {
     const BodyEntry be = a.bodies[b];
@@ -123,42 +92,6 @@ __device__ bool find_zero_crossing(const EventArgs &a, const Hermite &h, int bod
         }
     }
     return false;
-}
-// find_soi :172-185,208-221: inside iff d2 < r*r; the closest wins, the first on ties
-__device__ int soi_at_except(const EventArgs &a, double t, V3 position, int except) {
-    int best = -1;
-    double best_d2 = 0.0;
-    for (int b = 0; b < a.n_bodies; ++b) {
-        if (b == except) continue;
-        V3 bp;
-        if (!ev_body_pos(a, b, t, bp)) continue;
-        const V3 d = sub(position, bp);
-        const double d2 = dot(d, d), r = a.soi[b];
-        if (!(d2 < r * r)) continue;
-        if (best < 0 || d2 < best_d2) { best = b; best_d2 = d2; }
-    }
-    return best;
-}
-// SoiTransitions::insert :332-339 on the craft's column of the slab; false = slab full
-__device__ bool tr_insert(const EventArgs &a, long long i, int &ntr, double time, int body) {
-    const long long n = a.n_craft;
-    int lo = 0, hi = ntr;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        const double tm = a.tr_time[(long long)mid * n + i];
-        if (tm == time) { a.tr_body[(long long)mid * n + i] = body; return true; }
-        if (tm < time) lo = mid + 1; else hi = mid;
-    }
-    if (lo > 0 && a.tr_body[(long long)(lo - 1) * n + i] == body) return true;
-    if (ntr >= a.max_tr) return false;
-    for (int k = ntr; k > lo; --k) {
-        a.tr_time[(long long)k * n + i] = a.tr_time[(long long)(k - 1) * n + i];
-        a.tr_body[(long long)k * n + i] = a.tr_body[(long long)(k - 1) * n + i];
-    }
-    a.tr_time[(long long)lo * n + i] = time;
-    a.tr_body[(long long)lo * n + i] = body;
-    ntr += 1;
-    return true;
 }
 __device__ bool ap_insert(const EventArgs &a, long long i, int &nap, double time, double dist, int body, int kind) {
     const long long n = a.n_craft;

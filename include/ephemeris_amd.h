@@ -447,6 +447,34 @@ int32_t eph_timeline_divergence_time(int64_t n_old, const double *old_start, con
                                      const int32_t *old_ref, int64_t n_new, const double *new_start,
                                      const double *new_end, const double *new_acc, const int32_t *new_ref,
                                      double before, double *restart_epoch);
+/* Flight-plan restart of a batch in place: FlightPlan::restart_propagator + apply_flight_plan (ephemeris_explorer/src/
+ * flight_plan.rs:263-303,325-361) for every selected craft, on the device. which[i] != 0 selects craft i (NULL: all). The burns
+ * are the NEW flight plans, CSR over all n craft exactly as in eph_craft_batch_create (burn_offset NULL: no burns; entries of
+ * unselected craft are ignored). plan_end[i] = FlightPlan.end (NULL: +inf). params: NULL keeps the batch's parameters, otherwise
+ * they become the batch's (only with which == NULL); a changed tol_position, tol_velocity or n_max restarts every craft at its
+ * trajectory start (flight_plan.rs:283-288).
+ * Per selected craft: restart epoch = max(divergence_time_before(new, old, min(plan_end, last knot)), creation epoch) -- bit-equal
+ * to eph_timeline_divergence_time -- into restart_epoch[i] (may be NULL; NaN for EPH_ERR_BAD_ARGUMENT); outcome[i] (may be NULL):
+ *   EPH_OK                the craft now is what eph_craft_batch_create gives for (restart epoch, knot state, new burns, batch
+ *                         parameters) -- state, next_h = h_init, attempts 0, FSAL registers from the state, current segment, status
+ *                         EPH_OK (a StepError or EPH_KNOTS_FULL is cleared) -- except that knots 0 .. j stay (j = the restart
+ *                         knot; CubicHermiteSpline join), `steps` keeps counting, and with events on, transitions and apsides are
+ *                         cleared after the epoch, new_solution's entry (epoch, soi_at(knot position)) is inserted as
+ *                         SoiTransitions::insert does, EPH_EVENTS_FULL is cleared and the search resumes at knot j;
+ *   EPH_EVAL_FAILED       no knot has exactly that epoch (the app's "could not restart"; e.g. drained by eph_craft_batch_reset_knots);
+ *   EPH_EVENTS_FULL       the event search has not yet examined the steps before the restart knot, or new_solution's entry finds
+ *                         the transition slab full: drain with eph_craft_batch_reset_events, eph_craft_batch_propagate to a t_end
+ *                         no later than the craft's time (no step, only the search) and restart again;
+ *   EPH_ERR_BAD_ARGUMENT  no common segment start lies before `before` (the reference unwraps).
+ * A craft that does not restart, and every unselected craft, is left bit for bit as it was; unselected craft's output entries
+ * are not written. The batch keeps its deal to the lanes; clones are independent; set_body_order and a pending retry_failed are
+ * unaffected. Refused with nothing changed: NULL batch, a bad CSR, burn_ref out of range, params with which
+ * (EPH_ERR_BAD_ARGUMENT); a relative-frame burn on a Tsitouras75Nystrom batch (EPH_ERR_UNSUPPORTED). An empty batch: EPH_OK. */
+int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which,
+                                const int64_t *burn_offset, const double *burn_start, const double *burn_end,
+                                const double *burn_acc_xyz, const int32_t *burn_ref,
+                                const double *plan_end, const eph_adaptive_params *params,
+                                double *restart_epoch, int32_t *outcome);
 /* Drain point for long propagations: after the caller has read the knots it wants, the newest knot of every craft
  * becomes knot 0 of an otherwise empty slab (so consecutive pieces of the CubicHermiteSpline share their end point,
  * what CubicHermiteSpline::extend, ephemeris/src/trajectory.rs:842-844, needs to stitch them, minus the duplicate), EPH_KNOTS_FULL is cleared and the next

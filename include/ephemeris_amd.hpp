@@ -18,6 +18,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -473,6 +474,36 @@ public:
                     out[e * n + c].position[d] = y[(e * 6 + d) * n + c];
                     out[e * n + c].velocity[d] = y[(e * 6 + 3 + d) * n + c];
                 }
+    }
+    // Flight-plan restart in place (FlightPlan::restart_propagator + apply_flight_plan, flight_plan.rs:263-361), on the device: every
+    // selected craft (which: one flag per craft, empty = all) continues from the knot where its new plan (one burn list per craft)
+    // diverges from the old one. plan_end: one FlightPlan.end per craft (empty = +inf); params: the batch's new parameters (only with
+    // `which` empty). Returns one outcome per craft (EPH_OK, EPH_EVAL_FAILED, EPH_EVENTS_FULL, EPH_ERR_BAD_ARGUMENT; INT32_MIN for an
+    // unselected craft) and, if asked, the restart epochs (NaN where none).
+    std::vector<int32_t> restart(const std::vector<std::vector<Burn>> &timelines, std::vector<double> *restart_epoch = nullptr,
+                                 const std::vector<double> &plan_end = {}, const AdaptiveParams *params = nullptr,
+                                 const std::vector<uint8_t> &which = {}) {
+        const size_t n = static_cast<size_t>(n_);
+        if (timelines.size() != n || (!plan_end.empty() && plan_end.size() != n) || (!which.empty() && which.size() != n))
+            throw std::invalid_argument("SpacecraftBatch::restart: one timeline (and plan end / flag) per craft");
+        std::vector<int64_t> off(n + 1, 0);
+        std::vector<double> bs, be, ba;
+        std::vector<int32_t> br;
+        for (size_t i = 0; i < n; ++i) {
+            for (const Burn &b : timelines[i]) {
+                bs.push_back(b.start); be.push_back(b.end); br.push_back(b.reference);
+                ba.insert(ba.end(), b.acceleration.begin(), b.acceleration.end());
+            }
+            off[i + 1] = static_cast<int64_t>(bs.size());
+        }
+        if (bs.empty()) { bs = {0.0}; be = {0.0}; ba = {0.0, 0.0, 0.0}; br = {0}; }
+        std::vector<double> epoch(n, std::numeric_limits<double>::quiet_NaN());
+        std::vector<int32_t> outcome(n, std::numeric_limits<int32_t>::min());
+        detail::check(eph_craft_batch_restart(h_, which.empty() ? nullptr : which.data(), off.data(), bs.data(), be.data(), ba.data(), br.data(),
+                                              plan_end.empty() ? nullptr : plan_end.data(), params, epoch.data(), outcome.data()),
+                      "eph_craft_batch_restart");
+        if (restart_epoch) *restart_epoch = epoch;
+        return outcome;
     }
     // problem.{time, state} and the controller's next step size of every craft
     void state(std::vector<double> &t, std::vector<DVec3> &position, std::vector<DVec3> &velocity, std::vector<double> *next_h = nullptr) const {
