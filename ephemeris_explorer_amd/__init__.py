@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "eph_ephemeris_is_valid_at", "eph_ephemeris_export", "eph_ephemeris_import", "eph_craft_batch_retry_failed",
     "eph_ephemeris_interpolation_errors", "eph_craft_batch_create", "eph_craft_batch_set_body_order", "eph_craft_batch_propagate", "eph_craft_batch_step_n",
     "eph_craft_batch_status", "eph_craft_batch_state", "eph_craft_batch_summary", "eph_craft_batch_knots", "eph_craft_batch_kernel_time",
-    "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_eval", "eph_craft_batch_restart", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
+    "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_eval", "eph_craft_batch_plot_points", "eph_craft_batch_restart", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
     "eph_craft_batch_destroy", "eph_hermite_eval", "eph_hermite_join", "eph_transitions_join", "eph_apsides_join", "eph_plot_points",
 ]
 
@@ -210,6 +210,8 @@ def _lib():
     L.eph_craft_batch_step_n.argtypes = [vp, C.c_uint32]
     L.eph_craft_batch_knot_slabs.argtypes = [vp, i32, i32, _dp, _dp]
     L.eph_craft_batch_eval.argtypes = [vp, i64, _dp, i32, i32, _dp, _u8p]
+    L.eph_craft_batch_plot_points.argtypes = [vp, C.POINTER(PlotView), i64, C.POINTER(PlotRequest), _i64p, i64, _dp,
+                                              C.POINTER(C.c_float), _i64p, _i32p, _dp]
     L.eph_craft_batch_restart.argtypes = [vp, _u8p, _i64p, _dp, _dp, _dp, _i32p, _dp, C.POINTER(AdaptiveParams), _dp, _i32p]
     L.eph_craft_batch_reset_knots.argtypes = [vp]
     L.eph_craft_batch_reset_events.argtypes = [vp]
@@ -884,6 +886,33 @@ class SpacecraftBatch:
             return y, inside
         return (np.ascontiguousarray(y[:, :3].transpose(0, 2, 1)), np.ascontiguousarray(y[:, 3:].transpose(0, 2, 1)), inside)
 
+    def plot_points(self, view, requests, craft=None):
+        """The adaptive plot sampler on the batch's own knots (eph_craft_batch_plot_points): plot p draws craft craft[p]
+        (None: plot p is craft p), read from the knot slabs on the device. view and requests as in plot_points(), the
+        requests without source_body / knots (the source is the craft); one dict may be given for all plots.
+        -> list of (status, failed_at, t[k], xyz[k, 3] float32), what plot_points() returns for the craft's knots."""
+        crafts = None if craft is None else np.ascontiguousarray(craft, dtype=np.int64).ravel()
+        if isinstance(requests, dict):
+            requests = [requests] * (self.n if crafts is None else len(crafts))
+        n = len(requests)
+        if crafts is not None and len(crafts) != n:
+            raise ValueError("SpacecraftBatch.plot_points: one craft per request")
+        v = _plot_view(view)
+        arr = (PlotRequest * max(n, 1))()
+        cap = 1
+        for i, r in enumerate(requests):
+            if "source_body" in r or "knots" in r:
+                raise ValueError("SpacecraftBatch.plot_points: the source is the craft (no source_body / knots)")
+            arr[i] = PlotRequest(-1, int(r.get("reference_body", -1)), 0, 0, float(r["start"]), float(r["end"]), int(r.get("bound", 0)),
+                                 int(r.get("enabled", 1)), float(r["tan2_angular_resolution"]), int(r["max_points"]))
+            cap = max(cap, int(r["max_points"]))
+        ot, ox = np.zeros((max(n, 1), cap)), np.zeros((max(n, 1), cap, 3), dtype=np.float32)
+        cnt, st, fail = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1))
+        _check(self._L.eph_craft_batch_plot_points(self._h, C.byref(v), n, arr, None if crafts is None else _p(crafts, _i64p), cap,
+                                                   _p(ot), ox.ctypes.data_as(C.POINTER(C.c_float)), _p(cnt, _i64p), _p(st, _i32p),
+                                                   _p(fail)), "eph_craft_batch_plot_points")
+        return [(int(st[i]), float(fail[i]), ot[i, :cnt[i]].copy(), ox[i, :cnt[i]].copy()) for i in range(n)]
+
     UNSELECTED = np.iinfo(np.int32).min     # restart(): the outcome entry of a craft `which` did not select (never written)
 
     def restart(self, burns, plan_end=None, params=None, which=None):
@@ -992,6 +1021,18 @@ def hermite_eval(t, pos, vel, at, with_velocity=True):
     _check(_lib().eph_hermite_eval(len(t), _p(t), _p(pos), _p(vel), m, _p(at), _p(op), _p(ov) if with_velocity else None,
                                    _p(inside, _u8p)), "eph_hermite_eval")
     return op, (ov if with_velocity else None), inside.astype(bool)
+
+
+def _plot_view(view):
+    """dict(camera_position, grid_matrix3 (3x3, columns = axes), grid_translation, cell_offset, current) -> PlotView"""
+    v = PlotView()
+    v.camera_position[:] = [float(x) for x in view["camera_position"]]
+    m = np.asarray(view.get("grid_matrix3", np.eye(3)), dtype=np.float64)
+    v.grid_matrix3[:] = [float(m[r, c]) for c in range(3) for r in range(3)]          # column major
+    v.grid_translation[:] = [float(x) for x in view.get("grid_translation", (0.0, 0.0, 0.0))]
+    v.cell_offset[:] = [float(x) for x in view.get("cell_offset", (0.0, 0.0, 0.0))]
+    v.current = float(view["current"])
+    return v
 
 
 def plot_points(ephemeris, view, requests, knots=None):

@@ -523,6 +523,27 @@ int32_t eph_plot_points(const eph_ephemeris *e, const eph_plot_view *view, int64
                         int64_t n_knots, const double *knot_t, const double *knot_pos_xyz, const double *knot_vel_xyz,
                         int64_t capacity, double *out_t, float *out_xyz, int64_t *out_count, int32_t *out_status,
                         double *out_failed_at);
+/* The same sampler for ships that live in an eph_craft_batch: plot p draws craft craft[p] of the batch (craft == NULL: plot
+ * p is craft p, so n_plots <= n_craft; a craft may appear in several plots), its source being the craft's
+ * CubicHermiteSpline as the batch holds it now, knots 0 .. nknots - 1, read from the knot slabs on the device: no knot
+ * crosses the bus. requests[p] as above with source_body == -1 and knot_first == knot_count == 0; reference_body is -1
+ * or a body of the bound ephemeris in table order (eph_craft_batch_set_body_order does not affect it), taken from the
+ * LIVE table as it is when the call starts. view, capacity and the five outputs are eph_plot_points's.
+ * For every plot, out_count, out_status, out_failed_at and the first out_count[p] epochs and points are bit for bit
+ * what eph_plot_points returns for the same view and request with knot_first = 0, knot_count = nknots on the arrays
+ * eph_craft_batch_knots(craft[p]) gives; a craft with fewer than two knots draws nothing (count 0, EPH_OK), so after
+ * eph_craft_batch_reset_knots only the drained slab's span is drawn. Entries of out_t / out_xyz at or beyond
+ * out_count[p] are NOT written: only the used part of a row travels to the caller.
+ * Does not change the batch (state, knots, events, a pending retry, the FSAL stages, the deal to the lanes); works on
+ * clones. n_plots == 0 or an empty batch: EPH_OK, nothing written. EPH_ERR_BAD_ARGUMENT (nothing written, no device
+ * work): NULL batch or view; n_plots < 0; capacity < 0; NULL requests, out_count, out_status or out_failed_at with plots
+ * to do; NULL out_t / out_xyz with capacity > 0; craft[p] outside 0 .. n_craft - 1; craft == NULL with n_plots > n_craft;
+ * source_body != -1; a non-zero knot_first / knot_count; reference_body < -1 or >= n_bodies; max_points < 0 or
+ * > capacity; bound outside 0..2. The result is produced in passes over plots of at most 256 MB each. */
+int32_t eph_craft_batch_plot_points(eph_craft_batch *b, const eph_plot_view *view, int64_t n_plots,
+                                    const eph_plot_request *requests, const int64_t *craft, int64_t capacity,
+                                    double *out_t, float *out_xyz, int64_t *out_count, int32_t *out_status,
+                                    double *out_failed_at);
 
 /* SpacecraftPropagator::join(lhs, rhs) (ephemeris/src/propagators/spacecraft.rs:558-561; the app's
  * PredictionTarget::merge, ephemeris_explorer/src/dynamics/spacecraft.rs:830-841): lhs.clear_after(rhs.start())

@@ -475,6 +475,42 @@ public:
                     out[e * n + c].velocity[d] = y[(e * 6 + 3 + d) * n + c];
                 }
     }
+    // compute_plot_points_parallel + PlotPoints::new (ephemeris_explorer/src/ui/world/plot.rs:93-149,272-374) for ships that live in the
+    // batch, on the device, from the knots the batch holds: plot p draws craft craft[p] (craft empty: plot p is craft p) as `requests[p]`
+    // asks (source_body -1, knot_first = knot_count = 0; reference_body in table order or -1). One PlotPoints per plot: the epochs and
+    // f32 points (x, y, z per point) the reference pushes, the status (EPH_OK, EPH_EVAL_FAILED, EPH_MAX_ITERATIONS_REACHED) and the
+    // epoch a failure happened at.
+    struct PlotPoints {
+        int32_t status = EPH_OK;
+        double failed_at = 0.0;
+        std::vector<double> t;
+        std::vector<float> xyz;
+    };
+    std::vector<PlotPoints> plot_points(const eph_plot_view &view, const std::vector<eph_plot_request> &requests,
+                                        const std::vector<int64_t> &craft = {}) const {
+        const size_t np = requests.size();
+        if (!craft.empty() && craft.size() != np) throw std::invalid_argument("SpacecraftBatch::plot_points: one craft per request");
+        if (craft.empty() && np > static_cast<size_t>(n_)) throw std::invalid_argument("SpacecraftBatch::plot_points: more requests than craft");
+        int64_t capacity = 1;
+        for (const eph_plot_request &r : requests) capacity = r.max_points > capacity ? r.max_points : capacity;
+        const size_t cap = static_cast<size_t>(capacity);
+        std::vector<double> t(np * cap), failed(np);
+        std::vector<float> xyz(np * cap * 3);
+        std::vector<int64_t> count(np);
+        std::vector<int32_t> status(np);
+        detail::check(eph_craft_batch_plot_points(h_, &view, static_cast<int64_t>(np), requests.data(), craft.empty() ? nullptr : craft.data(), capacity,
+                                                  t.data(), xyz.data(), count.data(), status.data(), failed.data()),
+                      "eph_craft_batch_plot_points");
+        std::vector<PlotPoints> out(np);
+        for (size_t p = 0; p < np; ++p) {
+            const size_t k = static_cast<size_t>(count[p]);
+            out[p].status = status[p];
+            out[p].failed_at = failed[p];
+            out[p].t.assign(t.begin() + static_cast<std::ptrdiff_t>(p * cap), t.begin() + static_cast<std::ptrdiff_t>(p * cap + k));
+            out[p].xyz.assign(xyz.begin() + static_cast<std::ptrdiff_t>(p * cap * 3), xyz.begin() + static_cast<std::ptrdiff_t>((p * cap + k) * 3));
+        }
+        return out;
+    }
     // Flight-plan restart in place (FlightPlan::restart_propagator + apply_flight_plan, flight_plan.rs:263-361), on the device: every
     // selected craft (which: one flag per craft, empty = all) continues from the knot where its new plan (one burn list per craft)
     // diverges from the old one. plan_end: one FlightPlan.end per craft (empty = +inf); params: the batch's new parameters (only with
