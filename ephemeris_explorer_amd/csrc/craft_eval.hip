@@ -2,10 +2,8 @@
 // sweep leaves on the device (eph_craft_batch_eval). Reads the batch; changes nothing in it.
 //
 // Mirrors (paths relative to the reference repository root):
-//   CubicHermiteSpline::state_vector, CubicHermite::{new, eval, eval_derivative}   ephemeris/src/trajectory.rs:645-696,766-797
 //   RelativeTrajectory::state_vector (reference first, `?`, one subtraction per component)   ephemeris/src/trajectory.rs:326-334
-//   UniformSpline::state_vector (velocity = derivative / interval)                 ephemeris/src/trajectory.rs:449-470,551-617
-// The spline part is k_hermite_eval's operation sequence (evaluators.hip), the body part k_spline_eval's (solout.hip).
+// over CubicHermiteSpline::state_vector and UniformSpline::state_vector, which are trajectory_eval.h's.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -14,32 +12,9 @@
 #include <shared_mutex>
 
 #include "craft_batch.h"
+#include "trajectory_eval.h"
 
 namespace eph {
-
-// UniformSpline::state_vector of one body of the live table: out[0..2] position, out[3..5] velocity; false = None
-__device__ __forceinline__ bool eval_body_sv(const BodyEntry *__restrict__ bodies, const double *__restrict__ coeffs,
-                                             const int *__restrict__ ncoef, int body, double t, double (&out)[6]) {
-    const BodyEntry be = bodies[body];
-    long long idx;
-    double tau;
-    if (!spline_locate(be, t, idx, tau)) return false;
-    const double *co = coeffs + (be.coeff_off + idx) * kDiv * 3;
-    const int nc = ncoef[be.coeff_off + idx];
-    for (int c = 0; c < 3; ++c) {                     // Polynomial::eval_and_deriv
-        const double first = nc ? co[c] : 0.0;
-        const double last = nc ? co[(nc - 1) * 3 + c] : 0.0;
-        double e = last, d = last;
-        for (int k = nc - 2; k >= 1; --k) {
-            e = e * tau + co[k * 3 + c];
-            d = d * tau + e;
-        }
-        e = e * tau + first;
-        out[c] = e;
-        out[3 + c] = d / be.interval;
-    }
-    return true;
-}
 
 // Shared epochs: the reference body's state is the same for every craft, so it is evaluated once per epoch, not once per lane.
 __global__ void __launch_bounds__(64) k_craft_eval_reference(long long m, const double *__restrict__ at, int body,
@@ -48,8 +23,9 @@ __global__ void __launch_bounds__(64) k_craft_eval_reference(long long m, const 
                                                              double *__restrict__ ref /*[m][6]*/, uint8_t *__restrict__ ref_ok) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= m) return;
-    double r[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const bool ok = eval_body_sv(bodies, coeffs, ncoef, body, at[e], r);
+    V3 p = {0.0, 0.0, 0.0}, v = {0.0, 0.0, 0.0};
+    const bool ok = body_state_vector(BodyTable{bodies, coeffs, ncoef}, body, at[e], p, v);
+    const double r[6] = {p.x, p.y, p.z, v.x, v.y, v.z};
 #pragma unroll
     for (int d = 0; d < 6; ++d) ref[e * 6 + d] = ok ? r[d] : 0.0;
     ref_ok[e] = ok ? 1 : 0;
@@ -68,75 +44,40 @@ struct CraftEvalArgs {
     int body;                    // reference body (table order) or -1
     const double *ref;           // shared epochs with a reference body: [m][6] and [m] from k_craft_eval_reference
     const uint8_t *ref_ok;
-    const BodyEntry *bodies;
-    const double *coeffs;
-    const int *ncoef;
+    BodyTable table;
     double *out_y;               // [m][6][column]
     uint8_t *inside;             // [m][column]
 };
 
 // One lane per slab COLUMN: the lanes of a wave read neighbouring words of a knot row wherever their knot indices agree; the
-// craft-order translation happens once, at the copy to the caller (k_craft_eval_rows_out). One search path, the reference's binary
-// search per (craft, epoch): a per-lane cursor galloping forward over ascending shared epochs was measured and dropped -- it takes
-// 10 % off a kernel that is under 1 % of the call (profiles/craft_eval.md, scripts/experiments/craft_eval_gallop.patch).
+// craft-order translation happens once, at the copy to the caller (k_craft_eval_rows_out). One search per (craft, epoch); what was
+// tried instead is told at hermite_state_vector (trajectory_eval.h).
 __global__ void __launch_bounds__(256) k_craft_eval(const CraftEvalArgs a) {
     const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (col >= a.n) return;
     const long long n = a.n;
     const long long craft = a.perm ? a.perm[col] : col;
-    const long long nk = min(max(a.nknots[craft], 0), a.max_knots);
-    const double *__restrict__ kt = a.knot_t + col;
-    const double *__restrict__ ky = a.knot_y + col;
+    const KnotColumn knots = {min(max(a.nknots[craft], 0), a.max_knots), n, a.knot_t + col, a.knot_y + col};
     for (long long e = 0; e < a.m; ++e) {
         const double x = a.per_craft ? a.at[e * n + craft] : a.at[e];
-        double r[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        V3 rp = {0.0, 0.0, 0.0}, rv = {0.0, 0.0, 0.0};
         bool ok = true;
         if (a.body >= 0) {                            // reference.state_vector(at)?   trajectory.rs:330
             if (a.per_craft) {
-                ok = eval_body_sv(a.bodies, a.coeffs, a.ncoef, a.body, x, r);
+                ok = body_state_vector(a.table, a.body, x, rp, rv);
             } else {
                 ok = a.ref_ok[e] != 0;
-#pragma unroll
-                for (int d = 0; d < 6; ++d) r[d] = a.ref[e * 6 + d];
+                rp = {a.ref[e * 6 + 0], a.ref[e * 6 + 1], a.ref[e * 6 + 2]};
+                rv = {a.ref[e * 6 + 3], a.ref[e * 6 + 4], a.ref[e * 6 + 5]};
             }
         }
-        double o[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (ok) {
-            long long lo = 0, hi = nk, hit = -1;
-            while (lo < hi) {                                      // binary_search_by(|(t, _)| t.cmp(&at))
-                const long long mid = lo + (hi - lo) / 2;
-                const double tm = kt[mid * n];
-                if (tm == x) { hit = mid; break; }
-                if (tm < x) lo = mid + 1; else hi = mid;
-            }
-            if (hit >= 0) {
-#pragma unroll
-                for (int d = 0; d < 6; ++d) o[d] = ky[(hit * 6 + d) * n];
-            } else if (lo == 0 || lo >= nk) {                      // i.checked_sub(1)? / self.0.get(i + 1)?
-                ok = false;
-            } else {
-                const long long i = lo - 1;
-                const double b0 = kt[i * n], dt = kt[(i + 1) * n] - b0;
-                const double dt_recip = 1.0 / dt;
-                const double dt_recip_2 = dt_recip * dt_recip;
-                const double dt_recip_3 = dt_recip * dt_recip_2;
-                const double s = x - b0;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double v0 = ky[(i * 6 + c) * n], v1 = ky[((i + 1) * 6 + c) * n];
-                    const double d0 = ky[(i * 6 + 3 + c) * n], d1 = ky[((i + 1) * 6 + 3 + c) * n];
-                    const double dt_val = v1 - v0;
-                    const double a2 = dt_val * dt_recip_2 * 3.0 - (d0 * 2.0 + d1) * dt_recip;
-                    const double a3 = dt_val * dt_recip_3 * -2.0 + (d0 + d1) * dt_recip_2;
-                    o[c] = (((a3 * s + a2) * s) + d0) * s + v0;
-                    o[3 + c] = ((a3 * s * 3.0 + a2 * 2.0) * s) + d0;
-                }
-            }
-            if (ok && a.body >= 0) {                               // position - ref_position, velocity - ref_velocity
-#pragma unroll
-                for (int d = 0; d < 6; ++d) o[d] = o[d] - r[d];
-            }
+        V3 p = {0.0, 0.0, 0.0}, v = {0.0, 0.0, 0.0};
+        ok = ok && hermite_state_vector(knots, x, p, v);
+        if (ok && a.body >= 0) {                      // position - ref_position, velocity - ref_velocity
+            p = sub(p, rp);
+            v = sub(v, rv);
         }
+        const double o[6] = {p.x, p.y, p.z, v.x, v.y, v.z};
 #pragma unroll
         for (int d = 0; d < 6; ++d) a.out_y[(e * 6 + d) * n + col] = ok ? o[d] : 0.0;
         a.inside[e * n + col] = ok ? 1 : 0;
@@ -207,7 +148,7 @@ int32_t eph_craft_batch_eval(eph_craft_batch *b, int64_t m, const double *at, in
         a.n = b->n; a.max_knots = b->max_knots; a.nknots = b->nknots.p; a.perm = dealt ? b->perm.p : nullptr;
         a.knot_t = b->knot_t.p; a.knot_y = b->knot_y.p;
         a.per_craft = per_craft; a.body = reference_body;
-        a.bodies = b->eph->bodies.p; a.coeffs = b->eph->coeffs.p; a.ncoef = b->eph->ncoef.p;
+        a.table = {b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p};
         a.out_y = d_y.p; a.inside = d_in.p;
         double *stage_y = static_cast<double *>(stage.dev());
         uint8_t *stage_in = reinterpret_cast<uint8_t *>(stage_y + y_count);

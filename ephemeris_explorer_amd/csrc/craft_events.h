@@ -1,17 +1,16 @@
 // craft_events.h -- what the event search (craft_events.hip) shares with the flight-plan restart (craft_restart.hip): the search's
-// argument block, a body's position from the live table, find_soi and SoiTransitions::insert on a craft's column of the slabs.
+// argument block, find_soi and SoiTransitions::insert on a craft's column of the slabs.
 // Mirrors ephemeris_explorer/src/dynamics/spacecraft.rs:172-185,208-221,332-339 (paths relative to the reference repository root).
 #pragma once
 #include "craft_batch.h"
+#include "trajectory_eval.h"
 
 namespace eph {
 
 struct EventArgs {
     long long n_craft;
     int n_bodies;
-    const BodyEntry *bodies;
-    const double *coeffs;
-    const int *ncoef;
+    BodyTable table;              // the live table (trajectory_eval.h)
     const double *soi;            // [n_bodies] sphere radii (inf for the root)
     const int *nknots;
     const double *knot_t, *knot_y;
@@ -22,22 +21,6 @@ struct EventArgs {
     int max_tr, max_ap;
     const int *slot_of;           // craft -> its column in the knot slabs (null: identity)
 };
-__device__ __forceinline__ bool ev_body_pos(const EventArgs &a, int b, double t, V3 &out) {
-    const BodyEntry be = a.bodies[b];
-    long long idx;
-    double tau;
-    if (!spline_locate(be, t, idx, tau)) return false;
-    const double *co = a.coeffs + (be.coeff_off + idx) * kDiv * 3;
-    const int nc = a.ncoef[be.coeff_off + idx];
-    V3 bp = {0.0, 0.0, 0.0};
-    for (int k = nc - 1; k >= 0; --k) {
-        bp.x = bp.x * tau + co[k * 3 + 0];
-        bp.y = bp.y * tau + co[k * 3 + 1];
-        bp.z = bp.z * tau + co[k * 3 + 2];
-    }
-    out = bp;
-    return true;
-}
 // find_soi :172-185,208-221: inside iff d2 < r*r; the closest wins, the first on ties
 __device__ inline int soi_at_except(const EventArgs &a, double t, V3 position, int except) {
     int best = -1;
@@ -45,7 +28,7 @@ __device__ inline int soi_at_except(const EventArgs &a, double t, V3 position, i
     for (int b = 0; b < a.n_bodies; ++b) {
         if (b == except) continue;
         V3 bp;
-        if (!ev_body_pos(a, b, t, bp)) continue;
+        if (!body_position(a.table, b, t, bp)) continue;
         const V3 d = sub(position, bp);
         const double d2 = dot(d, d), r = a.soi[b];
         if (!(d2 < r * r)) continue;

@@ -4,7 +4,7 @@
 //   SpacecraftSolout, SoiTransitions, find_zero_crossing, find_root_bisection, find_soi
 //                                                       ephemeris_explorer/src/dynamics/spacecraft.rs:77-221,296-451,525-586
 //   CubicHermite::{new, eval, eval_derivative}          ephemeris/src/trajectory.rs:645-697
-//   UniformSpline::{position, state_vector}             ephemeris/src/trajectory.rs:459-470,551-617
+// A body's position and state vector (UniformSpline::{position, state_vector}) are trajectory_eval.h's.
 // glam::DVec3 operations (crate glam 0.30.10, not on disk) are restated from the published crate.
 #include <algorithm>
 
@@ -29,43 +29,19 @@ __device__ __forceinline__ V3 hermite_vel(const Hermite &h, double t) {      // 
     const double dt = t - h.b0;
     return add(scale(add(scale(scale(h.a3, dt), 3.0), scale(h.a2, 2.0)), dt), h.a1);
 }
-__device__ __forceinline__ bool ev_body_sv(const EventArgs &a, int b, double t, V3 &pos, V3 &vel) {
-    const BodyEntry be = a.bodies[b];
-    long long idx;
-    double tau;
-    if (!spline_locate(be, t, idx, tau)) return false;
-    const double *co = a.coeffs + (be.coeff_off + idx) * kDiv * 3;
-    const int nc = a.ncoef[be.coeff_off + idx];
-    double rp[3], rv[3];
-    for (int c = 0; c < 3; ++c) {                     // Polynomial::eval_and_deriv
-        const double first = nc ? co[c] : 0.0;
-        const double last = nc ? co[(nc - 1) * 3 + c] : 0.0;
-        double e = last, d = last;
-        for (int k = nc - 2; k >= 1; --k) {
-            e = e * tau + co[k * 3 + c];
-            d = d * tau + e;
-        }
-        e = e * tau + first;
-        rp[c] = e;
-        rv[c] = d / be.interval;
-    }
-    pos = {rp[0], rp[1], rp[2]};
-    vel = {rv[0], rv[1], rv[2]};
-    return true;
-}
 // soi_distance_squared_at :77-83 (RADIAL = false) / radial_velocity_at :85-89 (RADIAL = true)
 template <bool RADIAL>
 __device__ __forceinline__ bool event_f(const EventArgs &a, const Hermite &h, int body, double t, double &out) {
     if (!RADIAL) {
         V3 bp;
-        if (!ev_body_pos(a, body, t, bp)) return false;
+        if (!body_position(a.table, body, t, bp)) return false;
         const V3 d = sub(hermite_pos(h, t), bp);
         const double r = a.soi[body];
         out = dot(d, d) - r * r;
         return true;
     }
     V3 bp, bv;
-    if (!ev_body_sv(a, body, t, bp, bv)) return false;
+    if (!body_state_vector(a.table, body, t, bp, bv)) return false;
     const V3 rp = sub(hermite_pos(h, t), bp), rv = sub(hermite_vel(h, t), bv);
     out = dot(rp, rv);
     return true;
@@ -208,7 +184,7 @@ __global__ void __launch_bounds__(64) k_craft_events(const EventArgs a) {
             bool asc;
             if (!find_zero_crossing<true>(a, h, soi, ta, tb, time, asc)) continue;
             V3 bp;
-            if (!ev_body_pos(a, soi, time, bp)) continue;
+            if (!body_position(a.table, soi, time, bp)) continue;
             const V3 d = sub(bp, hermite_pos(h, time));          // distance_at  dynamics/mod.rs:141-146
             full = !ap_insert(a, i, nap, time, sqrt(dot(d, d)), soi, asc ? 0 : 1);
         }
@@ -240,7 +216,7 @@ __global__ void __launch_bounds__(256) k_craft_reset_events(long long n, int *nt
 int craft_events_search(eph_craft_batch *b, hipStream_t s) {
     EventArgs e{};
     e.n_craft = b->n; e.n_bodies = b->eph->n_bodies;
-    e.bodies = b->eph->bodies.p; e.coeffs = b->eph->coeffs.p; e.ncoef = b->eph->ncoef.p;
+    e.table = {b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p};
     e.soi = b->soi.p; e.nknots = b->nknots.p; e.knot_t = b->knot_t.p; e.knot_y = b->knot_y.p;
     e.ev_seg = b->ev_seg.p; e.ntr = b->ntr.p; e.nap = b->nap.p; e.ev_status = b->ev_status.p;
     e.tr_time = b->tr_time.p; e.tr_body = b->tr_body.p;

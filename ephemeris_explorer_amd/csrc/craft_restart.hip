@@ -242,7 +242,7 @@ int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which, const 
         a.events = b->events ? 1 : 0;
         EventArgs &e = a.ev;
         e.n_craft = n; e.n_bodies = b->eph->n_bodies;
-        e.bodies = b->eph->bodies.p; e.coeffs = b->eph->coeffs.p; e.ncoef = b->eph->ncoef.p;
+        e.table = {b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p};
         if (b->events) {
             e.soi = b->soi.p; e.ev_seg = b->ev_seg.p; e.ntr = b->ntr.p; e.nap = b->nap.p; e.ev_status = b->ev_status.p;
             e.tr_time = b->tr_time.p; e.tr_body = b->tr_body.p; e.ap_time = b->ap_time.p;

@@ -14,6 +14,7 @@
 
 #include "pair_ns.h"
 #include "craft_device.h"
+#include "trajectory_eval.h"
 
 namespace eph {
 namespace EPH_PV_NS {
@@ -362,26 +363,9 @@ __device__ __forceinline__ bool burn_acceleration(const BodyEntry *bodies_by_ind
                                                   double ay, double az, double t, const V3 &pos, const V3 &vel, V3 &man) {
     const V3 thrust = {ax, ay, az};
     if (ref >= 0) {                                   // ReferenceFrame::Relative -> TNB::try_new(sv - ref.state_vector(t))
-        const BodyEntry be = bodies_by_index[ref];
-        long long idx;
-        double tau;
-        if (!spline_locate(be, t, idx, tau)) return false;
-        const double *co = coeffs + (be.coeff_off + idx) * kDiv * 3;
-        const int nc = ncoef[be.coeff_off + idx];
-        double rp[3], rv[3];
-        for (int c = 0; c < 3; ++c) {                 // Polynomial::eval_and_deriv
-            const double first = nc ? co[c] : 0.0;
-            const double last = nc ? co[(nc - 1) * 3 + c] : 0.0;
-            double e = last, d = last;
-            for (int k = nc - 2; k >= 1; --k) {
-                e = e * tau + co[k * 3 + c];
-                d = d * tau + e;
-            }
-            e = e * tau + first;
-            rp[c] = e;
-            rv[c] = d / be.interval;
-        }
-        const V3 rel_p = sub(pos, V3{rp[0], rp[1], rp[2]}), rel_v = sub(vel, V3{rv[0], rv[1], rv[2]});
+        V3 rp, rv;                                    // ref.state_vector(t): trajectory_eval.h
+        if (!body_state_vector(BodyTable{bodies_by_index, coeffs, ncoef}, ref, t, rp, rv)) return false;
+        const V3 rel_p = sub(pos, rp), rel_v = sub(vel, rv);
         V3 x, yv;
         if (!try_normalize(rel_v, x)) return false;
         if (!try_normalize(cross(rel_p, rel_v), yv)) return false;

@@ -3,6 +3,7 @@
 // Reference citations are relative to the reference repository root.
 #include "eph_internal.h"
 #include "force_common.h"
+#include "trajectory_eval.h"
 
 namespace eph {
 
@@ -189,10 +190,8 @@ __global__ void __launch_bounds__(64) k_lsq_fit(long long nwin, const uint64_t *
     ncoef[w] = nco;
 }
 
-// ------------------------------------------------------------------------------------------------------
-// UniformSpline::state_vector  ephemeris/src/trajectory.rs:459-470 (get_polynomial :551-561,
-// get_index_local_exclusive :600-607, index_local_exclusive :614-617, eval_and_deriv :368-385)
-// ------------------------------------------------------------------------------------------------------
+// UniformSpline::state_vector (vel != null) or ::position of one spline given by value, at many epochs (trajectory_eval.h);
+// outside the spline: zeros and inside = 0
 __global__ void __launch_bounds__(256) k_spline_eval(long long m, const double *__restrict__ at, double start,
                                                      double interval, long long npoly,
                                                      const double *__restrict__ coeffs,
@@ -200,42 +199,13 @@ __global__ void __launch_bounds__(256) k_spline_eval(long long m, const double *
                                                      double *__restrict__ vel, uint8_t *__restrict__ inside) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= m) return;
-    const double local = at[q] - start;
-    const double span = interval * (double)npoly;            // Duration::scaled
-    bool ok = !(__builtin_signbit(local) || local > span);   // is_negative() is the sign bit
-    unsigned long long idx = 0;
-    if (ok) {
-        const double c = ceil(local / interval);
-        const unsigned long long ci = c <= 0.0 ? 0ull : (c >= 18446744073709551616.0 ? ~0ull : (unsigned long long)c);
-        idx = ci == 0 ? 0 : ci - 1;                          // saturating_sub(1)
-        ok = idx < (unsigned long long)npoly;
-    }
+    BodyEntry be{};                                           // coeffs / ncoef start at this spline's polynomial 0
+    be.start = start; be.interval = interval; be.npoly = npoly;
+    V3 p = {0.0, 0.0, 0.0}, v = {0.0, 0.0, 0.0};
+    const bool ok = vel ? spline_state_vector(be, coeffs, ncoef, at[q], p, v) : spline_position(be, coeffs, ncoef, at[q], p);
     inside[q] = ok ? 1 : 0;
-    if (!ok) {
-        for (int c = 0; c < 3; ++c) { pos[q * 3 + c] = 0.0; if (vel) vel[q * 3 + c] = 0.0; }
-        return;
-    }
-    const double tau = (local - interval * (double)idx) / interval;
-    const double *co = coeffs + idx * kDiv * 3;
-    const int nc = ncoef[idx];
-    for (int c = 0; c < 3; ++c) {
-        if (vel) {
-            const double first = nc ? co[c] : 0.0;
-            const double last = nc ? co[(nc - 1) * 3 + c] : 0.0;
-            double e = last, d = last;
-            for (int k = nc - 2; k >= 1; --k) {
-                e = e * tau + co[k * 3 + c];
-                d = d * tau + e;
-            }
-            e = e * tau + first;
-            pos[q * 3 + c] = e;
-            vel[q * 3 + c] = d / interval;
-        } else {
-            double r = 0.0;                                   // eval_slice_horner :398-410
-            for (int k = nc - 1; k >= 0; --k) r = r * tau + co[k * 3 + c];
-            pos[q * 3 + c] = r;
-        }
-    }
+    pos[q * 3] = p.x; pos[q * 3 + 1] = p.y; pos[q * 3 + 2] = p.z;
+    if (vel) { vel[q * 3] = v.x; vel[q * 3 + 1] = v.y; vel[q * 3 + 2] = v.z; }
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------

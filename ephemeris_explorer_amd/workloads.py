@@ -130,7 +130,7 @@ def wave_divergence(attempts, wave=64):
 # the sha256 of the sources of the kernel it describes; bench.py recomputes them and DROPS the figures when a source has changed since.
 PROFILE_SOURCES = {
     "nbody": ["step_wg.hip", "step_wave.hip", "pair_term.h", "ieee_seq.h", "force_common.h", "chain_tile.inc"],
-    "craft": ["craft_sweep.hip", "craft_device.h", "craft_attempt.inc", "pair_term.h", "ieee_seq.h"],
+    "craft": ["craft_sweep.hip", "craft_device.h", "trajectory_eval.h", "craft_attempt.inc", "pair_term.h", "ieee_seq.h"],
     "fast": ["fast.hip", "pair_term.h", "ieee_seq.h", "force_common.h"],
 }
 

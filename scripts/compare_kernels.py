@@ -2,13 +2,23 @@
 """Is the device code of two builds the same code? For every kernel (`.amdhsa_kernel` symbol) of two gfx950 assembly files, or of
 every compiled-once .hip unit of two source trees, compares the kernel descriptor block and the instruction text between the
 symbol's label and its `.Lfunc_end`, with `;` comments dropped and the function index in `.LBB<n>_` labels normalised (it changes
-when a kernel changes file; nothing else should). For a refactor that moves kernels between units.
+when a kernel changes file; nothing else should). For a refactor that moves kernels between units or code between functions.
 
-    compare_kernels.py A.s B.s
-    compare_kernels.py TREE_A TREE_B        # compiles SOURCES + HOOKS_SOURCES (*.hip) of each tree's build.py with its FLAGS
+    compare_kernels.py [-v] A.s B.s
+    compare_kernels.py [-v] TREE_A TREE_B   # compiles SOURCES + HOOKS_SOURCES (*.hip) of each tree's build.py with its FLAGS
 
-Exit status 0: the same kernel names on both sides, every one identical. No GPU needed."""
+Three verdicts per kernel:
+    same       descriptor block and instruction text identical
+    reordered  descriptor block (VGPRs, SGPRs, scratch, LDS) identical, and every floating-point arithmetic opcode (v_*_f64, v_*_f32
+               other than compares and v_cndmask) and every global_load_* / global_store_* occurs equally often, the _e32 / _e64
+               encoding suffix dropped; integer and address arithmetic, compares, moves, mask operations, waits, branches and labels
+               may differ: the same arithmetic on the same memory traffic in the same registers, scheduled or addressed differently
+    DIFF       anything else
+-v prints, for every kernel that is not `same`, the descriptor lines and the opcode counts that differ.
+
+Exit status 0: the same kernel names on both sides, every one `same` or `reordered`. No GPU needed."""
 import re
+from collections import Counter
 import runpy
 import subprocess
 import sys
@@ -47,6 +57,38 @@ def kernels(path):
     return out
 
 
+def opcodes(text):
+    """opcode -> count over a kernel's normalised instruction text, the encoding suffix dropped"""
+    return Counter(re.sub(r"_e(32|64)$", "", ln.split()[0]) for ln in text if not ln.endswith(":") and not ln.startswith("."))
+
+
+def pinned(op):
+    """the opcodes whose counts `reordered` holds equal: floating-point arithmetic and global memory traffic"""
+    if op.startswith(("global_load_", "global_store_")):
+        return True
+    return op.startswith("v_") and bool(re.search(r"_f(32|64)(_|$)", op)) and not op.startswith(("v_cmp", "v_cndmask"))
+
+
+def verdict(a, b):
+    """a, b: (descriptor, text) of one kernel in the two builds"""
+    if a == b:
+        return "same"
+    ca, cb = opcodes(a[1]), opcodes(b[1])
+    if a[0] == b[0] and all(ca[op] == cb[op] for op in set(ca) | set(cb) if pinned(op)):
+        return "reordered"
+    return "DIFF"
+
+
+def explain(a, b):
+    for x, y in zip(a[0], b[0]):
+        if x != y:
+            print(f"        {x}  ->  {y}")
+    ca, cb = opcodes(a[1]), opcodes(b[1])
+    for op in sorted(set(ca) | set(cb)):
+        if ca[op] != cb[op]:
+            print(f"        {'*' if pinned(op) else ' '} {op:<28} {ca[op]:>5} -> {cb[op]:<5}")
+
+
 def tree_kernels(tree, tmp):
     """{kernel symbol: (unit, descriptor, text)} of the compiled-once .hip units of a source tree"""
     b = runpy.run_path(str(Path(tree) / "ephemeris_explorer_amd" / "build.py"), run_name="build")
@@ -70,28 +112,32 @@ def demangle(names):
     return {n: re.sub(r"\(.*", "", d).replace("void ", "") for n, d in zip(names, out)}
 
 
-def main(a, b):
+def main(a, b, verbose=False):
     if Path(a).is_dir():
         with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
             ka, kb = tree_kernels(a, ta), tree_kernels(b, tb)
     else:
         ka, kb = ({k: (Path(p).name, *v) for k, v in kernels(p).items()} for p in (a, b))
     short = demangle(sorted(set(ka) | set(kb)))
-    bad = moved = 0
+    bad = moved = reordered = 0
     for k in sorted(set(ka) | set(kb), key=lambda k: short[k]):
         if k not in ka or k not in kb:
             print(f"ONLY IN {'A' if k in ka else 'B'}  {short[k]}  ({(ka.get(k) or kb.get(k))[0]})")
             bad += 1
             continue
-        same = ka[k][1:] == kb[k][1:]
-        bad += not same
+        v = verdict(ka[k][1:], kb[k][1:])
+        bad += v == "DIFF"
+        reordered += v == "reordered"
         moved += ka[k][0] != kb[k][0]
-        print(f"{'same' if same else 'DIFF'}  {short[k]:<44} {len(ka[k][2]):>6} lines  {ka[k][0]} -> {kb[k][0]}")
-    print(f"{len(set(ka) | set(kb))} kernels, {moved} in another unit, {bad} different or missing")
+        print(f"{v:<9}  {short[k]:<44} {len(ka[k][2]):>6} -> {len(kb[k][2]):<6} lines  {ka[k][0]} -> {kb[k][0]}")
+        if verbose and v != "same":
+            explain(ka[k][1:], kb[k][1:])
+    print(f"{len(set(ka) | set(kb))} kernels, {moved} in another unit, {reordered} reordered, {bad} different or missing")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = [x for x in sys.argv[1:] if x != "-v"]
+    if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[0], args[1], verbose="-v" in sys.argv[1:]))
