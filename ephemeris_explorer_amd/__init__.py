@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "eph_craft_batch_status", "eph_craft_batch_state", "eph_craft_batch_summary", "eph_craft_batch_knots", "eph_craft_batch_kernel_time",
     "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_eval", "eph_craft_batch_plot_points", "eph_craft_batch_restart", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
     "eph_craft_batch_destroy", "eph_hermite_eval", "eph_hermite_join", "eph_transitions_join", "eph_apsides_join", "eph_plot_points",
+    "eph_closest_separation", "eph_craft_batch_closest_separation",
 ]
 
 
@@ -99,6 +100,14 @@ class PlotRequest(C.Structure):
     _fields_ = [("source_body", C.c_int32), ("reference_body", C.c_int32), ("knot_first", C.c_int64),
                 ("knot_count", C.c_int64), ("start", C.c_double), ("end", C.c_double), ("bound", C.c_int32),
                 ("enabled", C.c_int32), ("tan2_angular_resolution", C.c_double), ("max_points", C.c_int64)]
+
+
+class SeparationRequest(C.Structure):
+    """eph_separation_request: one closest-separation search of target plotting (ephemeris_explorer/src/analysis.rs:344-348)."""
+    _fields_ = [("source_body", C.c_int32), ("target_body", C.c_int32), ("source_knot_first", C.c_int64),
+                ("source_knot_count", C.c_int64), ("target_knot_first", C.c_int64), ("target_knot_count", C.c_int64),
+                ("left", C.c_double), ("right", C.c_double), ("precision", C.c_double), ("max_iterations", C.c_int64),
+                ("metric", C.c_int32)]
 
 
 class AdaptiveParams(C.Structure):
@@ -224,6 +233,9 @@ def _lib():
     L.eph_hermite_eval.argtypes = [i64, _dp, _dp, _dp, i64, _dp, _dp, _dp, _u8p]
     L.eph_plot_points.argtypes = [vp, C.POINTER(PlotView), i64, C.POINTER(PlotRequest), i64, _dp, _dp, _dp, i64, _dp,
                                   C.POINTER(C.c_float), _i64p, _i32p, _dp]
+    L.eph_closest_separation.argtypes = [vp, i64, C.POINTER(SeparationRequest), i64, _dp, _dp, _dp, _u8p, _dp, _dp, _i32p, _i32p, _dp]
+    L.eph_craft_batch_closest_separation.argtypes = [vp, i64, C.POINTER(SeparationRequest), _i64p, _i64p, _u8p, _dp, _dp, _i32p,
+                                                     _i32p, _dp]
     L.eph_hermite_join.argtypes = [i64, _dp, _dp, _dp, i64, _dp, _dp, _dp, i64, _dp, _dp, _dp, _i64p]
     L.eph_transitions_join.argtypes = [i64, _dp, _i32p, i64, _dp, _i32p, f64, i64, _dp, _i32p, _i64p]
     L.eph_apsides_join.argtypes = [i64, _dp, _dp, _i32p, _i32p, i64, _dp, _dp, _i32p, _i32p, f64, i64, _dp, _dp, _i32p,
@@ -913,6 +925,31 @@ class SpacecraftBatch:
                                                    _p(fail)), "eph_craft_batch_plot_points")
         return [(int(st[i]), float(fail[i]), ot[i, :cnt[i]].copy(), ox[i, :cnt[i]].copy()) for i in range(n)]
 
+    def closest_separation(self, requests, craft=None, target_craft=None):
+        """The closest-separation search of target plotting on the batch's own knots (eph_craft_batch_closest_separation):
+        request p searches craft craft[p] (None: request p is craft p) against body requests[p]["target_body"] of the live
+        table or craft target_craft[p] of this batch (exactly one of the two >= 0; target_craft None: bodies only).
+        requests: list of dict(target_body, left, right, precision, max_iterations, metric), or one dict for all.
+        -> list of dict(found, time, distance, iterations, status, failed_at), what closest_separation() returns for the
+        knots of the two craft."""
+        crafts = None if craft is None else np.ascontiguousarray(craft, dtype=np.int64).ravel()
+        targets = None if target_craft is None else np.ascontiguousarray(target_craft, dtype=np.int64).ravel()
+        if isinstance(requests, dict):
+            requests = [requests] * (self.n if crafts is None else len(crafts))
+        n = len(requests)
+        if (crafts is not None and len(crafts) != n) or (targets is not None and len(targets) != n):
+            raise ValueError("SpacecraftBatch.closest_separation: one craft (and one target craft) per request")
+        arr = (SeparationRequest * max(n, 1))()
+        for i, r in enumerate(requests):
+            if "source_body" in r or "source_knots" in r or "target_knots" in r:
+                raise ValueError("SpacecraftBatch.closest_separation: source and target craft are the batch's (no source_body / knots)")
+            arr[i] = _separation_request(r)
+        out = _SeparationOut(n)
+        _check(self._L.eph_craft_batch_closest_separation(self._h, n, arr, None if crafts is None else _p(crafts, _i64p),
+                                                          None if targets is None else _p(targets, _i64p), *out.args()),
+               "eph_craft_batch_closest_separation")
+        return out.rows(n)
+
     UNSELECTED = np.iinfo(np.int32).min     # restart(): the outcome entry of a craft `which` did not select (never written)
 
     def restart(self, burns, plan_end=None, params=None, which=None):
@@ -1066,6 +1103,50 @@ def plot_points(ephemeris, view, requests, knots=None):
                                   ox.ctypes.data_as(C.POINTER(C.c_float)), _p(cnt, _i64p), _p(st, _i32p), _p(fail)),
            "eph_plot_points")
     return [(int(st[i]), float(fail[i]), ot[i, :cnt[i]].copy(), ox[i, :cnt[i]].copy()) for i in range(n)]
+
+
+def _separation_request(r):
+    sf, sc = r.get("source_knots", (0, 0))
+    tf, tc = r.get("target_knots", (0, 0))
+    return SeparationRequest(int(r.get("source_body", -1)), int(r.get("target_body", -1)), int(sf), int(sc), int(tf), int(tc),
+                             float(r["left"]), float(r["right"]), float(r.get("precision", 0.001)), int(r.get("max_iterations", 1000)),
+                             int(r.get("metric", 0)))
+
+
+class _SeparationOut:
+    """the six output arrays of the two closest-separation calls"""
+
+    def __init__(self, n):
+        m = max(n, 1)
+        self.found, self.time, self.distance = np.zeros(m, np.uint8), np.zeros(m), np.zeros(m)
+        self.iterations, self.status, self.failed_at = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m)
+
+    def args(self):
+        return (_p(self.found, _u8p), _p(self.time), _p(self.distance), _p(self.iterations, _i32p), _p(self.status, _i32p),
+                _p(self.failed_at))
+
+    def rows(self, n):
+        return [dict(found=bool(self.found[i]), time=float(self.time[i]), distance=float(self.distance[i]),
+                     iterations=int(self.iterations[i]), status=int(self.status[i]), failed_at=float(self.failed_at[i]))
+                for i in range(n)]
+
+
+def closest_separation(ephemeris, requests, knots=None):
+    """setup_target_plotting's search (ephemeris_explorer/src/analysis.rs:344-366): RelativeTrajectory::
+    closest_separation_between + PlotSeparation.distance for a batch of (trajectory, target) pairs, on the device.
+    requests: list of dict(source_body | source_knots=(first, count), target_body | target_knots=(first, count), left, right,
+    precision=0.001, max_iterations=1000, metric=0 (distance_squared_at) | 1 (distance_at)); knots: (t, pos, vel) arrays the
+    Hermite trajectories index into. -> list of dict(found, time, distance, iterations, status, failed_at)."""
+    n = len(requests)
+    arr = (SeparationRequest * max(n, 1))()
+    for i, r in enumerate(requests):
+        arr[i] = _separation_request(r)
+    kt, kp, kv = (np.zeros(0), np.zeros((0, 3)), np.zeros((0, 3))) if knots is None else (_f64(knots[0]).ravel(),
+                                                                                        _f64(knots[1]).reshape(-1, 3),
+                                                                                        _f64(knots[2]).reshape(-1, 3))
+    out = _SeparationOut(n)
+    _check(_lib().eph_closest_separation(ephemeris._h, n, arr, len(kt), _p(kt), _p(kp), _p(kv), *out.args()), "eph_closest_separation")
+    return out.rows(n)
 
 
 def hermite_join(lhs, rhs):

@@ -57,4 +57,26 @@ int craft_events_search(eph_craft_batch *b, hipStream_t s);   // craft_events.hi
 // craft.hip: Timeline::new (spacecraft.rs:129-152) of one craft's burns, appended to `segs` (create, restart, divergence time)
 void timeline_new(long long nburns, const double *burn_start, const double *burn_end, const double *burn_acc, const int32_t *burn_ref,
                   std::vector<SegmentDev> &segs);
+// Lanes in slab-column order for the units that run one lane per request over a craft's knot column (craft_plot.hip,
+// craft_separation.hip): request p reads craft craft[p] (null: craft p); lane l serves request lane_item[l] and reads column
+// lane_col[l]. A counting sort by column, stable in request order; an undealt batch asked craft by craft is in that order already.
+inline void lanes_by_column(const eph_craft_batch *b, size_t n_items, const int64_t *craft, std::vector<long long> &lane_item,
+                            std::vector<int> &lane_col) {
+    const size_t n = (size_t)b->n;
+    const bool dealt = !b->h_slot.empty();
+    lane_item.resize(n_items);
+    lane_col.resize(n_items);
+    if (!dealt && !craft) {
+        for (size_t p = 0; p < n_items; ++p) { lane_item[p] = (long long)p; lane_col[p] = (int)p; }
+        return;
+    }
+    auto column = [&](size_t p) { const size_t c = craft ? (size_t)craft[p] : p; return dealt ? (size_t)b->h_slot[c] : c; };
+    std::vector<size_t> first(n + 1, 0);
+    for (size_t p = 0; p < n_items; ++p) first[column(p) + 1] += 1;
+    for (size_t c = 0; c < n; ++c) first[c + 1] += first[c];
+    for (size_t p = 0; p < n_items; ++p) {
+        const size_t c = column(p), l = first[c]++;
+        lane_item[l] = (long long)p; lane_col[l] = (int)c;
+    }
+}
 }  // namespace eph

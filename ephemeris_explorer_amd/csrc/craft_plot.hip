@@ -129,24 +129,12 @@ int32_t eph_craft_batch_plot_points(eph_craft_batch *b, const eph_plot_view *vie
         if (craft)
             for (int64_t p = 0; p < n_plots; ++p)
                 if (craft[p] < 0 || craft[p] >= b->n) return EPH_ERR_BAD_ARGUMENT;
-        const size_t n = (size_t)b->n, np_all = (size_t)n_plots, cap = (size_t)capacity;
-        // lanes in slab-column order (a counting sort by column, stable in plot order); an undealt batch plotted craft by craft is in
-        // that order already
+        const size_t np_all = (size_t)n_plots, cap = (size_t)capacity;
+        // lanes in slab-column order (craft_batch.h)
         const bool dealt = !b->h_slot.empty();
-        std::vector<long long> lane_plot(np_all);
-        std::vector<int> lane_col(np_all);
-        if (!dealt && !craft) {
-            for (size_t p = 0; p < np_all; ++p) { lane_plot[p] = (long long)p; lane_col[p] = (int)p; }
-        } else {
-            auto column = [&](size_t p) { const size_t c = craft ? (size_t)craft[p] : p; return dealt ? (size_t)b->h_slot[c] : c; };
-            std::vector<size_t> first(n + 1, 0);
-            for (size_t p = 0; p < np_all; ++p) first[column(p) + 1] += 1;
-            for (size_t c = 0; c < n; ++c) first[c + 1] += first[c];
-            for (size_t p = 0; p < np_all; ++p) {
-                const size_t c = column(p), l = first[c]++;
-                lane_plot[l] = (long long)p; lane_col[l] = (int)c;
-            }
-        }
+        std::vector<long long> lane_plot;
+        std::vector<int> lane_col;
+        lanes_by_column(b, np_all, craft, lane_plot, lane_col);
         std::shared_lock<std::shared_mutex> table_lock(b->eph->mu, std::defer_lock);
         if (any_reference) table_lock.lock();
         EPH_HIP(hipSetDevice(b->device));

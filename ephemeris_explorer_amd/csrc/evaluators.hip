@@ -1,9 +1,10 @@
 // evaluators.hip -- evaluators that never touch a spacecraft batch: the debug window's interpolation-error scan of the bodies' table,
-// CubicHermiteSpline evaluation at many epochs, and the adaptive plot sampling.
+// CubicHermiteSpline evaluation at many epochs, the adaptive plot sampling and the closest-separation search.
 //
 // Mirrors (paths relative to the reference repository root):
 //   the interpolation-error scan                        ephemeris_explorer/src/ui/windows/debug.rs:182-238
-// The spline evaluations and the sampler themselves (trajectory.rs, plot.rs) are trajectory_eval.h's, with their line numbers.
+// The spline evaluations, the sampler and the search themselves (trajectory.rs, plot.rs, analysis.rs) are trajectory_eval.h's, with
+// their line numbers.
 #include <algorithm>
 #include <vector>
 
@@ -101,6 +102,39 @@ __global__ void __launch_bounds__(64) k_plot_points(const PlotArgs a) {
                             KnotArrays{rq.knot_count, a.knot_t + rq.knot_first, a.knot_pos + 3 * rq.knot_first, a.knot_vel + 3 * rq.knot_first}};
     PlotRowSink sink = {a.out_t + p * a.capacity, a.out_xyz + p * a.capacity * 3, a.out_count + p, a.out_status + p, a.out_failed_at + p};
     plot_sample(a.table, a.view, rq, src, sink);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The closest-separation search of target plotting (closest_separation, trajectory_eval.h), one thread per request: source and
+// target are bodies of the table or ranges of the caller's knot arrays.
+// ------------------------------------------------------------------------------------------------------
+struct SeparationArgs {
+    long long n_requests;
+    BodyTable table;
+    const eph_separation_request *req;
+    const double *knot_t, *knot_pos, *knot_vel;
+    uint8_t *out_found;
+    double *out_time, *out_distance;
+    int *out_iterations, *out_status;
+    double *out_failed_at;
+};
+
+__global__ void __launch_bounds__(64) k_closest_separation(const SeparationArgs a) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.n_requests) return;
+    const eph_separation_request rq = a.req[p];
+    auto knots = [&](long long first, long long count) {
+        return KnotArrays{count, a.knot_t + first, a.knot_pos + 3 * first, a.knot_vel + 3 * first};
+    };
+    const SeparationTrajectory<KnotArrays> src = {a.table, rq.source_body, knots(rq.source_knot_first, rq.source_knot_count)};
+    const SeparationTrajectory<KnotArrays> tgt = {a.table, rq.target_body, knots(rq.target_knot_first, rq.target_knot_count)};
+    const Separation r = closest_separation(src, tgt, rq.left, rq.right, rq.precision, rq.max_iterations, rq.metric);
+    a.out_found[p] = (uint8_t)r.found;
+    a.out_time[p] = r.time;
+    a.out_distance[p] = r.distance;
+    a.out_iterations[p] = r.iterations;
+    a.out_status[p] = r.status;
+    a.out_failed_at[p] = r.failed_at;
 }
 
 }  // namespace eph
@@ -234,6 +268,65 @@ int32_t eph_plot_points(const eph_ephemeris *e, const eph_plot_view *view, int64
             EPH_HIP(hipMemcpy(out_t, d_t.p, sizeof(double) * np * cap, hipMemcpyDeviceToHost));
             EPH_HIP(hipMemcpy(out_xyz, d_xyz.p, sizeof(float) * 3 * np * cap, hipMemcpyDeviceToHost));
         }
+        return EPH_OK;
+    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+}
+
+int32_t eph_closest_separation(const eph_ephemeris *e, int64_t n_requests, const eph_separation_request *requests,
+                               int64_t n_knots, const double *knot_t, const double *knot_pos, const double *knot_vel,
+                               uint8_t *out_found, double *out_time, double *out_distance, int32_t *out_iterations,
+                               int32_t *out_status, double *out_failed_at) {
+    try {
+        if (!e || n_requests < 0 || n_knots < 0 ||
+            (n_requests > 0 && (!requests || !out_found || !out_time || !out_distance || !out_iterations || !out_status || !out_failed_at)) ||
+            (n_knots > 0 && (!knot_t || !knot_pos || !knot_vel)))
+            return EPH_ERR_BAD_ARGUMENT;
+        auto slice_ok = [&](int32_t body, int64_t first, int64_t count) {
+            return body >= 0 || (first >= 0 && count >= 0 && first <= n_knots && count <= n_knots - first);
+        };
+        for (int64_t p = 0; p < n_requests; ++p) {
+            const eph_separation_request &r = requests[p];
+            if (r.source_body < -1 || r.source_body >= e->n_bodies || r.target_body < -1 || r.target_body >= e->n_bodies ||
+                !slice_ok(r.source_body, r.source_knot_first, r.source_knot_count) ||
+                !slice_ok(r.target_body, r.target_knot_first, r.target_knot_count) || !separation_request_ok(r))
+                return EPH_ERR_BAD_ARGUMENT;
+        }
+        int st = check_device();
+        if (st) return st;
+        if (n_requests == 0) return EPH_OK;
+        std::shared_lock<std::shared_mutex> table_lock(e->mu);
+        EPH_HIP(hipSetDevice(e->device));
+        const size_t nk = (size_t)std::max<int64_t>(n_knots, 1), np = (size_t)n_requests;
+        DevBuf<eph_separation_request> d_req;
+        DevBuf<double> d_kt, d_kp, d_kv, d_time, d_dist, d_fail;
+        DevBuf<uint8_t> d_found;
+        DevBuf<int> d_it, d_st;
+        if ((st = d_req.alloc(np)) || (st = d_kt.alloc(nk)) || (st = d_kp.alloc(3 * nk)) || (st = d_kv.alloc(3 * nk)) ||
+            (st = d_found.alloc(np)) || (st = d_time.alloc(np)) || (st = d_dist.alloc(np)) || (st = d_it.alloc(np)) ||
+            (st = d_st.alloc(np)) || (st = d_fail.alloc(np)))
+            return st;
+        EPH_HIP(hipMemcpy(d_req.p, requests, sizeof(eph_separation_request) * np, hipMemcpyHostToDevice));
+        if (n_knots) {
+            EPH_HIP(hipMemcpy(d_kt.p, knot_t, sizeof(double) * n_knots, hipMemcpyHostToDevice));
+            EPH_HIP(hipMemcpy(d_kp.p, knot_pos, sizeof(double) * 3 * n_knots, hipMemcpyHostToDevice));
+            EPH_HIP(hipMemcpy(d_kv.p, knot_vel, sizeof(double) * 3 * n_knots, hipMemcpyHostToDevice));
+        }
+        SeparationArgs a{};
+        a.n_requests = n_requests;
+        a.table = {e->bodies.p, e->coeffs.p, e->ncoef.p};
+        a.req = d_req.p;
+        a.knot_t = d_kt.p; a.knot_pos = d_kp.p; a.knot_vel = d_kv.p;
+        a.out_found = d_found.p; a.out_time = d_time.p; a.out_distance = d_dist.p; a.out_iterations = d_it.p; a.out_status = d_st.p;
+        a.out_failed_at = d_fail.p;
+        hipLaunchKernelGGL(k_closest_separation, dim3((unsigned)((n_requests + 63) / 64)), dim3(64), 0, nullptr, a);
+        hipError_t he = hipGetLastError();
+        if (he != hipSuccess) { set_last_error("k_closest_separation", he); return EPH_ERR_HIP; }
+        EPH_HIP(hipMemcpy(out_found, d_found.p, np, hipMemcpyDeviceToHost));
+        EPH_HIP(hipMemcpy(out_time, d_time.p, sizeof(double) * np, hipMemcpyDeviceToHost));
+        EPH_HIP(hipMemcpy(out_distance, d_dist.p, sizeof(double) * np, hipMemcpyDeviceToHost));
+        EPH_HIP(hipMemcpy(out_iterations, d_it.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+        EPH_HIP(hipMemcpy(out_status, d_st.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+        EPH_HIP(hipMemcpy(out_failed_at, d_fail.p, sizeof(double) * np, hipMemcpyDeviceToHost));
         return EPH_OK;
     } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
 }

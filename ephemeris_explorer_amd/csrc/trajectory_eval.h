@@ -1,10 +1,12 @@
-// trajectory_eval.h -- the reference's trajectory evaluation and its adaptive plot sampling, each operation stated once for every
-// device unit: a UniformSpline given by its table entry, a body of the live table, a CubicHermiteSpline over knots wherever they lie,
-// the plot sampler over any such trajectory. Every function restates the reference's operation order bit for bit
-// (-ffp-contract=off; the association of every expression is the reference's): a correction is made here and nowhere else.
-// Device code only, every function inlined into its kernel. Not here, on purpose: the sweep's own body loop (craft_sweep.hip: Horner
-// over all kDiv rows, spline_locate_fast), k_craft_tau (approximate by design) and the event search's struct Hermite
-// (craft_events.hip: coefficients built once per step, evaluated many times).
+// trajectory_eval.h -- the reference's trajectory evaluation, its adaptive plot sampling and its closest-separation search, each
+// operation stated once for every device unit: a UniformSpline given by its table entry, a body of the live table, a
+// CubicHermiteSpline over knots wherever they lie, the plot sampler and the search over any such trajectory. Every function restates
+// the reference's operation order bit for bit (-ffp-contract=off; the association of every expression is the reference's): a
+// correction is made here and nowhere else.
+// Device code only (but separation_request_ok, the host's check of what both searches refuse), every function inlined into its
+// kernel. Not here, on purpose: the sweep's own body loop (craft_sweep.hip: Horner over all kDiv rows, spline_locate_fast),
+// k_craft_tau (approximate by design) and the event search's struct Hermite (craft_events.hip: coefficients built once per step,
+// evaluated many times).
 //
 // Mirrors (paths relative to the reference repository root):
 //   UniformSpline::{position, state_vector, get_polynomial}, Polynomial::{eval, eval_and_deriv}, eval_slice_horner
@@ -13,6 +15,9 @@
 //                                                                     ephemeris/src/trajectory.rs:645-696,756-797
 //   RelativeTrajectory::{start, end, len, state_vector}              ephemeris/src/trajectory.rs:277-334
 //   compute_plot_points_parallel, PlotPoints::new, angular_distance   ephemeris_explorer/src/ui/world/plot.rs:93-149,272-374,429-436
+//   RelativeTrajectory::closest_separation_between                   ephemeris/src/trajectory.rs:202-248
+//   Trajectory::{distance_squared_at, distance_at}                   ephemeris_explorer/src/dynamics/mod.rs:133-146
+//   setup_target_plotting (the search's caller and PlotSeparation)   ephemeris_explorer/src/analysis.rs:344-366
 // glam::DVec3 / DMat3 operations (crate glam 0.30.10, not on disk) are restated from the published crate.
 #pragma once
 #include "craft_device.h"
@@ -247,6 +252,102 @@ __device__ __forceinline__ void plot_sample(const BodyTable &tb, const eph_plot_
         out.push(np++, t, ppos);
     }
     out.count(np);
+}
+
+// ---- the closest-separation search (target plotting) ----------------------------------------------------------------------------
+struct Separation {           // what one search returns
+    int found;                      // 1 = Some(time), 0 = None or a failure
+    double time;                    // the epoch of closest separation
+    double distance;                // PlotSeparation.distance at that epoch
+    int iterations;                 // the value of the loop counter i at return
+    int status;                     // EPH_OK; EPH_EVAL_FAILED: the reference unwraps a None position at failed_at
+    double failed_at;
+};
+// What a search cannot run with, for both entry points: a metric outside 0..1, a NaN window, an iteration cap outside 0 .. 2^20.
+inline bool separation_request_ok(const eph_separation_request &r) {
+    return (r.metric == 0 || r.metric == 1) && r.left == r.left && r.right == r.right && r.max_iterations >= 0 &&
+           r.max_iterations <= (1LL << 20);
+}
+// A trajectory of the search: body >= 0: that body of the table (bounds as plot_sample takes them from the BodyEntry); otherwise the
+// CubicHermiteSpline over `knots`, whose ::position is the position half of ::state_vector (the same operations, a knot hit included).
+template <class Knots>
+struct SeparationTrajectory {
+    const BodyTable &table;
+    int body;
+    Knots knots;
+    __device__ __forceinline__ void bounds(double &start, double &end) const {
+        if (body >= 0) {
+            const BodyEntry be = table.bodies[body];
+            start = be.start; end = be.start + be.span;
+        } else {
+            long long segs;
+            hermite_bounds(knots, start, end, segs);
+        }
+    }
+    __device__ __forceinline__ bool position(double t, V3 &p) const {
+        if (body >= 0) return body_position(table, body, t, p);
+        V3 v;
+        return hermite_state_vector(knots, t, p, v);
+    }
+};
+// RelativeTrajectory::closest_separation_between (trajectory.rs:202-248) of `src` relative to `tgt` with one of the app's two
+// distance closures, then PlotSeparation.distance (analysis.rs:362-366).
+//   Source, Target: bounds(start, end) of the trajectory and position(t, p) (false = None).
+//   metric 0: Trajectory::distance_squared_at, 1: Trajectory::distance_at (dynamics/mod.rs:133-146): source position first, then
+//   the target's; glam distance_squared = (a - b).length_squared() = (x*x + y*y) + z*z, distance = its sqrt.
+// Epoch / Duration arithmetic is plain f64; Ord::max / Ord::min on Epoch: a.max(b) = b < a ? a : b, a.min(b) = b < a ? b : a (on
+// equal operands max yields b and min yields a, which only +-0 can tell apart).
+// Both distances are evaluated before the test, so max_iterations = 0 evaluates once and returns with iterations = 1. The caller
+// bounds max_iterations (2^20): with a precision of 0 or NaN the reference runs until its cap, and this loop must end.
+// The one deliberate departure: a NaN difference d. The reference then branches on the sign bit of a NaN, which IEEE leaves to the
+// platform; here that is EPH_EVAL_FAILED with failed_at = mid1 and found = 0, before the precision test.
+template <class Source, class Target>
+__device__ __forceinline__ Separation closest_separation(const Source &src, const Target &tgt, double left, double right,
+                                                         double precision, long long max_iterations, int metric) {
+    Separation out = {0, 0.0, 0.0, 0, EPH_OK, 0.0};
+    double sstart, send, tstart, tend;
+    src.bounds(sstart, send);
+    tgt.bounds(tstart, tend);
+    const double start = tstart < sstart ? sstart : tstart;         // self.trajectory.start().max(reference.start())  :283-288
+    const double end = tend < send ? tend : send;                   // self.trajectory.end().min(reference.end())      :291-296
+    left = left < start ? start : left;                             // self.start().max(left)   :223
+    right = right < end ? right : end;                              // self.end().min(right)    :224
+    if (right <= left) return out;                                  // None
+    // |at| t1.distance_squared_at(t2, at).unwrap() / t1.distance_at(t2, at).unwrap()
+    auto dist = [&](double at, double &d) -> bool {
+        V3 a, b;
+        if (!src.position(at, a)) return false;                     // self.position(at)?
+        if (!tgt.position(at, b)) return false;                     // other.position(at)?
+        const V3 r = sub(a, b);
+        const double d2 = dot(r, r);
+        d = metric ? sqrt(d2) : d2;
+        return true;
+    };
+    long long i = 0;
+    double mid1, mid2;
+    for (;;) {                                                      // the ternary search
+        i += 1;
+        out.iterations = (int)i;
+        const double total = right - left;
+        mid1 = left + total / 3.0;
+        mid2 = right - total / 3.0;
+        double d1, d2;
+        if (!dist(mid1, d1)) { out.status = EPH_EVAL_FAILED; out.failed_at = mid1; return out; }
+        if (!dist(mid2, d2)) { out.status = EPH_EVAL_FAILED; out.failed_at = mid2; return out; }
+        const double d = d1 - d2;
+        if (d != d) { out.status = EPH_EVAL_FAILED; out.failed_at = mid1; return out; }     // the departure told above
+        if (fabs(d) < precision || i > max_iterations) break;
+        if (!__builtin_signbit(d)) left = mid1; else right = mid2;  // d.is_sign_positive()
+    }
+    const double time = mid1 + (mid2 - mid1) / 2.0;
+    // relative.position(time).unwrap().length(): the reference (the target) first  trajectory.rs:319-325
+    V3 tp, sp;
+    if (!tgt.position(time, tp) || !src.position(time, sp)) { out.status = EPH_EVAL_FAILED; out.failed_at = time; return out; }
+    const V3 r = sub(sp, tp);
+    out.found = 1;
+    out.time = time;
+    out.distance = sqrt(dot(r, r));
+    return out;
 }
 
 }  // namespace eph

@@ -545,6 +545,60 @@ int32_t eph_craft_batch_plot_points(eph_craft_batch *b, const eph_plot_view *vie
                                     double *out_t, float *out_xyz, int64_t *out_count, int32_t *out_status,
                                     double *out_failed_at);
 
+/* ---- target plotting: the closest-separation search (ephemeris_explorer/src/analysis.rs:308-371) -------------------
+ * setup_target_plotting for a batch of (trajectory, OrbitTarget) pairs, one device thread per request:
+ * RelativeTrajectory::closest_separation_between(left, right, precision, max_iterations, distance) (ephemeris/src/
+ * trajectory.rs:202-248; the ternary search, operation for operation) with one of the app's two distance closures, then
+ * PlotSeparation.distance = relative.position(time).unwrap().length() (analysis.rs:362-366). A trajectory is a body of
+ * the ephemeris or a ship's CubicHermiteSpline given as knots; the search window is [max(starts, left), min(ends,
+ * right)] of the two (trajectory.rs:223-224,283-296). */
+typedef struct eph_separation_request {
+    int32_t source_body, target_body;           /* >= 0: body of the ephemeris; -1: Hermite knots */
+    int64_t source_knot_first, source_knot_count;
+    int64_t target_knot_first, target_knot_count;
+    double left, right;                         /* plot.start / plot.end */
+    double precision;                           /* the app: 0.001 */
+    int64_t max_iterations;                     /* the app: 1000 */
+    int32_t metric;                             /* 0 distance_squared_at, 1 distance_at (dynamics/mod.rs:133-146) */
+} eph_separation_request;
+/* Per request p: out_found[p] = 1 with out_time[p] = the Some(epoch) and out_distance[p] = the separation there (km), or 0
+ * for None (an empty window, right <= left) and for a failure (time and distance 0). out_iterations[p] = the loop
+ * counter at return (0 for None; both distances are evaluated before the test, so max_iterations = 0 returns 1).
+ * out_status[p]: EPH_OK; EPH_EVAL_FAILED with out_failed_at[p] = the epoch where the reference unwraps a None position,
+ * inside the loop or at the result (an empty knot slice, bounded by Epoch::MIN / MAX, reaches this; so may the last ulp
+ * of a body's spline). One deliberate departure: where the difference of the two distances is NaN the reference
+ * branches on the sign bit of a NaN, which IEEE leaves to the platform; here that is EPH_EVAL_FAILED with failed_at =
+ * mid1 of that iteration. Trajectories are bodies of the table (as it is when the call starts) or slices [first, first +
+ * count) of the caller's knot arrays (n_knots knots); body-body, ship-body, ship-ship and body-ship are all allowed.
+ * EPH_ERR_BAD_ARGUMENT (nothing written, no device work): NULL ephemeris; n_requests < 0 or n_knots < 0; NULL requests or
+ * outputs with requests to do; NULL knot arrays with n_knots > 0; a body index < -1 or >= n_bodies; a knot slice
+ * outside 0 .. n_knots (of a side whose body is -1); metric outside 0..1; NaN left or right; max_iterations < 0 or > 2^20
+ * (with a precision of 0 or NaN the reference runs until its cap, and a kernel must end). n_requests == 0: EPH_OK, nothing
+ * written. */
+int32_t eph_closest_separation(const eph_ephemeris *e, int64_t n_requests, const eph_separation_request *requests,
+                               int64_t n_knots, const double *knot_t, const double *knot_pos_xyz, const double *knot_vel_xyz,
+                               uint8_t *out_found, double *out_time, double *out_distance, int32_t *out_iterations,
+                               int32_t *out_status, double *out_failed_at);
+/* The same search for ships that live in an eph_craft_batch: request p searches craft craft[p] of the batch (craft ==
+ * NULL: request p is craft p, so n_requests <= n_craft; a craft may appear in several requests) against either body
+ * requests[p].target_body of the bound ephemeris (table order; the LIVE table as it is when the call starts) or craft
+ * target_craft[p] of the same batch: exactly one of the two is >= 0 (target_craft == NULL: every target is a body; a
+ * craft may target itself). Both splines are the craft's knots 0 .. nknots - 1 as the batch holds them now, read from
+ * the knot slabs on the device: no knot crosses the bus. requests[p] as above with source_body == -1 and all four knot
+ * fields 0. For every request all six outputs are bit for bit what eph_closest_separation returns for the arrays
+ * eph_craft_batch_knots gives for the two craft; a craft with one knot gives found 0, EPH_OK, so after
+ * eph_craft_batch_reset_knots only the drained slab's span is searched.
+ * Does not change the batch (state, knots, events, a pending retry, the FSAL stages, the deal to the lanes); works on
+ * clones. n_requests == 0 or an empty batch: EPH_OK, nothing written. EPH_ERR_BAD_ARGUMENT (nothing written, no device
+ * work): NULL batch; n_requests < 0; NULL requests or outputs with requests to do; craft[p] or a used target_craft[p]
+ * outside 0 .. n_craft - 1; craft == NULL with n_requests > n_craft; source_body != -1; a non-zero knot field;
+ * target_body < -1 or >= n_bodies; the target given neither or both ways (target_craft[p] < 0 counts as not given);
+ * metric, left, right and max_iterations as above. */
+int32_t eph_craft_batch_closest_separation(eph_craft_batch *b, int64_t n_requests, const eph_separation_request *requests,
+                                           const int64_t *craft, const int64_t *target_craft,
+                                           uint8_t *out_found, double *out_time, double *out_distance,
+                                           int32_t *out_iterations, int32_t *out_status, double *out_failed_at);
+
 /* SpacecraftPropagator::join(lhs, rhs) (ephemeris/src/propagators/spacecraft.rs:558-561; the app's
  * PredictionTarget::merge, ephemeris_explorer/src/dynamics/spacecraft.rs:830-841): lhs.clear_after(rhs.start())
  * -- keep the knots with t < rhs.start() (trajectory.rs:842-845; rhs.start() of an empty spline is Epoch::MIN,

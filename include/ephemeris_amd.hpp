@@ -511,6 +511,42 @@ public:
         }
         return out;
     }
+    // setup_target_plotting's search (ephemeris_explorer/src/analysis.rs:344-366) for ships that live in the batch, on the device, from
+    // the knots the batch holds: RelativeTrajectory::closest_separation_between(left, right, precision, max_iterations, distance) of
+    // craft craft[p] (craft empty: request p is craft p) against body requests[p].target_body of the ephemeris or craft
+    // target_craft[p] of this batch (exactly one of the two >= 0; target_craft empty: bodies only), then PlotSeparation.distance.
+    // requests[p]: source_body -1, the four knot fields 0. One Separation per request: found = Some / None, the epoch and the
+    // distance there, the search's iteration count, the status (EPH_OK, EPH_EVAL_FAILED) and the epoch a failure happened at.
+    struct Separation {
+        bool found = false;
+        double time = 0.0, distance = 0.0;
+        int32_t iterations = 0, status = EPH_OK;
+        double failed_at = 0.0;
+    };
+    std::vector<Separation> closest_separation(const std::vector<eph_separation_request> &requests, const std::vector<int64_t> &craft = {},
+                                               const std::vector<int64_t> &target_craft = {}) const {
+        const size_t np = requests.size();
+        if ((!craft.empty() && craft.size() != np) || (!target_craft.empty() && target_craft.size() != np))
+            throw std::invalid_argument("SpacecraftBatch::closest_separation: one craft (and one target craft) per request");
+        if (craft.empty() && np > static_cast<size_t>(n_)) throw std::invalid_argument("SpacecraftBatch::closest_separation: more requests than craft");
+        std::vector<uint8_t> found(np);
+        std::vector<double> time(np), distance(np), failed(np);
+        std::vector<int32_t> iterations(np), status(np);
+        detail::check(eph_craft_batch_closest_separation(h_, static_cast<int64_t>(np), requests.data(), craft.empty() ? nullptr : craft.data(),
+                                                         target_craft.empty() ? nullptr : target_craft.data(), found.data(), time.data(),
+                                                         distance.data(), iterations.data(), status.data(), failed.data()),
+                      "eph_craft_batch_closest_separation");
+        std::vector<Separation> out(np);
+        for (size_t p = 0; p < np; ++p) {
+            out[p].found = found[p] != 0;
+            out[p].time = time[p];
+            out[p].distance = distance[p];
+            out[p].iterations = iterations[p];
+            out[p].status = status[p];
+            out[p].failed_at = failed[p];
+        }
+        return out;
+    }
     // Flight-plan restart in place (FlightPlan::restart_propagator + apply_flight_plan, flight_plan.rs:263-361), on the device: every
     // selected craft (which: one flag per craft, empty = all) continues from the knot where its new plan (one burn list per craft)
     // diverges from the old one. plan_end: one FlightPlan.end per craft (empty = +inf); params: the batch's new parameters (only with
