@@ -36,17 +36,6 @@ struct eph_prop {
     eph_nbody view;
 };
 
-#define EPH_GUARD_BEGIN try {
-#define EPH_GUARD_END                                   \
-    }                                                   \
-    catch (const std::bad_alloc &) {                    \
-        return EPH_ERR_OUT_OF_MEMORY;                   \
-    }                                                   \
-    catch (...) {                                       \
-        set_last_error_text("unexpected C++ exception"); \
-        return EPH_ERR_HIP;                             \
-    }
-
 // the library is compiled with -fvisibility=hidden: the boundary below (and the rest of it in craft.hip, craft_events.hip, ephemeris_table.hip, evaluators.hip) is ALL it exports
 #pragma GCC visibility push(default)
 extern "C" {

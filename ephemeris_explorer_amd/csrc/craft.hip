@@ -210,16 +210,14 @@ static int craft_sort(eph_craft_batch *b) {
     DevBuf<float> tau;
     int st = tau.alloc(n4);
     if (st) return st;
-    hipLaunchKernelGGL(k_craft_tau, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, n, b->eph->n_bodies, b->eph->bodies.p,
-                       b->eph->coeffs.p, b->time.p, b->y.p, tau.p);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) { set_last_error("k_craft_tau", he); return EPH_ERR_HIP; }
+    EPH_LAUNCH("k_craft_tau", k_craft_tau, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, n, b->eph->n_bodies, b->eph->bodies.p,
+               b->eph->coeffs.p, b->time.p, b->y.p, tau.p);
     if ((st = b->perm.alloc(n4)) || (st = b->slot_of.alloc(n4))) return st;
     PinnedStage stage(2 * n4 * sizeof(int));
     if (stage.status()) return stage.status();
     StreamIdleOnExit idle(b->stream);
     const unsigned cgrid = (unsigned)std::min<size_t>((n4 / 4 + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_copy16, dim3(cgrid), dim3(256), 0, b->stream, (long long)(n4 / 4), (const double2 *)tau.p, (double2 *)stage.dev());
+    EPH_LAUNCH("k_copy16", k_copy16, dim3(cgrid), dim3(256), b->stream, (long long)(n4 / 4), (const double2 *)tau.p, (double2 *)stage.dev());
     EPH_HIP(hipStreamSynchronize(b->stream));
     const float *h = static_cast<const float *>(stage.host());
     // stable LSD radix sort of the estimates (positive binary32 values order like their bit patterns; anything else goes last)
@@ -249,14 +247,12 @@ static int craft_sort(eph_craft_batch *b) {
     std::memcpy(hp, perm.data(), sizeof(int) * (size_t)n);
     std::memcpy(hp + n4, slot.data(), sizeof(int) * (size_t)n);
     const int *dp = static_cast<const int *>(stage.dev());
-    hipLaunchKernelGGL(k_copy16, dim3(cgrid), dim3(256), 0, b->stream, (long long)(n4 / 4), (const double2 *)dp, (double2 *)b->perm.p);
-    hipLaunchKernelGGL(k_copy16, dim3(cgrid), dim3(256), 0, b->stream, (long long)(n4 / 4), (const double2 *)(dp + n4), (double2 *)b->slot_of.p);
+    EPH_LAUNCH("k_copy16", k_copy16, dim3(cgrid), dim3(256), b->stream, (long long)(n4 / 4), (const double2 *)dp, (double2 *)b->perm.p);
+    EPH_LAUNCH("k_copy16", k_copy16, dim3(cgrid), dim3(256), b->stream, (long long)(n4 / 4), (const double2 *)(dp + n4), (double2 *)b->slot_of.p);
     b->h_slot = std::move(slot);
     // knot 0 (the initial state, uploaded in craft order) moves to the lanes' columns
-    hipLaunchKernelGGL(k_knot0_to_lanes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, n, b->perm.p, b->time.p, b->y.p,
-                       b->knot_t.p, b->knot_y.p);
-    he = hipGetLastError();
-    if (he != hipSuccess) { set_last_error("k_knot0_to_lanes", he); return EPH_ERR_HIP; }
+    EPH_LAUNCH("k_knot0_to_lanes", k_knot0_to_lanes, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, n, b->perm.p, b->time.p,
+               b->y.p, b->knot_t.p, b->knot_y.p);
     EPH_HIP(hipStreamSynchronize(b->stream));
     return EPH_OK;
 }
@@ -318,6 +314,32 @@ void eph::timeline_new(long long nburns, const double *burn_start, const double 
     if (cursor < EMAX) segs.push_back(SegmentDev{cursor, EMAX, 0, 0, 0, 0, -1});
 }
 
+int eph::burn_csr_check(long long n, const int64_t *burn_offset, const double *burn_start, const double *burn_end, const double *burn_acc,
+                        const int32_t *burn_ref, int n_bodies, const uint8_t *which, bool from_zero) {
+    if (!burn_offset) return EPH_OK;
+    if (burn_offset[0] < 0) return EPH_ERR_BAD_ARGUMENT;
+    for (long long i = 0; i < n; ++i)
+        if (burn_offset[i + 1] < burn_offset[i]) return EPH_ERR_BAD_ARGUMENT;
+    if (burn_offset[n] > (from_zero ? 0 : burn_offset[0]) && (!burn_start || !burn_end || !burn_acc || !burn_ref)) return EPH_ERR_BAD_ARGUMENT;
+    for (long long i = 0; i < n; ++i)
+        for (int64_t q = burn_offset[i]; (!which || which[i]) && q < burn_offset[i + 1]; ++q)
+            if (burn_ref[q] < -1 || burn_ref[q] >= n_bodies) return EPH_ERR_BAD_ARGUMENT;
+    return EPH_OK;
+}
+// ERKN integrates y'' = f(t, y) (P::ODE: SecondOrderODE, nystrom/explicit.rs:60): the spacecraft model is one only while no burn is
+// expressed in a frame built from the velocity (ReferenceFrame::Relative -> TNB of the relative state,
+// dynamics/spacecraft.rs:281-293). The reference cannot even express that combination.
+int eph::burn_erkn_check(long long n, const int64_t *burn_offset, const int32_t *burn_ref, const uint8_t *which) {
+    for (long long i = 0; burn_offset && i < n; ++i)
+        for (int64_t q = burn_offset[i]; (!which || which[i]) && q < burn_offset[i + 1]; ++q)
+            if (burn_ref[q] >= 0) {
+                set_last_error_text("Tsitouras75Nystrom (ERKN) needs a velocity-independent right-hand side: "
+                                    "burns must use the inertial frame");
+                return EPH_ERR_UNSUPPORTED;
+            }
+    return EPH_OK;
+}
+
 template <typename T>
 static int clone_buf(const DevBuf<T> &src, DevBuf<T> &dst, hipStream_t s) {
     if (!src.p) return EPH_OK;
@@ -336,35 +358,16 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
                                const int64_t *burn_offset, const double *burn_start, const double *burn_end,
                                const double *burn_acc, const int32_t *burn_ref, int32_t max_knots,
                                eph_craft_batch **out) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || n_craft < 0 || !method || !params || !out || max_knots < 1 || (n_craft > 0 && (!t0 || !pos || !vel)))
             return EPH_ERR_BAD_ARGUMENT;
-        // the burn tables are caller memory: validate before the first dereference (CSR offsets start at a
-        // non-negative value and never decrease; arrays present when any burn is; reference body -1 or a body index)
-        if (burn_offset) {
-            if (burn_offset[0] < 0) return EPH_ERR_BAD_ARGUMENT;
-            for (int64_t i = 0; i < n_craft; ++i)
-                if (burn_offset[i + 1] < burn_offset[i]) return EPH_ERR_BAD_ARGUMENT;
-            if (burn_offset[n_craft] > 0 && (!burn_start || !burn_end || !burn_acc || !burn_ref))
-                return EPH_ERR_BAD_ARGUMENT;
-            for (int64_t q = burn_offset[0]; q < burn_offset[n_craft]; ++q)
-                if (burn_ref[q] < -1 || burn_ref[q] >= e->n_bodies) return EPH_ERR_BAD_ARGUMENT;
-        }
-        int st = check_device();
-        if (st) return st;
+        // the burn tables are caller memory: validate before the first dereference
+        int st = burn_csr_check(n_craft, burn_offset, burn_start, burn_end, burn_acc, burn_ref, e->n_bodies, nullptr, true);
+        if (st || (st = check_device())) return st;
         std::shared_lock<std::shared_mutex> table_lock(e->mu);       // (the deal to the lanes reads the table)
         std::unique_ptr<eph_craft_batch> b(new eph_craft_batch());
         if (!find_erk(method, &b->rk) || !b->rk.has_embedded) return EPH_ERR_BAD_ARGUMENT;
-        // ERKN integrates y'' = f(t, y) (P::ODE: SecondOrderODE, nystrom/explicit.rs:60): the spacecraft model is one
-        // only while no burn is expressed in a frame built from the velocity (ReferenceFrame::Relative -> TNB of the
-        // relative state, dynamics/spacecraft.rs:281-293). The reference cannot even express that combination.
-        if (b->rk.nystrom == 2 && burn_offset)
-            for (int64_t q = burn_offset[0]; q < burn_offset[n_craft]; ++q)
-                if (burn_ref[q] >= 0) {
-                    set_last_error_text("Tsitouras75Nystrom (ERKN) needs a velocity-independent right-hand side: "
-                                        "burns must use the inertial frame");
-                    return EPH_ERR_UNSUPPORTED;
-                }
+        if (b->rk.nystrom == 2 && (st = burn_erkn_check(n_craft, burn_offset, burn_ref, nullptr))) return st;
         b->pv = default_pair_variant();
         b->eph = e;
         b->n = n_craft;
@@ -432,7 +435,7 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
         b->h_segs = std::move(segs);
         *out = b.release();
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 static int32_t craft_run(eph_craft_batch *b, double t_end, unsigned step_limit);
@@ -450,10 +453,8 @@ static int32_t craft_run(eph_craft_batch *b, double t_end, unsigned step_limit) 
     // every append since the last call is seen, and none lands while the kernels read
     std::shared_lock<std::shared_mutex> table_lock(b->eph->mu);
     if (!b->body_order.empty()) {
-        hipLaunchKernelGGL(k_permute_bodies, dim3((unsigned)((b->eph->n_bodies + 63) / 64)), dim3(64), 0, b->stream, b->eph->n_bodies,
-                           b->body_order_dev.p, b->eph->bodies.p, b->bodies_ordered.p);
-        hipError_t pe = hipGetLastError();
-        if (pe != hipSuccess) { set_last_error("k_permute_bodies", pe); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_permute_bodies", k_permute_bodies, dim3((unsigned)((b->eph->n_bodies + 63) / 64)), dim3(64), b->stream,
+                   b->eph->n_bodies, b->body_order_dev.p, b->eph->bodies.p, b->bodies_ordered.p);
     }
     CraftArgs a{};
     a.n_craft = b->n;
@@ -539,10 +540,8 @@ int32_t eph_craft_batch_summary(eph_craft_batch *b, eph_craft_record *out) {
     const auto t0 = tick();
     int st;
     if ((st = b->summary.reserve((size_t)b->n))) return st;
-    hipLaunchKernelGGL(k_craft_summary, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, b->stream, b->n, b->time.p, b->y.p,
-                       b->next_h.p, b->status.p, b->nknots.p, b->n_attempts.p, b->steps.p, b->summary.p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_last_error("k_craft_summary", e); return EPH_ERR_HIP; }
+    EPH_LAUNCH("k_craft_summary", k_craft_summary, dim3((unsigned)((b->n + 255) / 256)), dim3(256), b->stream, b->n, b->time.p, b->y.p,
+               b->next_h.p, b->status.p, b->nknots.p, b->n_attempts.p, b->steps.p, b->summary.p);
     const auto t1 = tick();
     EPH_HIP(hipMemcpyAsync(out, b->summary.p, sizeof(eph_craft_record) * (size_t)b->n, hipMemcpyDeviceToHost, b->stream));
     const auto t2 = tick();
@@ -555,7 +554,7 @@ int32_t eph_craft_batch_summary(eph_craft_batch *b, eph_craft_record *out) {
 // unspecified upstream). Table (file) order by default -- the library test's IndexMap; a maintainer who wants the bits of a given
 // app run passes that run's iteration order here. Burn reference bodies, SOI radii and event body indices keep the table's numbering.
 int32_t eph_craft_batch_set_body_order(eph_craft_batch *b, const int32_t *order) {
-    try {
+    EPH_GUARD_BEGIN
         if (!b) return EPH_ERR_BAD_ARGUMENT;
         EPH_HIP(hipSetDevice(b->device));
         EPH_HIP(hipStreamSynchronize(b->stream));
@@ -574,7 +573,7 @@ int32_t eph_craft_batch_set_body_order(eph_craft_batch *b, const int32_t *order)
         b->body_order.assign(order, order + n);
         if (n) EPH_HIP(hipMemcpy(b->body_order_dev.p, order, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 // IncrementalPropagator::step on a propagator whose last step returned Err (ephemeris/src/propagators/spacecraft.rs:598-615): nothing
 // in the reference remembers the failure -- the next step() simply runs AdaptiveRungeKuttaIntegrator::advance again from the state the
@@ -616,7 +615,7 @@ int32_t eph_timeline_divergence_time(int64_t n_old, const double *old_start, con
                                      const int32_t *old_ref, int64_t n_new, const double *new_start,
                                      const double *new_end, const double *new_acc, const int32_t *new_ref,
                                      double before, double *restart_epoch) {
-    try {
+    EPH_GUARD_BEGIN
         if (n_old < 0 || n_new < 0 || !restart_epoch || (n_old > 0 && (!old_start || !old_end || !old_acc || !old_ref)) ||
             (n_new > 0 && (!new_start || !new_end || !new_acc || !new_ref)))
             return EPH_ERR_BAD_ARGUMENT;
@@ -640,17 +639,15 @@ int32_t eph_timeline_divergence_time(int64_t n_old, const double *old_start, con
         if (!any) return EPH_ERR_BAD_ARGUMENT;                           // the reference unwraps (before <= Epoch::MIN)
         *restart_epoch = last;
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 int32_t eph_craft_batch_reset_knots(eph_craft_batch *b) {
     if (!b) return EPH_ERR_BAD_ARGUMENT;
     if (b->n == 0) return EPH_OK;
     EPH_HIP(hipSetDevice(b->device));
-    hipLaunchKernelGGL(k_craft_reset_knots, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, b->stream, b->n,
-                       b->nknots.p, b->status.p, b->knot_t.p, b->knot_y.p, b->events ? b->ev_seg.p : nullptr, b->slot_of.p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_last_error("k_craft_reset_knots", e); return EPH_ERR_HIP; }
+    EPH_LAUNCH("k_craft_reset_knots", k_craft_reset_knots, dim3((unsigned)((b->n + 255) / 256)), dim3(256), b->stream, b->n,
+               b->nknots.p, b->status.p, b->knot_t.p, b->knot_y.p, b->events ? b->ev_seg.p : nullptr, b->slot_of.p);
     EPH_HIP(hipStreamSynchronize(b->stream));
     return EPH_OK;
 }
@@ -658,7 +655,7 @@ int32_t eph_craft_batch_reset_knots(eph_craft_batch *b) {
 // SpacecraftPropagator: Clone (the UI snapshots a propagator and later resumes from the snapshot,
 // ephemeris_explorer/src/prediction.rs:224-229,378): a deep copy of every per-craft buffer, knots and events included
 int32_t eph_craft_batch_clone(eph_craft_batch *b, eph_craft_batch **out) {
-    try {
+    EPH_GUARD_BEGIN
         if (!b || !out) return EPH_ERR_BAD_ARGUMENT;
         *out = nullptr;
         EPH_HIP(hipSetDevice(b->device));
@@ -695,7 +692,7 @@ int32_t eph_craft_batch_clone(eph_craft_batch *b, eph_craft_batch **out) {
         EPH_HIP(hipStreamSynchronize(s));
         *out = c.release();
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 int32_t eph_craft_batch_knot_slabs(eph_craft_batch *b, int32_t first_knot, int32_t n_knots, double *knot_t,
@@ -719,10 +716,8 @@ int32_t eph_craft_batch_knot_slabs(eph_craft_batch *b, int32_t first_knot, int32
             StreamIdleOnExit idle(b->stream);
             for (long long r0 = 0; r0 < rows; r0 += rows_per_pass) {
                 const long long nr = std::min(rows_per_pass, rows - r0);
-                hipLaunchKernelGGL(k_rows_to_craft_order, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, nr, (long long)n,
-                                   b->slot_of.p, src + (size_t)r0 * n, static_cast<double *>(stage.dev()));
-                hipError_t he = hipGetLastError();
-                if (he != hipSuccess) { set_last_error("k_rows_to_craft_order", he); return EPH_ERR_HIP; }
+                EPH_LAUNCH("k_rows_to_craft_order", k_rows_to_craft_order, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, nr,
+                           (long long)n, b->slot_of.p, src + (size_t)r0 * n, static_cast<double *>(stage.dev()));
                 EPH_HIP(hipStreamSynchronize(b->stream));
                 std::memcpy(dst + (size_t)r0 * n, stage.host(), (size_t)nr * row_bytes);
             }

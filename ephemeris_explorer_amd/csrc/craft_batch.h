@@ -1,7 +1,11 @@
-// craft_batch.h -- struct eph_craft_batch (craft.hip owns it) for craft_events.hip, whose entry points fill and read the batch's
-// event slabs, and the two calls that cross between the two units.
+// craft_batch.h -- struct eph_craft_batch (craft.hip owns it) and what the units that read or restart a batch on the device share
+// (craft_events.hip, craft_eval.hip, craft_plot.hip, craft_separation.hip, craft_restart.hip): the view of the knot slabs a kernel
+// takes, the request-to-lane map, the pass timing of the EPH_TRACE_* variables, and the calls that cross between the units.
 #pragma once
+#include <chrono>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 #include "ephemeris_table.h"
@@ -57,6 +61,32 @@ int craft_events_search(eph_craft_batch *b, hipStream_t s);   // craft_events.hi
 // craft.hip: Timeline::new (spacecraft.rs:129-152) of one craft's burns, appended to `segs` (create, restart, divergence time)
 void timeline_new(long long nburns, const double *burn_start, const double *burn_end, const double *burn_acc, const int32_t *burn_ref,
                   std::vector<SegmentDev> &segs);
+// craft.hip: a burn CSR over n craft, caller memory, checked before its first use -- offsets (non-negative start, never decreasing),
+// the arrays present when a burn is (`from_zero`, creation's rule: whenever the CSR ends beyond 0), burn_ref = -1 or a body index for
+// every craft that `which` keeps (null: all): any of them EPH_ERR_BAD_ARGUMENT.
+int burn_csr_check(long long n, const int64_t *burn_offset, const double *burn_start, const double *burn_end, const double *burn_acc,
+                   const int32_t *burn_ref, int n_bodies, const uint8_t *which, bool from_zero);
+// craft.hip: on a checked CSR, EPH_ERR_UNSUPPORTED and its text for a kept burn in a frame built from the velocity (ERKN pairs)
+int burn_erkn_check(long long n, const int64_t *burn_offset, const int32_t *burn_ref, const uint8_t *which);
+
+// The knot slabs as a kernel reads them. The columns are lane positions (craft_sort): column() translates through `perm`.
+struct KnotSlabs {
+    long long n;                 // craft = columns of the slabs
+    int max_knots;
+    const int *nknots;           // [craft]
+    const int *perm;             // slab column -> craft (null: identity)
+    const double *knot_t;        // [k][column]
+    const double *knot_y;        // [k][6][column]
+    __device__ __forceinline__ long long craft_of(long long col) const { return perm ? perm[col] : col; }
+    __device__ __forceinline__ KnotColumn column(long long col) const { return column(col, craft_of(col)); }
+    // for k_craft_eval, which indexes its epochs by craft_of(col) too: through column(col) it loaded perm[col] twice (one more VMEM load)
+    __device__ __forceinline__ KnotColumn column(long long col, long long craft) const {
+        return KnotColumn{min(max(nknots[craft], 0), max_knots), n, knot_t + col, knot_y + col};
+    }
+};
+inline KnotSlabs knot_slabs(const eph_craft_batch *b) {
+    return {b->n, b->max_knots, b->nknots.p, b->h_slot.empty() ? nullptr : b->perm.p, b->knot_t.p, b->knot_y.p};
+}
 // Lanes in slab-column order for the units that run one lane per request over a craft's knot column (craft_plot.hip,
 // craft_separation.hip): request p reads craft craft[p] (null: craft p); lane l serves request lane_item[l] and reads column
 // lane_col[l]. A counting sort by column, stable in request order; an undealt batch asked craft by craft is in that order already.
@@ -79,4 +109,55 @@ inline void lanes_by_column(const eph_craft_batch *b, size_t n_items, const int6
         lane_item[l] = (long long)p; lane_col[l] = (int)c;
     }
 }
+// lanes_by_column of a call's requests, on the device as well
+struct LaneMap {
+    std::vector<long long> item;          // lane -> request
+    std::vector<int> col;                 // lane -> slab column of the request's craft
+    DevBuf<long long> d_item;
+    DevBuf<int> d_col;
+    // EPH_ERR_BAD_ARGUMENT: more requests than craft without `craft`, or a craft[p] outside the batch
+    int sort(const eph_craft_batch *b, size_t n_items, const int64_t *craft) {
+        if (!craft && (long long)n_items > b->n) return EPH_ERR_BAD_ARGUMENT;
+        if (craft)
+            for (size_t p = 0; p < n_items; ++p)
+                if (craft[p] < 0 || craft[p] >= b->n) return EPH_ERR_BAD_ARGUMENT;
+        lanes_by_column(b, n_items, craft, item, col);
+        return EPH_OK;
+    }
+    int upload(hipStream_t s) {           // the batch's device is current
+        int st;
+        if ((st = d_item.alloc(item.size())) || (st = d_col.alloc(col.size()))) return st;
+        EPH_HIP(hipMemcpyAsync(d_item.p, item.data(), sizeof(long long) * item.size(), hipMemcpyHostToDevice, s));
+        EPH_HIP(hipMemcpyAsync(d_col.p, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, s));
+        return EPH_OK;
+    }
+};
+// EPH_TRACE_<UNIT>=1: the kernel time (between the batch's two events) and the host copy time of a call's passes, printed as the
+// line scripts/<unit>_timing.py parses. With the variable unset no event is recorded and no clock is read.
+struct PassTrace {
+    bool on;
+    const eph_craft_batch *b;
+    double kernel_ms = 0.0, copy_ms = 0.0;
+    std::chrono::steady_clock::time_point c0;
+    PassTrace(const char *variable, const eph_craft_batch *batch) : b(batch) {
+        const char *env = getenv(variable);
+        on = env && atoi(env) != 0;
+    }
+    int kernel_begin() { if (on) EPH_HIP(hipEventRecord(b->ev0, b->stream)); return EPH_OK; }
+    int kernel_end() { if (on) EPH_HIP(hipEventRecord(b->ev1, b->stream)); return EPH_OK; }
+    void copy_begin() { if (on) c0 = std::chrono::steady_clock::now(); }     // after the stream's synchronisation
+    int copy_end() {
+        if (!on) return EPH_OK;
+        float ms = 0.0f;
+        EPH_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+        kernel_ms += ms;
+        copy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+        return EPH_OK;
+    }
+    void report(const char *unit, const char *what1, long long v1, const char *what2, long long v2, long long passes) const {
+        if (on)
+            fprintf(stderr, "%s: %s %lld %s %lld passes %lld kernel_ms %.4f host_copy_ms %.4f\n", unit, what1, v1, what2, v2, passes,
+                    kernel_ms, copy_ms);
+    }
+};
 }  // namespace eph

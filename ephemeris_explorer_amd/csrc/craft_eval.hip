@@ -5,14 +5,9 @@
 //   RelativeTrajectory::state_vector (reference first, `?`, one subtraction per component)   ephemeris/src/trajectory.rs:326-334
 // over CubicHermiteSpline::state_vector and UniformSpline::state_vector, which are trajectory_eval.h's.
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <shared_mutex>
 
 #include "craft_batch.h"
-#include "trajectory_eval.h"
 
 namespace eph {
 
@@ -32,12 +27,7 @@ __global__ void __launch_bounds__(64) k_craft_eval_reference(long long m, const 
 }
 
 struct CraftEvalArgs {
-    long long n;                 // craft = columns of the slabs
-    int max_knots;
-    const int *nknots;           // [craft]
-    const int *perm;             // slab column -> craft (null: identity); the knot slabs' columns are lane positions
-    const double *knot_t;        // [k][column]
-    const double *knot_y;        // [k][6][column]
+    KnotSlabs slabs;
     long long m;                 // epochs of this pass
     const double *at;            // shared: [m]; per craft: [m][craft]
     int per_craft;
@@ -54,10 +44,10 @@ struct CraftEvalArgs {
 // tried instead is told at hermite_state_vector (trajectory_eval.h).
 __global__ void __launch_bounds__(256) k_craft_eval(const CraftEvalArgs a) {
     const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= a.n) return;
-    const long long n = a.n;
-    const long long craft = a.perm ? a.perm[col] : col;
-    const KnotColumn knots = {min(max(a.nknots[craft], 0), a.max_knots), n, a.knot_t + col, a.knot_y + col};
+    if (col >= a.slabs.n) return;
+    const long long n = a.slabs.n;
+    const long long craft = a.slabs.craft_of(col);
+    const KnotColumn knots = a.slabs.column(col, craft);
     for (long long e = 0; e < a.m; ++e) {
         const double x = a.per_craft ? a.at[e * n + craft] : a.at[e];
         V3 rp = {0.0, 0.0, 0.0}, rv = {0.0, 0.0, 0.0};
@@ -106,18 +96,15 @@ extern "C" {
 
 int32_t eph_craft_batch_eval(eph_craft_batch *b, int64_t m, const double *at, int32_t per_craft, int32_t reference_body,
                              double *out_y, uint8_t *inside) {
-    try {
+    EPH_GUARD_BEGIN
         if (!b || m < 0 || (per_craft != 0 && per_craft != 1) || (m > 0 && !at) || (m > 0 && b->n > 0 && !out_y) ||
             reference_body < -1 || reference_body >= b->eph->n_bodies)
             return EPH_ERR_BAD_ARGUMENT;
         if (m == 0 || b->n == 0) return EPH_OK;
         const size_t n = (size_t)b->n;
-        std::shared_lock<std::shared_mutex> table_lock(b->eph->mu, std::defer_lock);
-        if (reference_body >= 0) table_lock.lock();
+        const auto table_lock = table_lock_if(b->eph, reference_body >= 0);
         EPH_HIP(hipSetDevice(b->device));
-        // EPH_TRACE_CRAFT_EVAL=1 prints the call's kernel time and copy time (scripts/craft_eval_timing.py)
-        const char *env = getenv("EPH_TRACE_CRAFT_EVAL");
-        const bool trace = env && atoi(env) != 0;
+        PassTrace trace("EPH_TRACE_CRAFT_EVAL", b);     // the call's kernel time and copy time (scripts/craft_eval_timing.py)
         // passes over epochs: at most 256 MB of results each (one epoch at least), through one device block in slab-column order
         // and the pinned staging buffer in craft order
         const size_t epoch_bytes = n * (6 * sizeof(double) + 1);
@@ -134,28 +121,24 @@ int32_t eph_craft_batch_eval(eph_craft_batch *b, int64_t m, const double *at, in
         if (stage.status()) return stage.status();
         StreamIdleOnExit idle(b->stream);
         hipStream_t s = b->stream;
-        hipError_t he;
+        const BodyTable table = body_table(b->eph);
         if (!per_craft) {
             EPH_HIP(hipMemcpyAsync(d_at.p, at, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
-            if (shared_ref) {
-                hipLaunchKernelGGL(k_craft_eval_reference, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, (long long)m, d_at.p,
-                                   (int)reference_body, b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p, d_ref.p, d_ref_ok.p);
-                if ((he = hipGetLastError()) != hipSuccess) { set_last_error("k_craft_eval_reference", he); return EPH_ERR_HIP; }
-            }
+            if (shared_ref)
+                EPH_LAUNCH("k_craft_eval_reference", k_craft_eval_reference, dim3((unsigned)((m + 63) / 64)), dim3(64), s, (long long)m,
+                           d_at.p, (int)reference_body, table.bodies, table.coeffs, table.ncoef, d_ref.p, d_ref_ok.p);
         }
         const bool dealt = !b->h_slot.empty();          // the slabs' columns are lane positions (craft_sort)
         CraftEvalArgs a{};
-        a.n = b->n; a.max_knots = b->max_knots; a.nknots = b->nknots.p; a.perm = dealt ? b->perm.p : nullptr;
-        a.knot_t = b->knot_t.p; a.knot_y = b->knot_y.p;
+        a.slabs = knot_slabs(b);
         a.per_craft = per_craft; a.body = reference_body;
-        a.table = {b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p};
+        a.table = table;
         a.out_y = d_y.p; a.inside = d_in.p;
         double *stage_y = static_cast<double *>(stage.dev());
         uint8_t *stage_in = reinterpret_cast<uint8_t *>(stage_y + y_count);
-        const double *host_y = static_cast<const double *>(stage.host());
-        const uint8_t *host_in = reinterpret_cast<const uint8_t *>(host_y + y_count);
+        const double *host_y = stage.host_of(stage_y);
+        const uint8_t *host_in = stage.host_of(stage_in);
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        double kernel_ms = 0.0, copy_ms = 0.0;
         for (long long e0 = 0; e0 < m; e0 += per_pass) {
             const long long me = std::min<long long>(per_pass, m - e0);
             if (per_craft) EPH_HIP(hipMemcpyAsync(d_at.p, at + (size_t)e0 * n, sizeof(double) * (size_t)me * n, hipMemcpyHostToDevice, s));
@@ -163,30 +146,22 @@ int32_t eph_craft_batch_eval(eph_craft_batch *b, int64_t m, const double *at, in
             a.at = per_craft ? d_at.p : d_at.p + e0;
             a.ref = shared_ref ? d_ref.p + 6 * e0 : nullptr;
             a.ref_ok = shared_ref ? d_ref_ok.p + e0 : nullptr;
-            if (trace) EPH_HIP(hipEventRecord(b->ev0, s));
-            hipLaunchKernelGGL(k_craft_eval, grid, block, 0, s, a);
-            if ((he = hipGetLastError()) != hipSuccess) { set_last_error("k_craft_eval", he); return EPH_ERR_HIP; }
-            if (trace) EPH_HIP(hipEventRecord(b->ev1, s));
-            hipLaunchKernelGGL(k_craft_eval_rows_out, grid, block, 0, s, me, (long long)n, dealt ? (const int *)b->slot_of.p : nullptr, (const double *)d_y.p,
-                               (const uint8_t *)d_in.p, stage_y, inside ? stage_in : nullptr);
-            if ((he = hipGetLastError()) != hipSuccess) { set_last_error("k_craft_eval_rows_out", he); return EPH_ERR_HIP; }
+            if ((st = trace.kernel_begin())) return st;
+            EPH_LAUNCH("k_craft_eval", k_craft_eval, grid, block, s, a);
+            if ((st = trace.kernel_end())) return st;
+            EPH_LAUNCH("k_craft_eval_rows_out", k_craft_eval_rows_out, grid, block, s, me, (long long)n,
+                       dealt ? (const int *)b->slot_of.p : nullptr, (const double *)d_y.p, (const uint8_t *)d_in.p, stage_y,
+                       inside ? stage_in : nullptr);
             EPH_HIP(hipStreamSynchronize(s));
-            const auto c0 = std::chrono::steady_clock::now();
+            trace.copy_begin();
             std::memcpy(out_y + (size_t)e0 * 6 * n, host_y, sizeof(double) * (size_t)me * 6 * n);
             if (inside) std::memcpy(inside + (size_t)e0 * n, host_in, (size_t)me * n);
-            if (trace) {
-                float ms = 0.0f;
-                EPH_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-                kernel_ms += ms;
-                copy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
-            }
+            if ((st = trace.copy_end())) return st;
         }
         idle.disarm();
-        if (trace)
-            fprintf(stderr, "craft_eval: m %lld n %lld passes %lld kernel_ms %.4f host_copy_ms %.4f\n", (long long)m, (long long)n,
-                    (long long)((m + per_pass - 1) / per_pass), kernel_ms, copy_ms);
+        trace.report("craft_eval", "m", (long long)m, "n", (long long)n, (long long)((m + per_pass - 1) / per_pass));
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 }  // extern "C"

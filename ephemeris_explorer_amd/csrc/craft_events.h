@@ -3,7 +3,6 @@
 // Mirrors ephemeris_explorer/src/dynamics/spacecraft.rs:172-185,208-221,332-339 (paths relative to the reference repository root).
 #pragma once
 #include "craft_batch.h"
-#include "trajectory_eval.h"
 
 namespace eph {
 
@@ -21,6 +20,19 @@ struct EventArgs {
     int max_tr, max_ap;
     const int *slot_of;           // craft -> its column in the knot slabs (null: identity)
 };
+// the batch's event slabs and the live table; a batch without events has null slabs (the restart reads find_soi's table only)
+inline EventArgs event_args(const eph_craft_batch *b) {
+    EventArgs e{};
+    e.n_craft = b->n; e.n_bodies = b->eph->n_bodies;
+    e.table = body_table(b->eph);
+    e.soi = b->soi.p; e.nknots = b->nknots.p; e.knot_t = b->knot_t.p; e.knot_y = b->knot_y.p;
+    e.ev_seg = b->ev_seg.p; e.ntr = b->ntr.p; e.nap = b->nap.p; e.ev_status = b->ev_status.p;
+    e.tr_time = b->tr_time.p; e.tr_body = b->tr_body.p;
+    e.ap_time = b->ap_time.p; e.ap_dist = b->ap_dist.p; e.ap_body = b->ap_body.p; e.ap_kind = b->ap_kind.p;
+    e.max_tr = b->max_tr; e.max_ap = b->max_ap;
+    e.slot_of = b->slot_of.p;
+    return e;
+}
 // find_soi :172-185,208-221: inside iff d2 < r*r; the closest wins, the first on ties
 __device__ inline int soi_at_except(const EventArgs &a, double t, V3 position, int except) {
     int best = -1;

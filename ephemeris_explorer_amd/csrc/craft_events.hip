@@ -214,19 +214,9 @@ __global__ void __launch_bounds__(256) k_craft_reset_events(long long n, int *nt
 
 // craft_run's event step: the search over the steps just taken, queued on `s` behind the sweep
 int craft_events_search(eph_craft_batch *b, hipStream_t s) {
-    EventArgs e{};
-    e.n_craft = b->n; e.n_bodies = b->eph->n_bodies;
-    e.table = {b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p};
-    e.soi = b->soi.p; e.nknots = b->nknots.p; e.knot_t = b->knot_t.p; e.knot_y = b->knot_y.p;
-    e.ev_seg = b->ev_seg.p; e.ntr = b->ntr.p; e.nap = b->nap.p; e.ev_status = b->ev_status.p;
-    e.tr_time = b->tr_time.p; e.tr_body = b->tr_body.p;
-    e.ap_time = b->ap_time.p; e.ap_dist = b->ap_dist.p; e.ap_body = b->ap_body.p; e.ap_kind = b->ap_kind.p;
-    e.max_tr = b->max_tr; e.max_ap = b->max_ap;
-    e.slot_of = b->slot_of.p;
-    if (craft_wave_form(b->n)) hipLaunchKernelGGL(k_craft_events<true>, dim3((unsigned)b->n), dim3(64), 0, s, e);
-    else hipLaunchKernelGGL(k_craft_events<false>, dim3((unsigned)((b->n + 63) / 64)), dim3(64), 0, s, e);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) { set_last_error("k_craft_events", he); return EPH_ERR_HIP; }
+    const EventArgs e = event_args(b);
+    if (craft_wave_form(b->n)) EPH_LAUNCH("k_craft_events", k_craft_events<true>, dim3((unsigned)b->n), dim3(64), s, e);
+    else EPH_LAUNCH("k_craft_events", k_craft_events<false>, dim3((unsigned)((b->n + 63) / 64)), dim3(64), s, e);
     return EPH_OK;
 }
 
@@ -239,7 +229,7 @@ extern "C" {
 
 int32_t eph_craft_batch_enable_events(eph_craft_batch *b, const double *soi_radius, int32_t max_transitions,
                                       int32_t max_apsides) {
-    try {
+    EPH_GUARD_BEGIN
         if (!b || !soi_radius || max_transitions < 1 || max_apsides < 1 || b->events) return EPH_ERR_BAD_ARGUMENT;
         EPH_HIP(hipSetDevice(b->device));
         const size_t nn = (size_t)std::max<long long>(b->n, 1);
@@ -260,7 +250,7 @@ int32_t eph_craft_batch_enable_events(eph_craft_batch *b, const double *soi_radi
         b->max_ap = max_apsides;
         b->events = true;
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 int32_t eph_craft_batch_event_counts(eph_craft_batch *b, int32_t *n_transitions, int32_t *n_apsides,
@@ -300,10 +290,8 @@ int32_t eph_craft_batch_reset_events(eph_craft_batch *b) {
     if (!b || !b->events) return EPH_ERR_BAD_ARGUMENT;
     if (b->n == 0) return EPH_OK;
     EPH_HIP(hipSetDevice(b->device));
-    hipLaunchKernelGGL(k_craft_reset_events, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, b->stream, b->n,
-                       b->ntr.p, b->nap.p, b->ev_status.p, b->tr_time.p, b->tr_body.p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_last_error("k_craft_reset_events", e); return EPH_ERR_HIP; }
+    EPH_LAUNCH("k_craft_reset_events", k_craft_reset_events, dim3((unsigned)((b->n + 255) / 256)), dim3(256), b->stream, b->n,
+               b->ntr.p, b->nap.p, b->ev_status.p, b->tr_time.p, b->tr_body.p);
     EPH_HIP(hipStreamSynchronize(b->stream));
     return EPH_OK;
 }

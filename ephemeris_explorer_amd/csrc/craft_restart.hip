@@ -12,7 +12,6 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <shared_mutex>
 #include <vector>
 
 #include "craft_batch.h"
@@ -154,14 +153,6 @@ __global__ void __launch_bounds__(256) k_craft_restart(const RestartArgs a) {
     a.outcome_out[i] = EPH_OK;
 }
 
-template <typename T>
-static int upload(DevBuf<T> &dst, const T *src, size_t count) {
-    int st = dst.alloc(std::max<size_t>(count, 1));
-    if (st) return st;
-    if (count) EPH_HIP(hipMemcpy(dst.p, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return EPH_OK;
-}
-
 }  // namespace eph
 
 using namespace eph;
@@ -172,30 +163,13 @@ extern "C" {
 int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which, const int64_t *burn_offset, const double *burn_start,
                                 const double *burn_end, const double *burn_acc_xyz, const int32_t *burn_ref, const double *plan_end,
                                 const eph_adaptive_params *params, double *restart_epoch, int32_t *outcome) {
-    try {
+    EPH_GUARD_BEGIN
         if (!b || (params && which)) return EPH_ERR_BAD_ARGUMENT;
         const long long n = b->n;
         auto selected = [&](long long i) { return !which || which[i] != 0; };
         // validate everything before anything changes: the CSR over all craft, the burns of the selected ones (as create)
-        if (burn_offset) {
-            if (burn_offset[0] < 0) return EPH_ERR_BAD_ARGUMENT;
-            for (long long i = 0; i < n; ++i)
-                if (burn_offset[i + 1] < burn_offset[i]) return EPH_ERR_BAD_ARGUMENT;
-            if (burn_offset[n] > burn_offset[0] && (!burn_start || !burn_end || !burn_acc_xyz || !burn_ref)) return EPH_ERR_BAD_ARGUMENT;
-            for (long long i = 0; i < n; ++i)
-                if (selected(i))
-                    for (int64_t q = burn_offset[i]; q < burn_offset[i + 1]; ++q)
-                        if (burn_ref[q] < -1 || burn_ref[q] >= b->eph->n_bodies) return EPH_ERR_BAD_ARGUMENT;
-            if (b->rk.nystrom == 2)
-                for (long long i = 0; i < n; ++i)
-                    if (selected(i))
-                        for (int64_t q = burn_offset[i]; q < burn_offset[i + 1]; ++q)
-                            if (burn_ref[q] >= 0) {
-                                set_last_error_text("Tsitouras75Nystrom (ERKN) needs a velocity-independent right-hand side: "
-                                                    "burns must use the inertial frame");
-                                return EPH_ERR_UNSUPPORTED;
-                            }
-        }
+        int st = burn_csr_check(n, burn_offset, burn_start, burn_end, burn_acc_xyz, burn_ref, b->eph->n_bodies, which, false);
+        if (st || (b->rk.nystrom == 2 && (st = burn_erkn_check(n, burn_offset, burn_ref, which)))) return st;
         const eph_adaptive_params next = params ? *params : b->params;
         // flight_plan.rs:283-285 (the method is the batch's own and cannot change)
         const bool params_changed = next.tol_position != b->params.tol_position || next.tol_velocity != b->params.tol_velocity ||
@@ -222,7 +196,6 @@ int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which, const 
         DevBuf<SegmentDev> d_new_segs, d_segs;
         DevBuf<uint8_t> d_which;
         DevBuf<double> d_plan_end;
-        int st;
         if ((st = upload(d_new_off, new_off.data(), new_off.size())) || (st = upload(d_new_segs, new_segs.data(), new_segs.size())) ||
             (which && (st = upload(d_which, which, (size_t)n))) || (plan_end && (st = upload(d_plan_end, plan_end, (size_t)n))) ||
             (st = d_segs.alloc(std::max<size_t>(b->h_segs.size() + new_segs.size(), 1))))
@@ -240,24 +213,14 @@ int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which, const 
         a.time = b->time.p; a.y = b->y.p; a.next_h = b->next_h.p; a.klast = b->klast.p; a.kfirst = b->kfirst.p; a.last_knot = b->last_knot.p;
         a.n_attempts = b->n_attempts.p; a.rk_i = b->rk_i.p; a.cur_seg = b->cur_seg.p; a.status = b->status.p; a.nknots = b->nknots.p;
         a.events = b->events ? 1 : 0;
-        EventArgs &e = a.ev;
-        e.n_craft = n; e.n_bodies = b->eph->n_bodies;
-        e.table = {b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p};
-        if (b->events) {
-            e.soi = b->soi.p; e.ev_seg = b->ev_seg.p; e.ntr = b->ntr.p; e.nap = b->nap.p; e.ev_status = b->ev_status.p;
-            e.tr_time = b->tr_time.p; e.tr_body = b->tr_body.p; e.ap_time = b->ap_time.p;
-            e.max_tr = b->max_tr; e.max_ap = b->max_ap;
-        }
-        double *stage_epoch = static_cast<double *>(stage.dev());
-        a.epoch_out = stage_epoch;
-        a.outcome_out = reinterpret_cast<int *>(stage_epoch + n);
-        hipLaunchKernelGGL(k_craft_restart, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, a);
-        hipError_t he = hipGetLastError();
-        if (he != hipSuccess) { set_last_error("k_craft_restart", he); return EPH_ERR_HIP; }
+        a.ev = event_args(b);
+        a.epoch_out = static_cast<double *>(stage.dev());
+        a.outcome_out = reinterpret_cast<int *>(a.epoch_out + n);
+        EPH_LAUNCH("k_craft_restart", k_craft_restart, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, a);
         EPH_HIP(hipStreamSynchronize(b->stream));
         idle.disarm();
-        const double *h_epoch = static_cast<const double *>(stage.host());
-        const int *h_outcome = reinterpret_cast<const int *>(h_epoch + n);
+        const double *h_epoch = stage.host_of(a.epoch_out);
+        const int *h_outcome = stage.host_of(a.outcome_out);
         // the batch's CSR: the new timeline for every restarted craft, the old one for everyone else
         std::vector<long long> off((size_t)n + 1, 0);
         std::vector<SegmentDev> segs;
@@ -281,7 +244,7 @@ int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which, const 
         b->h_segs = std::move(segs);
         b->params = next;
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 }  // extern "C"

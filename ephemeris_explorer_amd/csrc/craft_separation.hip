@@ -8,11 +8,9 @@
 // where the six scalars of a result go.
 #include <algorithm>
 #include <cstring>
-#include <shared_mutex>
 #include <vector>
 
 #include "craft_batch.h"
-#include "trajectory_eval.h"
 
 namespace eph {
 
@@ -25,12 +23,7 @@ struct CraftSeparationArgs {
     const long long *lane_req;      // lane -> request (the caller's index); lanes are ordered by the source's slab column
     const int *lane_col;            // lane -> slab column of the source craft
     const int *lane_target_col;     // lane -> slab column of the target craft, -1: the target is the request's body
-    long long n;                    // craft = columns of the slabs
-    int max_knots;
-    const int *nknots;              // [craft]
-    const int *perm;                // slab column -> craft (null: identity)
-    const double *knot_t;           // [k][column]
-    const double *knot_y;           // [k][6][column]
+    KnotSlabs slabs;
     BodyTable table;
     const eph_separation_request *req;   // [request]
     SeparationRow *out;             // [lane]
@@ -43,14 +36,11 @@ __global__ void __launch_bounds__(64) k_craft_separation(const CraftSeparationAr
     const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= a.n_lanes) return;
     const eph_separation_request rq = a.req[a.lane_req[lane]];
-    auto column = [&](long long col) {
-        const long long craft = a.perm ? a.perm[col] : col;
-        return KnotColumn{min(max(a.nknots[craft], 0), a.max_knots), a.n, a.knot_t + col, a.knot_y + col};
-    };
     const long long tcol = a.lane_target_col[lane];
-    const SeparationTrajectory<KnotColumn> src = {a.table, -1, column(a.lane_col[lane])};
+    const SeparationTrajectory<KnotColumn> src = {a.table, -1, a.slabs.column(a.lane_col[lane])};
     // a body target never reads its knots: the source's column stands in
-    const SeparationTrajectory<KnotColumn> tgt = {a.table, tcol >= 0 ? -1 : rq.target_body, column(tcol >= 0 ? tcol : a.lane_col[lane])};
+    const SeparationTrajectory<KnotColumn> tgt = {a.table, tcol >= 0 ? -1 : rq.target_body,
+                                                  a.slabs.column(tcol >= 0 ? tcol : a.lane_col[lane])};
     const Separation r = closest_separation(src, tgt, rq.left, rq.right, rq.precision, rq.max_iterations, rq.metric);
     a.out[lane] = {r.time, r.distance, r.failed_at, r.iterations, r.status, r.found, 0};
 }
@@ -73,7 +63,7 @@ int32_t eph_craft_batch_closest_separation(eph_craft_batch *b, int64_t n_request
                                            const int64_t *craft, const int64_t *target_craft,
                                            uint8_t *out_found, double *out_time, double *out_distance,
                                            int32_t *out_iterations, int32_t *out_status, double *out_failed_at) {
-    try {
+    EPH_GUARD_BEGIN
         if (!b || n_requests < 0 ||
             (n_requests > 0 && (!requests || !out_found || !out_time || !out_distance || !out_iterations || !out_status || !out_failed_at)))
             return EPH_ERR_BAD_ARGUMENT;
@@ -88,54 +78,44 @@ int32_t eph_craft_batch_closest_separation(eph_craft_batch *b, int64_t n_request
             any_body = any_body || r.target_body >= 0;
         }
         if (n_requests == 0 || b->n == 0) return EPH_OK;
-        if (!craft && n_requests > b->n) return EPH_ERR_BAD_ARGUMENT;
-        for (int64_t p = 0; p < n_requests; ++p)
-            if ((craft && (craft[p] < 0 || craft[p] >= b->n)) || (target_craft && target_craft[p] >= b->n)) return EPH_ERR_BAD_ARGUMENT;
         const size_t np = (size_t)n_requests;
+        LaneMap lanes;                                  // lanes in the order of the source's slab column
+        int st;
+        if ((st = lanes.sort(b, np, craft))) return st;
+        for (int64_t p = 0; target_craft && p < n_requests; ++p)
+            if (target_craft[p] >= b->n) return EPH_ERR_BAD_ARGUMENT;
         const bool dealt = !b->h_slot.empty();
-        std::vector<long long> lane_req;
-        std::vector<int> lane_col, lane_target_col(np);
-        lanes_by_column(b, np, craft, lane_req, lane_col);
+        std::vector<int> lane_target_col(np);
         for (size_t l = 0; l < np; ++l) {
-            const int64_t t = target_craft ? target_craft[lane_req[l]] : -1;
+            const int64_t t = target_craft ? target_craft[lanes.item[l]] : -1;
             lane_target_col[l] = t < 0 ? -1 : (dealt ? b->h_slot[(size_t)t] : (int)t);
         }
-        std::shared_lock<std::shared_mutex> table_lock(b->eph->mu, std::defer_lock);
-        if (any_body) table_lock.lock();
+        const auto table_lock = table_lock_if(b->eph, any_body);
         EPH_HIP(hipSetDevice(b->device));
         DevBuf<eph_separation_request> d_req;
-        DevBuf<long long> d_lane_req;
-        DevBuf<int> d_lane_col, d_lane_target_col;
+        DevBuf<int> d_lane_target_col;
         DevBuf<SeparationRow> d_rows;
-        int st;
-        if ((st = d_req.alloc(np)) || (st = d_lane_req.alloc(np)) || (st = d_lane_col.alloc(np)) || (st = d_lane_target_col.alloc(np)) ||
-            (st = d_rows.alloc(np)))
-            return st;
+        if ((st = d_req.alloc(np)) || (st = d_lane_target_col.alloc(np)) || (st = d_rows.alloc(np))) return st;
         PinnedStage stage(np * sizeof(SeparationRow));
         if (stage.status()) return stage.status();
         StreamIdleOnExit idle(b->stream);
         hipStream_t s = b->stream;
-        hipError_t he;
         EPH_HIP(hipMemcpyAsync(d_req.p, requests, sizeof(eph_separation_request) * np, hipMemcpyHostToDevice, s));
-        EPH_HIP(hipMemcpyAsync(d_lane_req.p, lane_req.data(), sizeof(long long) * np, hipMemcpyHostToDevice, s));
-        EPH_HIP(hipMemcpyAsync(d_lane_col.p, lane_col.data(), sizeof(int) * np, hipMemcpyHostToDevice, s));
+        if ((st = lanes.upload(s))) return st;
         EPH_HIP(hipMemcpyAsync(d_lane_target_col.p, lane_target_col.data(), sizeof(int) * np, hipMemcpyHostToDevice, s));
         CraftSeparationArgs a{};
-        a.n_lanes = n_requests; a.lane_req = d_lane_req.p; a.lane_col = d_lane_col.p; a.lane_target_col = d_lane_target_col.p;
-        a.n = b->n; a.max_knots = b->max_knots; a.nknots = b->nknots.p; a.perm = dealt ? b->perm.p : nullptr;
-        a.knot_t = b->knot_t.p; a.knot_y = b->knot_y.p;
-        a.table = {b->eph->bodies.p, b->eph->coeffs.p, b->eph->ncoef.p};
+        a.n_lanes = n_requests; a.lane_req = lanes.d_item.p; a.lane_col = lanes.d_col.p; a.lane_target_col = d_lane_target_col.p;
+        a.slabs = knot_slabs(b);
+        a.table = body_table(b->eph);
         a.req = d_req.p; a.out = d_rows.p;
-        hipLaunchKernelGGL(k_craft_separation, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, s, a);
-        if ((he = hipGetLastError()) != hipSuccess) { set_last_error("k_craft_separation", he); return EPH_ERR_HIP; }
-        hipLaunchKernelGGL(k_craft_separation_rows_out, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, (long long)np,
-                           (const SeparationRow *)d_rows.p, static_cast<SeparationRow *>(stage.dev()));
-        if ((he = hipGetLastError()) != hipSuccess) { set_last_error("k_craft_separation_rows_out", he); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_craft_separation", k_craft_separation, dim3((unsigned)((np + 63) / 64)), dim3(64), s, a);
+        EPH_LAUNCH("k_craft_separation_rows_out", k_craft_separation_rows_out, dim3((unsigned)((np + 255) / 256)), dim3(256), s,
+                   (long long)np, (const SeparationRow *)d_rows.p, static_cast<SeparationRow *>(stage.dev()));
         EPH_HIP(hipStreamSynchronize(s));
         idle.disarm();
         const SeparationRow *rows = static_cast<const SeparationRow *>(stage.host());
         for (size_t l = 0; l < np; ++l) {
-            const size_t p = (size_t)lane_req[l];
+            const size_t p = (size_t)lanes.item[l];
             out_found[p] = (uint8_t)rows[l].found;
             out_time[p] = rows[l].time;
             out_distance[p] = rows[l].distance;
@@ -144,7 +124,7 @@ int32_t eph_craft_batch_closest_separation(eph_craft_batch *b, int64_t n_request
             out_failed_at[p] = rows[l].failed_at;
         }
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 }  // extern "C"

@@ -7,9 +7,6 @@
 
 using namespace eph;
 
-#define EPH_GUARD_BEGIN try {
-#define EPH_GUARD_END } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
-
 #pragma GCC visibility push(default)
 extern "C" {
 

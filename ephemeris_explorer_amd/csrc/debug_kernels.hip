@@ -20,7 +20,7 @@ __global__ void k_debug_div(long long n, const double *__restrict__ a, const dou
 }
 
 int debug_div_device(int64_t n, const double *a, const double *b, double *fast, double *ieee) {
-    try {
+    EPH_GUARD_BEGIN
         if (n < 0 || (n > 0 && (!a || !b || !fast || !ieee))) return EPH_ERR_BAD_ARGUMENT;
         int st = check_device();
         if (st) return st;
@@ -29,14 +29,11 @@ int debug_div_device(int64_t n, const double *a, const double *b, double *fast, 
         if ((st = da.alloc(n)) || (st = db.alloc(n)) || (st = df.alloc(n)) || (st = di.alloc(n))) return st;
         EPH_HIP(hipMemcpy(da.p, a, sizeof(double) * n, hipMemcpyHostToDevice));
         EPH_HIP(hipMemcpy(db.p, b, sizeof(double) * n, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_debug_div, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (long long)n, da.p, db.p,
-                           df.p, di.p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_last_error("k_debug_div", e); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_debug_div", k_debug_div, dim3((unsigned)((n + 255) / 256)), dim3(256), nullptr, (long long)n, da.p, db.p, df.p, di.p);
         EPH_HIP(hipMemcpy(fast, df.p, sizeof(double) * n, hipMemcpyDeviceToHost));
         EPH_HIP(hipMemcpy(ieee, di.p, sizeof(double) * n, hipMemcpyDeviceToHost));
         return EPH_OK;
-    } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 // raw v_rsq_f64(x) and the h = 0.5 / sqrt(x) that the square root's coupled step leaves (the reciprocal's seed is 8 h^3):
@@ -51,7 +48,7 @@ __global__ void k_debug_rsq(long long n, const double *__restrict__ x, double *_
     h1[i] = __builtin_fma(h, r, h);
 }
 int debug_rsq_device(int64_t n, const double *x, double *rsq, double *h) {
-    try {
+    EPH_GUARD_BEGIN
         if (n < 0 || (n > 0 && (!x || !rsq || !h))) return EPH_ERR_BAD_ARGUMENT;
         int st = check_device();
         if (st) return st;
@@ -59,17 +56,15 @@ int debug_rsq_device(int64_t n, const double *x, double *rsq, double *h) {
         DevBuf<double> dx, dy, dh;
         if ((st = dx.alloc(n)) || (st = dy.alloc(n)) || (st = dh.alloc(n))) return st;
         EPH_HIP(hipMemcpy(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_debug_rsq, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (long long)n, dx.p, dy.p, dh.p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_last_error("k_debug_rsq", e); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_debug_rsq", k_debug_rsq, dim3((unsigned)((n + 255) / 256)), dim3(256), nullptr, (long long)n, dx.p, dy.p, dh.p);
         EPH_HIP(hipMemcpy(rsq, dy.p, sizeof(double) * n, hipMemcpyDeviceToHost));
         EPH_HIP(hipMemcpy(h, dh.p, sizeof(double) * n, hipMemcpyDeviceToHost));
         return EPH_OK;
-    } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 int debug_pow_device(int64_t n, const double *x, double y, double *out) {
-    try {
+    EPH_GUARD_BEGIN
         if (n < 0 || (n > 0 && (!x || !out))) return EPH_ERR_BAD_ARGUMENT;
         int st = check_device();
         if (st) return st;
@@ -77,12 +72,10 @@ int debug_pow_device(int64_t n, const double *x, double y, double *out) {
         DevBuf<double> dx, dout;
         if ((st = dx.alloc(n)) || (st = dout.alloc(n))) return st;
         EPH_HIP(hipMemcpy(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_debug_pow, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (long long)n, dx.p, y, dout.p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_last_error("k_debug_pow", e); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_debug_pow", k_debug_pow, dim3((unsigned)((n + 255) / 256)), dim3(256), nullptr, (long long)n, dx.p, y, dout.p);
         EPH_HIP(hipMemcpy(out, dout.p, sizeof(double) * n, hipMemcpyDeviceToHost));
         return EPH_OK;
-    } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 }  // namespace eph

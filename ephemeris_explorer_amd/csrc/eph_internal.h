@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <new>
 #include <string>
 
 #include "../../include/ephemeris_amd.h"
@@ -41,6 +42,30 @@ int check_device();  // EPH_OK or EPH_ERR_NO_DEVICE
             return EPH_ERR_HIP;                                    \
         }                                                          \
     } while (0)
+
+// Launches `kernel` (in parentheses when its template arguments hold a comma) on stream `s`; a launch that fails records `name` as
+// the last error and makes the caller return EPH_ERR_HIP. (force_common.h keeps its own launched(): workloads.py hashes that file.)
+#define EPH_LAUNCH(name, kernel, grid, block, s, ...)                  \
+    do {                                                               \
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, __VA_ARGS__);     \
+        const hipError_t e_ = hipGetLastError();                       \
+        if (e_ != hipSuccess) {                                        \
+            ::eph::set_last_error(name, e_);                           \
+            return EPH_ERR_HIP;                                        \
+        }                                                              \
+    } while (0)
+
+// No exception crosses the extern "C" boundary: an entry point's body sits between these two.
+#define EPH_GUARD_BEGIN try {
+#define EPH_GUARD_END                                                  \
+    }                                                                  \
+    catch (const std::bad_alloc &) {                                   \
+        return EPH_ERR_OUT_OF_MEMORY;                                  \
+    }                                                                  \
+    catch (...) {                                                      \
+        ::eph::set_last_error_text("unexpected C++ exception");        \
+        return EPH_ERR_HIP;                                            \
+    }
 
 // ---- coefficient tables -> the f64 values the reference multiplies with (coeffs.cpp) ------------
 struct SrknCoeffs { int stages = 0; bool fsal = false; double A[32], B[32]; };

@@ -1,12 +1,12 @@
 // ephemeris_table.h -- struct eph_ephemeris, the LIVE device table of the massive bodies' piecewise-polynomial ephemeris, for the units
-// that bind to one: ephemeris_table.hip (the only writer), craft.hip, craft_events.hip, evaluators.hip.
+// that bind to one: ephemeris_table.hip (the only writer), the craft_*.hip units, evaluators.hip.
 #pragma once
 #include <cstdint>
 #include <shared_mutex>
 #include <vector>
 
-#include "craft_device.h"
 #include "host.h"
+#include "trajectory_eval.h"
 
 // The device-resident Vec<UniformSpline> of the massive bodies. LIVE, like the reference's: GravitationalBody.trajectory is
 // Trajectory(Arc<RwLock<PredictionTrajectory>>) (ephemeris_explorer/src/dynamics/spacecraft.rs:52-74, dynamics/mod.rs:84-85), merged
@@ -33,3 +33,11 @@ struct eph_ephemeris {
     std::vector<long long> base, cap;          // body b's region of rows
     std::vector<char> grows_front;             // body b has been prepended to: keep headroom in front as well
 };
+
+namespace eph {
+inline BodyTable body_table(const eph_ephemeris *e) { return {e->bodies.p, e->coeffs.p, e->ncoef.p}; }   // what a kernel reads, under `mu`
+// the read lock of a call that reads the table only when one of its requests names a body: held if `reads_a_body`
+inline std::shared_lock<std::shared_mutex> table_lock_if(const eph_ephemeris *e, bool reads_a_body) {
+    return reads_a_body ? std::shared_lock<std::shared_mutex>(e->mu) : std::shared_lock<std::shared_mutex>();
+}
+}  // namespace eph

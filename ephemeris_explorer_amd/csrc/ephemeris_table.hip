@@ -61,8 +61,7 @@ static int eph_upload_bodies(eph_ephemeris *e) {
     }
     if (!nb) return EPH_OK;
     EPH_HIP(hipMemcpy(e->bodies.p, e->host_bodies.data(), sizeof(BodyEntry) * (size_t)nb, hipMemcpyHostToDevice));
-    k_body_reciprocals<<<(nb + 63) / 64, 64>>>(nb, e->bodies.p);
-    EPH_HIP(hipGetLastError());
+    EPH_LAUNCH("k_body_reciprocals", k_body_reciprocals, dim3((nb + 63) / 64), dim3(64), nullptr, nb, e->bodies.p);
     EPH_HIP(hipStreamSynchronize(nullptr));
     return EPH_OK;
 }
@@ -148,7 +147,7 @@ static void eph_splice(eph_ephemeris *e, size_t b, const UniformSpline &y, int d
 extern "C" {
 
 int32_t eph_ephemeris_create(const eph_solution *s, const double *mu, eph_ephemeris **out) {
-    try {
+    EPH_GUARD_BEGIN
         if (!s || !mu || !out) return EPH_ERR_BAD_ARGUMENT;
         int st = check_device();
         if (st) return st;
@@ -164,14 +163,14 @@ int32_t eph_ephemeris_create(const eph_solution *s, const double *mu, eph_epheme
         if ((st = eph_rebuild(e.get()))) return st;
         *out = e.release();
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 void eph_ephemeris_destroy(eph_ephemeris *e) { delete e; }
 
 // UniformSpline::append (direction > 0) / prepend (< 0) for every body  trajectory.rs:515-534; the asserts become EPH_ERR_BAD_ARGUMENT
 // with the table untouched
 int32_t eph_ephemeris_append(eph_ephemeris *e, const eph_solution *tail, int32_t direction) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || !tail || direction == 0 || tail->s.splines.size() != e->splines.size()) return EPH_ERR_BAD_ARGUMENT;
         std::unique_lock<std::shared_mutex> lock(e->mu);
         const size_t nb = e->splines.size();
@@ -185,11 +184,11 @@ int32_t eph_ephemeris_append(eph_ephemeris *e, const eph_solution *tail, int32_t
         for (size_t b = 0; b < nb; ++b) eph_splice(e, b, tail->s.splines[b], direction, front, back);
         e->revision += 1;
         return eph_follow_or_rebuild(e, front, back, none);
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 // UniformSpline::clear_before (after = 0, trajectory.rs:536-542) / clear_after (after != 0, :544-549) on body's spline or on all (body < 0)
 int32_t eph_ephemeris_clear(eph_ephemeris *e, int32_t body, double at, int32_t after) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || body >= e->n_bodies) return EPH_ERR_BAD_ARGUMENT;
         std::unique_lock<std::shared_mutex> lock(e->mu);
         EPH_HIP(hipSetDevice(e->device));
@@ -204,12 +203,12 @@ int32_t eph_ephemeris_clear(eph_ephemeris *e, int32_t body, double at, int32_t a
         }
         e->revision += 1;
         return eph_follow_or_rebuild(e, none, none, dropped);
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 // CelestialTrajectory::merge  ephemeris_explorer/src/dynamics/celestial.rs:198-204 (Forward: clear_after(propagated.start()) then
 // append) and :220-226 (Backward: clear_before(propagated.end()) then prepend), body by body
 int32_t eph_ephemeris_merge(eph_ephemeris *e, const eph_solution *propagated, int32_t direction) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || !propagated || direction == 0 || propagated->s.splines.size() != e->splines.size()) return EPH_ERR_BAD_ARGUMENT;
         std::unique_lock<std::shared_mutex> lock(e->mu);
         const size_t nb = e->splines.size();
@@ -248,7 +247,7 @@ int32_t eph_ephemeris_merge(eph_ephemeris *e, const eph_solution *propagated, in
         }
         e->revision += 1;
         return eph_follow_or_rebuild(e, front, back, dropped);
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 int32_t eph_ephemeris_info(const eph_ephemeris *e, int32_t body, double *start, double *interval, int64_t *npoly, uint64_t *revision) {
     if (!e || body >= e->n_bodies) return EPH_ERR_BAD_ARGUMENT;
@@ -284,7 +283,7 @@ constexpr uint64_t kEphImageMagic = 0x3130485045485045ull;     // "EPHEPH01"
 struct EphImageBody { double start, interval, mu; int64_t npoly; };
 }
 int32_t eph_ephemeris_export(const eph_ephemeris *e, void *buf, uint64_t capacity, uint64_t *bytes) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || !bytes) return EPH_ERR_BAD_ARGUMENT;
         std::shared_lock<std::shared_mutex> lock(e->mu);
         uint64_t polys = 0;
@@ -311,10 +310,10 @@ int32_t eph_ephemeris_export(const eph_ephemeris *e, void *buf, uint64_t capacit
                 std::memcpy(w, &nc64, sizeof(nc64)); w += sizeof(nc64);
             }
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 int32_t eph_ephemeris_import(const void *buf, uint64_t bytes, eph_ephemeris **out) {
-    try {
+    EPH_GUARD_BEGIN
         if (!buf || !out || bytes < sizeof(EphImageHeader)) return EPH_ERR_BAD_ARGUMENT;
         *out = nullptr;
         const char *r = static_cast<const char *>(buf);
@@ -347,7 +346,7 @@ int32_t eph_ephemeris_import(const void *buf, uint64_t bytes, eph_ephemeris **ou
                 sol.s.splines[b].polynomials.push_back(p);
             }
         return eph_ephemeris_create(&sol, mu.data(), out);
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 }  // extern "C"

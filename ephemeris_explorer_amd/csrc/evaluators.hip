@@ -9,7 +9,6 @@
 #include <vector>
 
 #include "ephemeris_table.h"
-#include "trajectory_eval.h"
 
 namespace eph {
 
@@ -146,7 +145,7 @@ extern "C" {
 
 int32_t eph_ephemeris_interpolation_errors(const eph_ephemeris *e, eph_nbody *h, int64_t n_steps, double *max_error_m,
                                            int64_t *steps_done) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || !h || !h->p || n_steps < 0 || !max_error_m) return EPH_ERR_BAD_ARGUMENT;
         NBodyIntegration *g = h->p;
         const int n = g->n();
@@ -163,11 +162,12 @@ int32_t eph_ephemeris_interpolation_errors(const eph_ephemeris *e, eph_nbody *h,
         EPH_HIP(hipStreamSynchronize(g->stream()));
         int64_t done = 0;
         int status = EPH_OK;
+        const BodyTable table = body_table(e);
         for (; done < n_steps; ++done) {                       // while integrator.advance(&mut nbody).is_ok()
             if ((status = g->advance(1))) break;
             if (n > 0)
                 hipLaunchKernelGGL(k_interp_error, dim3((n + 255) / 256), dim3(256), 0, g->stream(), n, g->npad(),
-                                   g->positions_soa(), g->time(), e->bodies.p, e->coeffs.p, e->ncoef.p, err.p, failed.p);
+                                   g->positions_soa(), g->time(), table.bodies, table.coeffs, table.ncoef, err.p, failed.p);
         }
         hipError_t he = hipGetLastError();
         if (he != hipSuccess) { set_last_error("k_interp_error", he); return EPH_ERR_HIP; }
@@ -179,45 +179,37 @@ int32_t eph_ephemeris_interpolation_errors(const eph_ephemeris *e, eph_nbody *h,
         if (status < 0) return status;
         if (f) return EPH_EVAL_FAILED;                         // an epoch outside a spline: the reference would panic
         return EPH_OK;                                         // a StepError (bound reached) just ends the scan
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 int32_t eph_hermite_eval(int64_t nknots, const double *t, const double *pos, const double *vel, int64_t m,
                          const double *at, double *op, double *ov, uint8_t *inside) {
-    try {
+    EPH_GUARD_BEGIN
         if (nknots < 0 || m < 0 || (m > 0 && (!at || !op || !inside)) || (nknots > 0 && (!t || !pos || !vel)))
             return EPH_ERR_BAD_ARGUMENT;
         int st = check_device();
         if (st) return st;
         if (m == 0) return EPH_OK;
-        const size_t nk = (size_t)std::max<int64_t>(nknots, 1);
+        const size_t nk = (size_t)nknots;
         DevBuf<double> dt, dp, dv, dat, dop, dov;
         DevBuf<uint8_t> din;
-        if ((st = dt.alloc(nk)) || (st = dp.alloc(3 * nk)) || (st = dv.alloc(3 * nk)) || (st = dat.alloc(m)) ||
+        if ((st = upload(dt, t, nk)) || (st = upload(dp, pos, 3 * nk)) || (st = upload(dv, vel, 3 * nk)) || (st = upload(dat, at, (size_t)m)) ||
             (st = dop.alloc(3 * (size_t)m)) || (st = dov.alloc(3 * (size_t)m)) || (st = din.alloc(m)))
             return st;
-        if (nknots) {
-            EPH_HIP(hipMemcpy(dt.p, t, sizeof(double) * nknots, hipMemcpyHostToDevice));
-            EPH_HIP(hipMemcpy(dp.p, pos, sizeof(double) * 3 * nknots, hipMemcpyHostToDevice));
-            EPH_HIP(hipMemcpy(dv.p, vel, sizeof(double) * 3 * nknots, hipMemcpyHostToDevice));
-        }
-        EPH_HIP(hipMemcpy(dat.p, at, sizeof(double) * m, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_hermite_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, (long long)nknots,
-                           dt.p, dp.p, dv.p, (long long)m, dat.p, dop.p, ov ? dov.p : nullptr, din.p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_last_error("k_hermite_eval", e); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_hermite_eval", k_hermite_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), nullptr, (long long)nknots,
+                   dt.p, dp.p, dv.p, (long long)m, dat.p, dop.p, ov ? dov.p : nullptr, din.p);
         EPH_HIP(hipMemcpy(op, dop.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost));
         if (ov) EPH_HIP(hipMemcpy(ov, dov.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost));
         EPH_HIP(hipMemcpy(inside, din.p, m, hipMemcpyDeviceToHost));
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 int32_t eph_plot_points(const eph_ephemeris *e, const eph_plot_view *view, int64_t n_plots, const eph_plot_request *requests,
                         int64_t n_knots, const double *knot_t, const double *knot_pos, const double *knot_vel,
                         int64_t capacity, double *out_t, float *out_xyz, int64_t *out_count, int32_t *out_status,
                         double *out_failed_at) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || !view || n_plots < 0 || n_knots < 0 || capacity < 0 || (n_plots > 0 && (!requests || !out_count || !out_status || !out_failed_at)) ||
             (n_knots > 0 && (!knot_t || !knot_pos || !knot_vel)) || (n_plots > 0 && capacity > 0 && (!out_t || !out_xyz)))
             return EPH_ERR_BAD_ARGUMENT;
@@ -234,32 +226,24 @@ int32_t eph_plot_points(const eph_ephemeris *e, const eph_plot_view *view, int64
         if (n_plots == 0) return EPH_OK;
         std::shared_lock<std::shared_mutex> table_lock(e->mu);
         EPH_HIP(hipSetDevice(e->device));
-        const size_t nk = (size_t)std::max<int64_t>(n_knots, 1), np = (size_t)n_plots, cap = (size_t)std::max<int64_t>(capacity, 1);
+        const size_t nk = (size_t)n_knots, np = (size_t)n_plots, cap = (size_t)std::max<int64_t>(capacity, 1);
         DevBuf<eph_plot_request> d_req;
         DevBuf<double> d_kt, d_kp, d_kv, d_t, d_fail;
         DevBuf<float> d_xyz;
         DevBuf<long long> d_cnt;
         DevBuf<int> d_st;
-        if ((st = d_req.alloc(np)) || (st = d_kt.alloc(nk)) || (st = d_kp.alloc(3 * nk)) || (st = d_kv.alloc(3 * nk)) ||
-            (st = d_t.alloc(np * cap)) || (st = d_xyz.alloc(3 * np * cap)) || (st = d_cnt.alloc(np)) || (st = d_st.alloc(np)) ||
-            (st = d_fail.alloc(np)))
+        if ((st = upload(d_req, requests, np)) || (st = upload(d_kt, knot_t, nk)) || (st = upload(d_kp, knot_pos, 3 * nk)) ||
+            (st = upload(d_kv, knot_vel, 3 * nk)) || (st = d_t.alloc(np * cap)) || (st = d_xyz.alloc(3 * np * cap)) ||
+            (st = d_cnt.alloc(np)) || (st = d_st.alloc(np)) || (st = d_fail.alloc(np)))
             return st;
-        EPH_HIP(hipMemcpy(d_req.p, requests, sizeof(eph_plot_request) * np, hipMemcpyHostToDevice));
-        if (n_knots) {
-            EPH_HIP(hipMemcpy(d_kt.p, knot_t, sizeof(double) * n_knots, hipMemcpyHostToDevice));
-            EPH_HIP(hipMemcpy(d_kp.p, knot_pos, sizeof(double) * 3 * n_knots, hipMemcpyHostToDevice));
-            EPH_HIP(hipMemcpy(d_kv.p, knot_vel, sizeof(double) * 3 * n_knots, hipMemcpyHostToDevice));
-        }
         PlotArgs a{};
         a.n_plots = n_plots; a.n_bodies = e->n_bodies;
-        a.table = {e->bodies.p, e->coeffs.p, e->ncoef.p};
+        a.table = body_table(e);
         a.req = d_req.p; a.view = *view;
         a.knot_t = d_kt.p; a.knot_pos = d_kp.p; a.knot_vel = d_kv.p;
         a.capacity = capacity; a.out_t = d_t.p; a.out_xyz = d_xyz.p; a.out_count = d_cnt.p; a.out_status = d_st.p;
         a.out_failed_at = d_fail.p;
-        hipLaunchKernelGGL(k_plot_points, dim3((unsigned)((n_plots + 63) / 64)), dim3(64), 0, nullptr, a);
-        hipError_t he = hipGetLastError();
-        if (he != hipSuccess) { set_last_error("k_plot_points", he); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_plot_points", k_plot_points, dim3((unsigned)((n_plots + 63) / 64)), dim3(64), nullptr, a);
         static_assert(sizeof(long long) == sizeof(int64_t), "count type");
         EPH_HIP(hipMemcpy(out_count, d_cnt.p, sizeof(int64_t) * np, hipMemcpyDeviceToHost));
         EPH_HIP(hipMemcpy(out_status, d_st.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
@@ -269,14 +253,14 @@ int32_t eph_plot_points(const eph_ephemeris *e, const eph_plot_view *view, int64
             EPH_HIP(hipMemcpy(out_xyz, d_xyz.p, sizeof(float) * 3 * np * cap, hipMemcpyDeviceToHost));
         }
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 int32_t eph_closest_separation(const eph_ephemeris *e, int64_t n_requests, const eph_separation_request *requests,
                                int64_t n_knots, const double *knot_t, const double *knot_pos, const double *knot_vel,
                                uint8_t *out_found, double *out_time, double *out_distance, int32_t *out_iterations,
                                int32_t *out_status, double *out_failed_at) {
-    try {
+    EPH_GUARD_BEGIN
         if (!e || n_requests < 0 || n_knots < 0 ||
             (n_requests > 0 && (!requests || !out_found || !out_time || !out_distance || !out_iterations || !out_status || !out_failed_at)) ||
             (n_knots > 0 && (!knot_t || !knot_pos || !knot_vel)))
@@ -296,31 +280,23 @@ int32_t eph_closest_separation(const eph_ephemeris *e, int64_t n_requests, const
         if (n_requests == 0) return EPH_OK;
         std::shared_lock<std::shared_mutex> table_lock(e->mu);
         EPH_HIP(hipSetDevice(e->device));
-        const size_t nk = (size_t)std::max<int64_t>(n_knots, 1), np = (size_t)n_requests;
+        const size_t nk = (size_t)n_knots, np = (size_t)n_requests;
         DevBuf<eph_separation_request> d_req;
         DevBuf<double> d_kt, d_kp, d_kv, d_time, d_dist, d_fail;
         DevBuf<uint8_t> d_found;
         DevBuf<int> d_it, d_st;
-        if ((st = d_req.alloc(np)) || (st = d_kt.alloc(nk)) || (st = d_kp.alloc(3 * nk)) || (st = d_kv.alloc(3 * nk)) ||
-            (st = d_found.alloc(np)) || (st = d_time.alloc(np)) || (st = d_dist.alloc(np)) || (st = d_it.alloc(np)) ||
+        if ((st = upload(d_req, requests, np)) || (st = upload(d_kt, knot_t, nk)) || (st = upload(d_kp, knot_pos, 3 * nk)) ||
+            (st = upload(d_kv, knot_vel, 3 * nk)) || (st = d_found.alloc(np)) || (st = d_time.alloc(np)) || (st = d_dist.alloc(np)) || (st = d_it.alloc(np)) ||
             (st = d_st.alloc(np)) || (st = d_fail.alloc(np)))
             return st;
-        EPH_HIP(hipMemcpy(d_req.p, requests, sizeof(eph_separation_request) * np, hipMemcpyHostToDevice));
-        if (n_knots) {
-            EPH_HIP(hipMemcpy(d_kt.p, knot_t, sizeof(double) * n_knots, hipMemcpyHostToDevice));
-            EPH_HIP(hipMemcpy(d_kp.p, knot_pos, sizeof(double) * 3 * n_knots, hipMemcpyHostToDevice));
-            EPH_HIP(hipMemcpy(d_kv.p, knot_vel, sizeof(double) * 3 * n_knots, hipMemcpyHostToDevice));
-        }
         SeparationArgs a{};
         a.n_requests = n_requests;
-        a.table = {e->bodies.p, e->coeffs.p, e->ncoef.p};
+        a.table = body_table(e);
         a.req = d_req.p;
         a.knot_t = d_kt.p; a.knot_pos = d_kp.p; a.knot_vel = d_kv.p;
         a.out_found = d_found.p; a.out_time = d_time.p; a.out_distance = d_dist.p; a.out_iterations = d_it.p; a.out_status = d_st.p;
         a.out_failed_at = d_fail.p;
-        hipLaunchKernelGGL(k_closest_separation, dim3((unsigned)((n_requests + 63) / 64)), dim3(64), 0, nullptr, a);
-        hipError_t he = hipGetLastError();
-        if (he != hipSuccess) { set_last_error("k_closest_separation", he); return EPH_ERR_HIP; }
+        EPH_LAUNCH("k_closest_separation", k_closest_separation, dim3((unsigned)((n_requests + 63) / 64)), dim3(64), nullptr, a);
         EPH_HIP(hipMemcpy(out_found, d_found.p, np, hipMemcpyDeviceToHost));
         EPH_HIP(hipMemcpy(out_time, d_time.p, sizeof(double) * np, hipMemcpyDeviceToHost));
         EPH_HIP(hipMemcpy(out_distance, d_dist.p, sizeof(double) * np, hipMemcpyDeviceToHost));
@@ -328,7 +304,7 @@ int32_t eph_closest_separation(const eph_ephemeris *e, int64_t n_requests, const
         EPH_HIP(hipMemcpy(out_status, d_st.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
         EPH_HIP(hipMemcpy(out_failed_at, d_fail.p, sizeof(double) * np, hipMemcpyDeviceToHost));
         return EPH_OK;
-    } catch (const std::bad_alloc &) { return EPH_ERR_OUT_OF_MEMORY; } catch (...) { return EPH_ERR_HIP; }
+    EPH_GUARD_END
 }
 
 }  // extern "C"

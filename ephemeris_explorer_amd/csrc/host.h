@@ -39,6 +39,10 @@ public:
     int status() const { return status_; }
     void *host() const { return host_; }
     void *dev() const { return dev_; }
+    template <typename T>                              // where the host reads what a kernel stored through device address `d`
+    const T *host_of(const T *d) const {
+        return reinterpret_cast<const T *>(static_cast<const char *>(host_) + (reinterpret_cast<const char *>(d) - static_cast<const char *>(dev_)));
+    }
 
 private:
     void *host_ = nullptr, *dev_ = nullptr;
@@ -84,6 +88,14 @@ struct DevBuf {   // owning device allocation
     }
     int reserve(size_t n) { return n <= count ? EPH_OK : alloc(n + n / 2); }   // grow-only scratch; contents are lost
 };
+// a fresh allocation holding src[0, count) (DevBuf::alloc makes an empty one one element long): a blocking copy on the null stream
+template <typename T>
+int upload(DevBuf<T> &dst, const T *src, size_t count) {
+    const int st = dst.alloc(count);
+    if (st) return st;
+    if (count) EPH_HIP(hipMemcpy(dst.p, src, sizeof(T) * count, hipMemcpyHostToDevice));
+    return EPH_OK;
+}
 
 // Direct-write transport of the exchange step (peer.hip): every rank owns a mailbox that its peers map through
 // hipIpc and write into; no collective library involved.

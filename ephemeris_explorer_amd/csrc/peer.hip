@@ -234,8 +234,7 @@ int PeerTransport::all_gather_inplace(void *buf, size_t slice_bytes, hipStream_t
         a.len = std::min(slot_, slice_bytes - off);
         a.epoch = ++epoch_;
         a.parts = (int)std::min<size_t>(16, (a.len + 32767) / 32768);
-        hipLaunchKernelGGL(k_peer_exchange, dim3((unsigned)((world_ - 1) * a.parts)), dim3(kPeerThreads), 0, s, a);
-        EPH_HIP(hipGetLastError());
+        EPH_LAUNCH("k_peer_exchange", k_peer_exchange, dim3((unsigned)((world_ - 1) * a.parts)), dim3(kPeerThreads), s, a);
     }
     EPH_HIP(hipEventRecord(order_, s));
     last_stream_ = s;

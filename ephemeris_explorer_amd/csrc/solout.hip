@@ -212,66 +212,66 @@ __global__ void __launch_bounds__(256) k_spline_eval(long long m, const double *
 int launch_lm_predict(hipStream_t s, const LmArgs &a) {
     if (a.n <= 0 || a.hi <= a.lo) return EPH_OK;
     const dim3 grid((3 * (a.hi - a.lo) + 255) / 256), block(256);
-    if (a.L == 12) hipLaunchKernelGGL(k_lm_predict<12>, grid, block, 0, s, a);
-    else if (a.L == 13) hipLaunchKernelGGL(k_lm_predict<13>, grid, block, 0, s, a);
+    if (a.L == 12) EPH_LAUNCH("k_lm_predict", k_lm_predict<12>, grid, block, s, a);
+    else if (a.L == 13) EPH_LAUNCH("k_lm_predict", k_lm_predict<13>, grid, block, s, a);
     else return EPH_ERR_UNSUPPORTED;
-    return launched("k_lm_predict");
+    return EPH_OK;
 }
 int launch_pack(hipStream_t s, int n, int npad, const double *Yslot, const double *mu, Body4 *pos) {
     if (n <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_pack, dim3((n + 255) / 256), dim3(256), 0, s, n, npad, Yslot, mu, pos);
-    return launched("k_pack");
+    EPH_LAUNCH("k_pack", k_pack, dim3((n + 255) / 256), dim3(256), s, n, npad, Yslot, mu, pos);
+    return EPH_OK;
 }
 int launch_copy3(hipStream_t s, int n, int npad, const double *src, double *dst) {
     if (n <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_copy3, dim3((3 * n + 255) / 256), dim3(256), 0, s, n, npad, src, dst);
-    return launched("k_copy3");
+    EPH_LAUNCH("k_copy3", k_copy3, dim3((3 * n + 255) / 256), dim3(256), s, n, npad, src, dst);
+    return EPH_OK;
 }
 int launch_kick_drift(hipStream_t s, int n, int npad, const double *a, double *v, double *y, double hb, double ha,
                       const double *mu, Body4 *pos_out) {
     if (n <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_kick_drift, dim3((n + 255) / 256), dim3(256), 0, s, n, npad, a, v, y, hb, ha, mu, pos_out);
-    return launched("k_kick_drift");
+    EPH_LAUNCH("k_kick_drift", k_kick_drift, dim3((n + 255) / 256), dim3(256), s, n, npad, a, v, y, hb, ha, mu, pos_out);
+    return EPH_OK;
 }
 int launch_aos_to_soa(hipStream_t s, int n, int npad, const double *aos, double *soa) {
     if (n <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_aos_to_soa, dim3((3 * n + 255) / 256), dim3(256), 0, s, n, npad, aos, soa);
-    return launched("k_aos_to_soa");
+    EPH_LAUNCH("k_aos_to_soa", k_aos_to_soa, dim3((3 * n + 255) / 256), dim3(256), s, n, npad, aos, soa);
+    return EPH_OK;
 }
 int launch_soa_to_aos(hipStream_t s, int n, int npad, const double *soa, double *aos) {
     if (n <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_soa_to_aos, dim3((3 * n + 255) / 256), dim3(256), 0, s, n, npad, soa, aos);
-    return launched("k_soa_to_aos");
+    EPH_LAUNCH("k_soa_to_aos", k_soa_to_aos, dim3((3 * n + 255) / 256), dim3(256), s, n, npad, soa, aos);
+    return EPH_OK;
 }
 int launch_sample(hipStream_t s, int n, int npad, const double *Yslot, const SampleArgs &sa, uint32_t step) {
     if (n <= 0 || !sa.period) return EPH_OK;
-    hipLaunchKernelGGL(k_sample, dim3((3 * n + 255) / 256), dim3(256), 0, s, n, npad, Yslot, sa, step);
-    return launched("k_sample");
+    EPH_LAUNCH("k_sample", k_sample, dim3((3 * n + 255) / 256), dim3(256), s, n, npad, Yslot, sa, step);
+    return EPH_OK;
 }
 int launch_carry(hipStream_t s, int n, const uint64_t *region, const uint32_t *src, const uint32_t *cnt, double *log) {
     if (n <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_carry, dim3((n + 255) / 256), dim3(256), 0, s, n, region, src, cnt, log);
-    return launched("k_carry");
+    EPH_LAUNCH("k_carry", k_carry, dim3((n + 255) / 256), dim3(256), s, n, region, src, cnt, log);
+    return EPH_OK;
 }
 int launch_pack_records(hipStream_t s, int64_t nwin, const double *co, const int32_t *nc, double *rec) {
     if (nwin <= 0) return EPH_OK;
     const long long tot = nwin * (kDiv * 3 + 1);
-    hipLaunchKernelGGL(k_pack_records, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, (long long)nwin, co, nc, rec);
-    return launched("k_pack_records");
+    EPH_LAUNCH("k_pack_records", k_pack_records, dim3((unsigned)((tot + 255) / 256)), dim3(256), s, (long long)nwin, co, nc, rec);
+    return EPH_OK;
 }
 int launch_lsq_fit(hipStream_t s, int64_t nwin, const uint64_t *first_sample, const uint8_t *degree, int backward,
                    const double *log, double *coeffs, int32_t *ncoef) {
     if (nwin <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_lsq_fit, dim3((unsigned)((nwin + 63) / 64)), dim3(64), 0, s, (long long)nwin, first_sample,
-                       degree, backward, log, coeffs, ncoef);
-    return launched("k_lsq_fit");
+    EPH_LAUNCH("k_lsq_fit", k_lsq_fit, dim3((unsigned)((nwin + 63) / 64)), dim3(64), s, (long long)nwin, first_sample,
+               degree, backward, log, coeffs, ncoef);
+    return EPH_OK;
 }
 int launch_spline_eval(hipStream_t s, int64_t m, const double *at, double start, double interval, int64_t npoly,
                        const double *coeffs, const int32_t *ncoef, double *pos, double *vel, uint8_t *inside) {
     if (m <= 0) return EPH_OK;
-    hipLaunchKernelGGL(k_spline_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (long long)m, at, start,
-                       interval, (long long)npoly, coeffs, ncoef, pos, vel, inside);
-    return launched("k_spline_eval");
+    EPH_LAUNCH("k_spline_eval", k_spline_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), s, (long long)m, at, start,
+               interval, (long long)npoly, coeffs, ncoef, pos, vel, inside);
+    return EPH_OK;
 }
 
 }  // namespace eph
