@@ -11,19 +11,12 @@ There is NO CPU fallback: if the shared library is missing or no HIP device is v
 raises. (The CPU oracle lives in oracle/ and is test infrastructure only; this package never imports it.)
 """
 import ctypes as C
-from pathlib import Path
 
 import numpy as np
 
 from . import systems  # noqa: F401  (state.json / ephemeris.json / ships readers)
-
-_HERE = Path(__file__).resolve().parent
-import os as _os
-
-# (the evaluation order of the point-mass term is a run-time choice now: set_pair_variant(k) / EPH_PAIR_VARIANT=k)
-LIB_PATH = _HERE / "libephemeris_amd.so"
-if _os.environ.get("EPH_AMD_LIBRARY"):            # tuning builds (scripts/): another build of the same sources
-    LIB_PATH = Path(_os.environ["EPH_AMD_LIBRARY"])
+from ._abi import (ABI_SYMBOLS, EXCHANGE_FN, LIB_PATH, AdaptiveParams, PlotRequest, PlotView,  # noqa: F401  (the package's names)
+                   SeparationRequest, _dp, _fp, _i32p, _i64p, _lib, _u8p, _u32p, hip_runtime)
 
 FORWARD, BACKWARD = 1, -1
 PATH_FAST = 4
@@ -33,31 +26,7 @@ PATH_F32_PAIRS = 6   # OPT-IN mixed precision: f32 pair arithmetic, f64 accumula
 OK = 0
 STEP_SIZE_UNDERFLOW, MAX_ITERATIONS_REACHED, BOUND_REACHED, EVAL_FAILED, SOLOUT_EXIT = 1, 2, 3, 4, 5
 ERR_BAD_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_OUT_OF_MEMORY = -1, -2, -3, -4, -5
-
-# every symbol include/ephemeris_amd.h declares (tests check the .so exports exactly these)
-EXCHANGE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p)
-
-ABI_SYMBOLS = [
-    "eph_abi_version", "eph_pair_variant", "eph_set_pair_variant", "eph_release_cached_memory", "eph_status_string", "eph_last_error", "eph_device_count", "eph_set_device",
-    "eph_device_name", "eph_srkn_coeffs", "eph_elm2_coeffs", "eph_accel_eval",
-    "eph_nbody_create", "eph_nbody_advance", "eph_nbody_get_state", "eph_nbody_get_acc", "eph_nbody_set_bound",
-    "eph_nbody_clone", "eph_nbody_destroy", "eph_nbody_eval_count", "eph_nbody_set_path", "eph_nbody_kernel_time",
-    "eph_nbody_enable_timing", "eph_nbody_sync", "eph_rccl_unique_id", "eph_nbody_shard", "eph_nbody_shard_info",
-    "eph_prop_shard", "eph_peer_create", "eph_peer_create_ex", "eph_peer_memory_form", "eph_peer_handle", "eph_peer_connect", "eph_peer_destroy", "eph_nbody_shard_peer",
-    "eph_prop_shard_peer", "eph_nbody_advance_many", "eph_prop_step_n_many",
-    "eph_prop_create", "eph_prop_step", "eph_prop_step_n", "eph_prop_step_to", "eph_prop_time",
-    "eph_prop_has_reached", "eph_prop_integrator_time", "eph_prop_get_state", "eph_prop_take_solution",
-    "eph_prop_propagate", "eph_prop_clone", "eph_prop_destroy", "eph_prop_integrator",
-    "eph_solution_bodies", "eph_solution_info", "eph_solution_coeffs", "eph_solution_eval", "eph_solution_append", "eph_solution_create", "eph_solution_clear", "eph_solution_between",
-    "eph_solution_destroy", "eph_least_squares_fit",
-    "eph_ephemeris_create", "eph_ephemeris_destroy", "eph_ephemeris_append", "eph_ephemeris_merge", "eph_ephemeris_clear", "eph_ephemeris_info",
-    "eph_ephemeris_is_valid_at", "eph_ephemeris_export", "eph_ephemeris_import", "eph_craft_batch_retry_failed",
-    "eph_ephemeris_interpolation_errors", "eph_craft_batch_create", "eph_craft_batch_set_body_order", "eph_craft_batch_propagate", "eph_craft_batch_step_n",
-    "eph_craft_batch_status", "eph_craft_batch_state", "eph_craft_batch_summary", "eph_craft_batch_knots", "eph_craft_batch_kernel_time",
-    "eph_craft_batch_clone", "eph_craft_batch_knot_slabs", "eph_craft_batch_eval", "eph_craft_batch_plot_points", "eph_craft_batch_restart", "eph_craft_batch_reset_knots", "eph_craft_batch_reset_events", "eph_timeline_divergence_time", "eph_craft_batch_enable_events", "eph_craft_batch_event_counts", "eph_craft_batch_events",
-    "eph_craft_batch_destroy", "eph_hermite_eval", "eph_hermite_join", "eph_transitions_join", "eph_apsides_join", "eph_plot_points",
-    "eph_closest_separation", "eph_craft_batch_closest_separation",
-]
+KNOTS_FULL = 6
 
 
 class EphemerisError(RuntimeError):
@@ -80,176 +49,38 @@ class StepError(Exception):
         super().__init__(self.NAMES.get(status, str(status)))
 
 
-_dp = C.POINTER(C.c_double)
-_u32p = C.POINTER(C.c_uint32)
-_i32p = C.POINTER(C.c_int32)
-_u8p = C.POINTER(C.c_uint8)
-_i64p = C.POINTER(C.c_int64)
-_L = None
-KNOTS_FULL = 6
-
-
-class PlotView(C.Structure):
-    """eph_plot_view: camera position, the floating-origin grid's affine map and the simulation time."""
-    _fields_ = [("camera_position", C.c_double * 3), ("grid_matrix3", C.c_double * 9), ("grid_translation", C.c_double * 3),
-                ("cell_offset", C.c_double * 3), ("current", C.c_double)]
-
-
-class PlotRequest(C.Structure):
-    """eph_plot_request = PlotConfig + PlotSource (ephemeris_explorer/src/ui/world/plot.rs:15-83)."""
-    _fields_ = [("source_body", C.c_int32), ("reference_body", C.c_int32), ("knot_first", C.c_int64),
-                ("knot_count", C.c_int64), ("start", C.c_double), ("end", C.c_double), ("bound", C.c_int32),
-                ("enabled", C.c_int32), ("tan2_angular_resolution", C.c_double), ("max_points", C.c_int64)]
-
-
-class SeparationRequest(C.Structure):
-    """eph_separation_request: one closest-separation search of target plotting (ephemeris_explorer/src/analysis.rs:344-348)."""
-    _fields_ = [("source_body", C.c_int32), ("target_body", C.c_int32), ("source_knot_first", C.c_int64),
-                ("source_knot_count", C.c_int64), ("target_knot_first", C.c_int64), ("target_knot_count", C.c_int64),
-                ("left", C.c_double), ("right", C.c_double), ("precision", C.c_double), ("max_iterations", C.c_int64),
-                ("metric", C.c_int32)]
-
-
-class AdaptiveParams(C.Structure):
-    """eph_adaptive_params = integration::AdaptiveMethodParams; defaults = the app's INITIAL_ADAPTIVE_PARAMS
-    (ephemeris_explorer/src/load/mod.rs:472-486)."""
-    _fields_ = [("h_init", C.c_double), ("h_max", C.c_double), ("tol_position", C.c_double),
-                ("tol_velocity", C.c_double), ("fac_min", C.c_double), ("fac_max", C.c_double), ("fac", C.c_double),
-                ("n_max", C.c_uint32)]
-
-    @classmethod
-    def default(cls, tolerance=1e-3):
-        return cls(60.0, 1.7976931348623157e308, tolerance, tolerance, 1.0 / 5.0, 5.0 / 1.0, 9.0 / 10.0, 1_000_000)
-
-
-def _lib():
-    """Loads libephemeris_amd.so; raises if it has not been built (no fallback of any kind)."""
-    global _L
-    if _L is not None:
-        return _L
-    if not LIB_PATH.exists():
-        raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc, gfx950). ephemeris_explorer_amd has no CPU fallback.")
-    L = C.CDLL(str(LIB_PATH))
-    vp, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
-    L.eph_abi_version.restype = i32
-    L.eph_pair_variant.restype = i32
-    L.eph_set_pair_variant.argtypes = [i32]
-    L.eph_status_string.restype = C.c_char_p
-    L.eph_status_string.argtypes = [i32]
-    L.eph_last_error.restype = C.c_char_p
-    L.eph_device_count.argtypes = [_i32p]
-    L.eph_set_device.argtypes = [i32]
-    L.eph_device_name.argtypes = [C.c_char_p, i32]
-    L.eph_srkn_coeffs.argtypes = [C.c_char_p, _i32p, _i32p, _dp, _dp]
-    L.eph_elm2_coeffs.argtypes = [C.c_char_p, _i32p, _dp, _dp, _dp, _dp, _dp]
-    L.eph_accel_eval.argtypes = [i32, _dp, _dp, _dp]
-    L.eph_nbody_create.argtypes = [i32, _dp, _dp, _dp, f64, f64, C.c_char_p, C.POINTER(vp)]
-    L.eph_nbody_advance.argtypes = [vp, i64]
-    L.eph_nbody_get_state.argtypes = [vp, _dp, _dp, _dp, _u32p]
-    L.eph_nbody_get_acc.argtypes = [vp, _dp]
-    L.eph_nbody_set_bound.argtypes = [vp, f64]
-    L.eph_nbody_clone.argtypes = [vp, C.POINTER(vp)]
-    L.eph_nbody_destroy.argtypes = [vp]
-    L.eph_nbody_destroy.restype = None
-    L.eph_nbody_eval_count.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.eph_nbody_set_path.argtypes = [vp, i32]
-    L.eph_rccl_unique_id.argtypes = [vp]
-    L.eph_nbody_shard.argtypes = [vp, i32, i32, vp, EXCHANGE_FN, vp]
-    L.eph_nbody_shard_info.argtypes = [vp, _i32p, _i32p, C.POINTER(C.c_uint64)]
-    L.eph_prop_shard.argtypes = [vp, i32, i32, vp, EXCHANGE_FN, vp]
-    L.eph_peer_create.argtypes = [i32, i32, C.c_uint64, C.POINTER(vp)]
-    L.eph_peer_handle.argtypes = [vp, vp]
-    L.eph_peer_connect.argtypes = [vp, vp]
-    L.eph_peer_destroy.argtypes = [vp]
-    L.eph_nbody_shard_peer.argtypes = [vp, vp]
-    L.eph_prop_shard_peer.argtypes = [vp, vp]
-    L.eph_nbody_advance_many.argtypes = [C.POINTER(vp), i32, i64]
-    L.eph_prop_step_n_many.argtypes = [C.POINTER(vp), i32, i64]
-    L.eph_nbody_kernel_time.argtypes = [vp, _dp, C.POINTER(C.c_uint64)]
-    L.eph_nbody_enable_timing.argtypes = [vp, i32]
-    L.eph_nbody_sync.argtypes = [vp]
-    L.eph_prop_create.argtypes = [i32, _dp, _dp, _dp, f64, f64, i32, C.c_char_p, _u32p, _u32p, C.POINTER(vp)]
-    L.eph_prop_step.argtypes = [vp]
-    L.eph_prop_step_n.argtypes = [vp, i64]
-    L.eph_prop_step_to.argtypes = [vp, f64]
-    L.eph_prop_time.argtypes = [vp, _dp]
-    L.eph_prop_has_reached.argtypes = [vp, f64, _i32p]
-    L.eph_prop_integrator_time.argtypes = [vp, _dp]
-    L.eph_prop_get_state.argtypes = [vp, _dp, _dp, _dp, _u32p]
-    L.eph_prop_take_solution.argtypes = [vp, C.POINTER(vp)]
-    L.eph_prop_propagate.argtypes = [vp, f64, C.POINTER(vp)]
-    L.eph_prop_clone.argtypes = [vp, C.POINTER(vp)]
-    L.eph_prop_destroy.argtypes = [vp]
-    L.eph_prop_destroy.restype = None
-    L.eph_prop_integrator.argtypes = [vp]
-    L.eph_prop_integrator.restype = vp
-    L.eph_solution_bodies.argtypes = [vp, _i32p]
-    L.eph_solution_info.argtypes = [vp, i32, _dp, _dp, C.POINTER(i64)]
-    L.eph_solution_coeffs.argtypes = [vp, i32, _dp, _i32p]
-    L.eph_solution_eval.argtypes = [vp, i32, i64, _dp, _dp, _dp, _u8p]
-    L.eph_solution_append.argtypes = [vp, vp, i32]
-    L.eph_solution_destroy.argtypes = [vp]
-    L.eph_solution_destroy.restype = None
-    L.eph_least_squares_fit.argtypes = [i32, i32, i64, _dp, _dp, _i32p]
-    L.eph_ephemeris_create.argtypes = [vp, _dp, C.POINTER(vp)]
-    L.eph_ephemeris_interpolation_errors.argtypes = [vp, vp, i64, _dp, C.POINTER(i64)]
-    L.eph_ephemeris_destroy.argtypes = [vp]
-    L.eph_ephemeris_destroy.restype = None
-    L.eph_ephemeris_append.argtypes = [vp, vp, i32]
-    L.eph_ephemeris_merge.argtypes = [vp, vp, i32]
-    L.eph_ephemeris_clear.argtypes = [vp, i32, f64, i32]
-    L.eph_ephemeris_info.argtypes = [vp, i32, _dp, _dp, _i64p, C.POINTER(C.c_uint64)]
-    L.eph_ephemeris_is_valid_at.argtypes = [vp, f64, _i32p]
-    L.eph_ephemeris_export.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
-    L.eph_ephemeris_import.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-    L.eph_craft_batch_retry_failed.argtypes = [vp]
-    L.eph_craft_batch_create.argtypes = [vp, i64, _dp, _dp, _dp, C.c_char_p, C.POINTER(AdaptiveParams), _i64p, _dp, _dp,
-                                         _dp, _i32p, i32, C.POINTER(vp)]
-    L.eph_craft_batch_propagate.argtypes = [vp, f64]
-    L.eph_craft_batch_status.argtypes = [vp, _i32p, _i32p, _u32p, _u32p]
-    L.eph_craft_batch_state.argtypes = [vp, _dp, _dp, _dp, _dp]
-    L.eph_craft_batch_knots.argtypes = [vp, i64, _dp, _dp, _dp]
-    L.eph_craft_batch_kernel_time.argtypes = [vp, _dp]
-    L.eph_craft_batch_summary.argtypes = [vp, vp]
-    L.eph_craft_batch_clone.argtypes = [vp, C.POINTER(vp)]
-    L.eph_solution_create.argtypes = [i32, _dp, _dp, _i64p, _dp, _i32p, C.POINTER(vp)]
-    L.eph_solution_clear.argtypes = [vp, i32, f64, i32]
-    L.eph_solution_between.argtypes = [vp, f64, f64, C.POINTER(vp)]
-    L.eph_craft_batch_step_n.argtypes = [vp, C.c_uint32]
-    L.eph_craft_batch_knot_slabs.argtypes = [vp, i32, i32, _dp, _dp]
-    L.eph_craft_batch_eval.argtypes = [vp, i64, _dp, i32, i32, _dp, _u8p]
-    L.eph_craft_batch_plot_points.argtypes = [vp, C.POINTER(PlotView), i64, C.POINTER(PlotRequest), _i64p, i64, _dp,
-                                              C.POINTER(C.c_float), _i64p, _i32p, _dp]
-    L.eph_craft_batch_restart.argtypes = [vp, _u8p, _i64p, _dp, _dp, _dp, _i32p, _dp, C.POINTER(AdaptiveParams), _dp, _i32p]
-    L.eph_craft_batch_reset_knots.argtypes = [vp]
-    L.eph_craft_batch_reset_events.argtypes = [vp]
-    L.eph_timeline_divergence_time.argtypes = [i64, _dp, _dp, _dp, _i32p, i64, _dp, _dp, _dp, _i32p, f64, _dp]
-    L.eph_craft_batch_enable_events.argtypes = [vp, _dp, i32, i32]
-    L.eph_craft_batch_event_counts.argtypes = [vp, _i32p, _i32p, _i32p]
-    L.eph_craft_batch_events.argtypes = [vp, i64, _dp, _i32p, _dp, _dp, _i32p, _i32p]
-    L.eph_craft_batch_destroy.argtypes = [vp]
-    L.eph_craft_batch_destroy.restype = None
-    L.eph_hermite_eval.argtypes = [i64, _dp, _dp, _dp, i64, _dp, _dp, _dp, _u8p]
-    L.eph_plot_points.argtypes = [vp, C.POINTER(PlotView), i64, C.POINTER(PlotRequest), i64, _dp, _dp, _dp, i64, _dp,
-                                  C.POINTER(C.c_float), _i64p, _i32p, _dp]
-    L.eph_closest_separation.argtypes = [vp, i64, C.POINTER(SeparationRequest), i64, _dp, _dp, _dp, _u8p, _dp, _dp, _i32p, _i32p, _dp]
-    L.eph_craft_batch_closest_separation.argtypes = [vp, i64, C.POINTER(SeparationRequest), _i64p, _i64p, _u8p, _dp, _dp, _i32p,
-                                                     _i32p, _dp]
-    L.eph_hermite_join.argtypes = [i64, _dp, _dp, _dp, i64, _dp, _dp, _dp, i64, _dp, _dp, _dp, _i64p]
-    L.eph_transitions_join.argtypes = [i64, _dp, _i32p, i64, _dp, _i32p, f64, i64, _dp, _i32p, _i64p]
-    L.eph_apsides_join.argtypes = [i64, _dp, _dp, _i32p, _i32p, i64, _dp, _dp, _i32p, _i32p, f64, i64, _dp, _dp, _i32p,
-                                   _i32p, _i64p]
-    if L.eph_abi_version() != 3:
-        raise ImportError("libephemeris_amd.so ABI version mismatch")
-    _L = L
-    return L
-
-
 def _check(st, where):
     if st < 0:
         raise EphemerisError(st, where)
     return st
+
+
+def _call(name, *args):
+    """THE call into the library: eph_<name>(*args), a negative status raised as EphemerisError, the status returned."""
+    return _check(getattr(_lib(), name)(*args), name)
+
+
+def _step(name, *args):
+    """_call for the functions that step an integration: a positive status is the StepError the reference returns as Err."""
+    st = _call(name, *args)
+    if st:
+        raise StepError(st)
+
+
+def _contiguous(name, message, *args):
+    """_call for append / prepend / merge: EPH_ERR_BAD_ARGUMENT is the reference's assert_eq! on the splines' ends
+    (UniformSpline::append / prepend, trajectory.rs:517-518,530-531) and raises ValueError(message), the object untouched."""
+    st = getattr(_lib(), name)(*args)
+    if st == ERR_BAD_ARGUMENT:
+        raise ValueError(message)
+    _check(st, name)
+
+
+def _new_handle(name, *args):
+    """_call for the functions that leave a new object in their last parameter (eph_* **out) -> its handle."""
+    h = C.c_void_p()
+    _call(name, *args, C.byref(h))
+    return h
 
 
 def _f64(a):
@@ -260,34 +91,66 @@ def _p(a, t=_dp):
     return a.ctypes.data_as(t)
 
 
+def _p_or_null(a, t=_dp):
+    return None if a is None else _p(a, t)
+
+
+class _Handle:
+    """An object of the library: `_L` the library, `_h` the handle, destroyed with the Python object unless it is borrowed
+    from another one. A subclass names its eph_*_destroy in _DESTROY and binds the handle it creates with _bind()."""
+    _DESTROY = None
+    _owned = True
+
+    def _bind(self, handle):
+        self._L, self._h = _lib(), handle        # __del__ goes through self._L: module globals may be gone by then
+
+    @classmethod
+    def _adopt(cls, handle, owned=True, **attributes):
+        """An existing handle as a `cls`, __init__ not run: `attributes` are the ones __init__ would have set."""
+        self = object.__new__(cls)
+        self._bind(handle)
+        self._owned = owned
+        vars(self).update(attributes)
+        return self
+
+    def _clone(self, name):
+        """eph_*_clone -> a `cls` with a handle of its own and every other attribute of this one."""
+        return self._adopt(_new_handle(name, self._h), **{k: v for k, v in vars(self).items() if k not in ("_L", "_h", "_owned")})
+
+    def __del__(self):
+        if self._owned and getattr(self, "_h", None):
+            getattr(self._L, self._DESTROY)(self._h)
+            self._h = None
+
+
+
 def device_count():
     n = C.c_int32()
-    _check(_lib().eph_device_count(C.byref(n)), "eph_device_count")
+    _call("eph_device_count", C.byref(n))
     return n.value
 
 
 def set_device(i):
-    _check(_lib().eph_set_device(int(i)), "eph_set_device")
+    _call("eph_set_device", int(i))
 
 
 def release_cached_memory():
     """Returns the library's cache of large device blocks to the driver (eph_release_cached_memory); bytes released."""
     b = C.c_uint64()
-    _lib().eph_release_cached_memory.argtypes = [C.POINTER(C.c_uint64)]
-    _check(_lib().eph_release_cached_memory(C.byref(b)), "eph_release_cached_memory")
+    _call("eph_release_cached_memory", C.byref(b))
     return int(b.value)
 
 
 def device_name():
     buf = C.create_string_buffer(256)
-    _check(_lib().eph_device_name(buf, 256), "eph_device_name")
+    _call("eph_device_name", buf, 256)
     return buf.value.decode()
 
 
 def srkn_coeffs(name):
     A, B = np.zeros(32), np.zeros(32)
     s, f = C.c_int32(), C.c_int32()
-    _check(_lib().eph_srkn_coeffs(name.encode(), C.byref(s), C.byref(f), _p(A), _p(B)), "eph_srkn_coeffs")
+    _call("eph_srkn_coeffs", name.encode(), C.byref(s), C.byref(f), _p(A), _p(B))
     return A[: s.value].copy(), B[: s.value].copy(), bool(f.value)
 
 
@@ -295,8 +158,7 @@ def elm2_coeffs(name):
     wa, wb, cw = np.zeros(16), np.zeros(16), np.zeros(16)
     o = C.c_int32()
     ib, ic = C.c_double(), C.c_double()
-    _check(_lib().eph_elm2_coeffs(name.encode(), C.byref(o), _p(wa), _p(wb), C.byref(ib), _p(cw), C.byref(ic)),
-           "eph_elm2_coeffs")
+    _call("eph_elm2_coeffs", name.encode(), C.byref(o), _p(wa), _p(wb), C.byref(ib), _p(cw), C.byref(ic))
     k = o.value
     return dict(order=k, w_alpha=wa[:k].copy(), w_beta=wb[:k].copy(), inv_beta_d=ib.value, cowell=cw[:k].copy(),
                 inv_cowell_d=ic.value)
@@ -306,7 +168,7 @@ def accel_eval(pos, mu, acc=None):
     """SecondOrderODE::eval for NewtonianGravity: returns acc (+= the accelerations, reference summation order)."""
     pos, mu = _f64(pos), _f64(mu)
     acc = np.zeros_like(pos) if acc is None else _f64(acc).copy()
-    _check(_lib().eph_accel_eval(len(mu), _p(pos), _p(mu), _p(acc)), "eph_accel_eval")
+    _call("eph_accel_eval", len(mu), _p(pos), _p(mu), _p(acc))
     return acc
 
 
@@ -316,8 +178,7 @@ def least_squares_fit(degree, samples, backward=False):
     nwin = samples.shape[0]
     co = np.zeros((nwin, 8, 3))
     nc = np.zeros(nwin, dtype=np.int32)
-    _check(_lib().eph_least_squares_fit(int(degree), int(bool(backward)), nwin, _p(samples), _p(co), _p(nc, _i32p)),
-           "eph_least_squares_fit")
+    _call("eph_least_squares_fit", int(degree), int(bool(backward)), nwin, _p(samples), _p(co), _p(nc, _i32p))
     return co, nc
 
 
@@ -328,10 +189,10 @@ def pair_variant():
 
 def set_pair_variant(k):
     """eph_set_pair_variant: the order (0..6, csrc/pair_term.h) for every handle created afterwards"""
-    _check(_lib().eph_set_pair_variant(int(k)), "eph_set_pair_variant")
+    _call("eph_set_pair_variant", int(k))
 
 
-def _shard_call(fn, name, handle, rank, world, unique_id, exchange):
+def _shard_call(name, handle, rank, world, unique_id, exchange):
     cb = None
     if exchange is not None:
         def _tramp(ctx, buf, nbytes, r, w, stream):
@@ -347,190 +208,146 @@ def _shard_call(fn, name, handle, rank, world, unique_id, exchange):
         if len(unique_id) != 128:
             raise ValueError("unique_id must be 128 bytes")
         uid = (C.c_char * 128).from_buffer_copy(bytes(unique_id))
-    _check(fn(handle, int(rank), int(world), uid, cb if cb else EXCHANGE_FN(0), None), name)
+    _call(name, handle, int(rank), int(world), uid, cb if cb else EXCHANGE_FN(0), None)
     return cb                                          # the caller keeps the trampoline alive with the handle
 
 
 def advance_many(integrations, n_steps):
     """eph_nbody_advance_many: advance(n_steps) on every NBodyIntegration of the list, small systems in one launch."""
     arr = (C.c_void_p * len(integrations))(*[g._h for g in integrations])
-    st = _check(_lib().eph_nbody_advance_many(arr, len(integrations), int(n_steps)), "eph_nbody_advance_many")
-    if st:
-        raise StepError(st)
+    _step("eph_nbody_advance_many", arr, len(integrations), int(n_steps))
 
 
 def step_n_many(propagators, n_steps):
     """eph_prop_step_n_many: step_n(n_steps) on every NBodyPropagator of the list, small systems in shared launches."""
     arr = (C.c_void_p * len(propagators))(*[p._h for p in propagators])
-    st = _check(_lib().eph_prop_step_n_many(arr, len(propagators), int(n_steps)), "eph_prop_step_n_many")
-    if st:
-        raise StepError(st)
+    _step("eph_prop_step_n_many", arr, len(propagators), int(n_steps))
 
 
-class PeerTransport:
+class PeerTransport(_Handle):
     """eph_peer: the direct-write exchange (csrc/peer.hip). Create on every rank, pass `handle` (64 bytes) to every other
     rank, `connect(handles)` with all of them in rank order, then hand it to `NBodyIntegration.shard_peer` /
     `NBodyPropagator.shard_peer` (`parallel.peer_transport(dist)` does the hand-shake over torch.distributed)."""
 
+    _DESTROY = "eph_peer_destroy"
     MEMORY = {"auto": 0, "fine": 1, "coarse": 2}
 
     def __init__(self, rank, world, slot_bytes=1 << 22, memory="auto"):
-        self._L = _lib()
-        h = C.c_void_p()
-        self._L.eph_peer_create_ex.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.POINTER(C.c_void_p)]
-        _check(self._L.eph_peer_create_ex(int(rank), int(world), int(slot_bytes), self.MEMORY[memory], C.byref(h)), "eph_peer_create_ex")
-        self._h = h
+        self._bind(_new_handle("eph_peer_create_ex", int(rank), int(world), int(slot_bytes), self.MEMORY[memory]))
         self.rank, self.world = int(rank), int(world)
         f = C.c_int32()
-        self._L.eph_peer_memory_form.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        _check(self._L.eph_peer_memory_form(self._h, C.byref(f)), "eph_peer_memory_form")
+        _call("eph_peer_memory_form", self._h, C.byref(f))
         self.memory = {1: "fine", 2: "coarse"}[f.value]          # what is live (auto may have fallen back)
         buf = (C.c_char * 64)()
-        _check(self._L.eph_peer_handle(self._h, buf), "eph_peer_handle")
+        _call("eph_peer_handle", self._h, buf)
         self.handle = bytes(buf)
 
     def connect(self, handles):
         table = b"".join(bytes(h) for h in handles)
         if len(table) != 64 * self.world:
             raise ValueError("need one 64-byte handle per rank")
-        _check(self._L.eph_peer_connect(self._h, (C.c_char * len(table)).from_buffer_copy(table)), "eph_peer_connect")
+        _call("eph_peer_connect", self._h, (C.c_char * len(table)).from_buffer_copy(table))
         return self
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._L.eph_peer_destroy(self._h)
-            self._h = None
-
-
-def hip_runtime():
-    """The HIP runtime libephemeris_amd.so is bound to IN THIS PROCESS, as a ctypes object with hipMemcpy and
-    hipStreamSynchronize: symbols looked up through the library's own handle (dlsym searches its dependencies), not through
-    whatever "libamdhip64.so" resolves to -- a process that also imported PyTorch may carry a second, bundled runtime, and
-    device pointers / streams of one mean nothing to the other. For host programs (and tests) that touch the library's device
-    buffers themselves, e.g. inside an eph_exchange_fn."""
-    lib = _lib()
-    lib.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    lib.hipMemcpy.restype = C.c_int
-    lib.hipStreamSynchronize.argtypes = [C.c_void_p]
-    lib.hipStreamSynchronize.restype = C.c_int
-    return lib
 
 
 def rccl_unique_id():
     """ncclGetUniqueId through the library (rank 0 calls it and distributes the 128 bytes)."""
     out = (C.c_char * 128)()
-    _check(_lib().eph_rccl_unique_id(out), "eph_rccl_unique_id")
+    _call("eph_rccl_unique_id", out)
     return bytes(out.raw)
 
 
-class NBodyIntegration:
+class NBodyIntegration(_Handle):
     """Integration<NBodyProblem<DVec3>, M> (no solout). method: "QuinlanTremaine12", "Stormer13" or an SRKN name."""
 
-    def __init__(self, pos, vel, mu, t0, h, method="QuinlanTremaine12", _handle=None, _owned=True):
-        self._L = _lib()
-        self._owned = _owned
-        if _handle is not None:
-            self._h, self.n = _handle
-            return
+    _DESTROY = "eph_nbody_destroy"
+
+    def __init__(self, pos, vel, mu, t0, h, method="QuinlanTremaine12"):
         pos, vel, mu = _f64(pos), _f64(vel), _f64(mu)
         self.n = len(mu)
-        h_ = C.c_void_p()
-        st = self._L.eph_nbody_create(self.n, _p(pos), _p(vel), _p(mu), float(t0), float(h), method.encode(),
-                                      C.byref(h_))
-        _check(st, "eph_nbody_create")
-        self._h = h_
+        self._bind(_new_handle("eph_nbody_create", self.n, _p(pos), _p(vel), _p(mu), float(t0), float(h), method.encode()))
 
     def advance(self, n_steps=1):
         """n_steps x Integrator::advance; raises StepError like the reference returns Err."""
-        st = _check(self._L.eph_nbody_advance(self._h, int(n_steps)), "eph_nbody_advance")
-        if st:
-            raise StepError(st)
+        _step("eph_nbody_advance", self._h, int(n_steps))
 
     def state(self):
         pos, vel = np.zeros((self.n, 3)), np.zeros((self.n, 3))
         t, sc = C.c_double(), C.c_uint32()
-        _check(self._L.eph_nbody_get_state(self._h, _p(pos), _p(vel), C.byref(t), C.byref(sc)), "eph_nbody_get_state")
+        _call("eph_nbody_get_state", self._h, _p(pos), _p(vel), C.byref(t), C.byref(sc))
         return pos, vel, t.value, sc.value
 
     def acc(self):
         a = np.zeros((self.n, 3))
-        _check(self._L.eph_nbody_get_acc(self._h, _p(a)), "eph_nbody_get_acc")
+        _call("eph_nbody_get_acc", self._h, _p(a))
         return a
 
     def set_bound(self, b):
-        _check(self._L.eph_nbody_set_bound(self._h, float(b)), "eph_nbody_set_bound")
+        _call("eph_nbody_set_bound", self._h, float(b))
 
     def set_path(self, path):
         """0 auto | 1 wave kernel | 2 single workgroup | 3 workgroup kernel (all bit-identical to the reference order) |
         PATH_FAST = 4: opt-in slice-parallel sums, NOT the reference's summation order (include/ephemeris_amd.h)."""
-        _check(self._L.eph_nbody_set_path(self._h, int(path)), "eph_nbody_set_path")
+        _call("eph_nbody_set_path", self._h, int(path))
 
     def enable_timing(self, on=True):
-        _check(self._L.eph_nbody_enable_timing(self._h, int(on)), "eph_nbody_enable_timing")
+        _call("eph_nbody_enable_timing", self._h, int(on))
 
     def kernel_time(self):
         ms, n = C.c_double(), C.c_uint64()
-        _check(self._L.eph_nbody_kernel_time(self._h, C.byref(ms), C.byref(n)), "eph_nbody_kernel_time")
+        _call("eph_nbody_kernel_time", self._h, C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def sync(self):
-        _check(self._L.eph_nbody_sync(self._h), "eph_nbody_sync")
+        _call("eph_nbody_sync", self._h)
 
     def eval_count(self):
         n = C.c_uint64()
-        _check(self._L.eph_nbody_eval_count(self._h, C.byref(n)), "eph_nbody_eval_count")
+        _call("eph_nbody_eval_count", self._h, C.byref(n))
         return n.value
 
     def clone(self):
-        h_ = C.c_void_p()
-        _check(self._L.eph_nbody_clone(self._h, C.byref(h_)), "eph_nbody_clone")
-        return NBodyIntegration(None, None, None, 0, 0, _handle=(h_, self.n))
+        return self._clone("eph_nbody_clone")
 
     def shard(self, rank, world, unique_id=None, exchange=None):
         """Partition the system by target body over `world` ranks (eph_nbody_shard). unique_id: the 128 bytes of
         rccl_unique_id() from rank 0 (RCCL transport), or exchange: callable(device_ptr, slice_bytes, rank, world,
         hip_stream) -> 0 performing the in-place all-gather (see parallel.host_staged_exchange)."""
-        self._exchange_cb = _shard_call(self._L.eph_nbody_shard, "eph_nbody_shard", self._h, rank, world, unique_id,
-                                        exchange)
+        self._exchange_cb = _shard_call("eph_nbody_shard", self._h, rank, world, unique_id, exchange)
         return self
 
     def shard_peer(self, peer):
         """eph_nbody_shard_peer: the same partition with the direct-write transport (a connected PeerTransport)."""
-        _check(self._L.eph_nbody_shard_peer(self._h, peer._h), "eph_nbody_shard_peer")
+        _call("eph_nbody_shard_peer", self._h, peer._h)
         self._peer = peer
         return self
 
     def shard_info(self):
         lo, hi, g = C.c_int32(), C.c_int32(), C.c_uint64()
-        _check(self._L.eph_nbody_shard_info(self._h, C.byref(lo), C.byref(hi), C.byref(g)), "eph_nbody_shard_info")
+        _call("eph_nbody_shard_info", self._h, C.byref(lo), C.byref(hi), C.byref(g))
         return lo.value, hi.value, g.value
 
-    def __del__(self):
-        if getattr(self, "_owned", False) and getattr(self, "_h", None):
-            self._L.eph_nbody_destroy(self._h)
-            self._h = None
 
-
-class Solution:
+class Solution(_Handle):
     """Vec<UniformSpline<DVec3>>"""
+    _DESTROY = "eph_solution_destroy"
 
     def __init__(self, handle):
-        self._L = _lib()
-        self._h = handle
+        self._bind(handle)
         n = C.c_int32()
-        _check(self._L.eph_solution_bodies(handle, C.byref(n)), "eph_solution_bodies")
+        _call("eph_solution_bodies", handle, C.byref(n))
         self.n = n.value
 
     def info(self, body):
         s, i, n = C.c_double(), C.c_double(), C.c_int64()
-        _check(self._L.eph_solution_info(self._h, body, C.byref(s), C.byref(i), C.byref(n)), "eph_solution_info")
+        _call("eph_solution_info", self._h, body, C.byref(s), C.byref(i), C.byref(n))
         return s.value, i.value, n.value
 
     def coeffs(self, body):
         n = self.info(body)[2]
         co = np.zeros((max(n, 1), 8, 3))
         nc = np.zeros(max(n, 1), dtype=np.int32)
-        _check(self._L.eph_solution_coeffs(self._h, body, _p(co), _p(nc, _i32p)), "eph_solution_coeffs")
+        _call("eph_solution_coeffs", self._h, body, _p(co), _p(nc, _i32p))
         return co[:n], nc[:n]
 
     def eval(self, body, at, with_velocity=True):
@@ -540,8 +357,7 @@ class Solution:
         pos = np.zeros((m, 3))
         vel = np.zeros((m, 3)) if with_velocity else None
         inside = np.zeros(m, dtype=np.uint8)
-        _check(self._L.eph_solution_eval(self._h, body, m, _p(at), _p(pos), _p(vel) if with_velocity else None,
-                                         _p(inside, _u8p)), "eph_solution_eval")
+        _call("eph_solution_eval", self._h, body, m, _p(at), _p(pos), _p(vel) if with_velocity else None, _p(inside, _u8p))
         return pos, vel, inside.astype(bool)
 
     @classmethod
@@ -558,52 +374,36 @@ class Solution:
                 co[q, :len(poly)] = poly
                 nc[q] = len(poly)
                 q += 1
-        h_ = C.c_void_p()
-        _check(_lib().eph_solution_create(n, _p(_f64(start)), _p(_f64(interval)), _p(npoly, _i64p), _p(co), _p(nc, _i32p),
-                                          C.byref(h_)), "eph_solution_create")
-        return cls(h_)
+        return cls._adopt(_new_handle("eph_solution_create", n, _p(_f64(start)), _p(_f64(interval)), _p(npoly, _i64p), _p(co),
+                                      _p(nc, _i32p)), n=n)
 
     def clear_before(self, at, body=-1):
-        _check(self._L.eph_solution_clear(self._h, int(body), float(at), 0), "eph_solution_clear")
+        _call("eph_solution_clear", self._h, int(body), float(at), 0)
 
     def clear_after(self, at, body=-1):
-        _check(self._L.eph_solution_clear(self._h, int(body), float(at), 1), "eph_solution_clear")
+        _call("eph_solution_clear", self._h, int(body), float(at), 1)
 
     def between(self, start, end):
         """UniformSpline::between for every body -> Solution, or None where the reference returns None."""
-        h_ = C.c_void_p()
-        _check(self._L.eph_solution_between(self._h, float(start), float(end), C.byref(h_)), "eph_solution_between")
-        return Solution(h_) if h_.value else None
+        h = _new_handle("eph_solution_between", self._h, float(start), float(end))
+        return Solution._adopt(h, n=self.n) if h.value else None
 
     def append(self, tail, direction=FORWARD):
-        st = self._L.eph_solution_append(self._h, tail._h, int(direction))
-        if st == ERR_BAD_ARGUMENT:
-            raise ValueError("splines are not contiguous (UniformSpline::append/prepend assert)")
-        _check(st, "eph_solution_append")
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._L.eph_solution_destroy(self._h)
-            self._h = None
+        _contiguous("eph_solution_append", "splines are not contiguous (UniformSpline::append/prepend assert)", self._h, tail._h,
+                    int(direction))
 
 
-class NBodyPropagator:
+class NBodyPropagator(_Handle):
     """NBodyPropagator<D, DVec3, M, SplineInterpolators<D, DVec3, LeastSquaresFit>> on the device."""
+    _DESTROY = "eph_prop_destroy"
 
-    def __init__(self, pos, vel, mu, t0, dt, direction, count, degree, method="QuinlanTremaine12", _handle=None):
-        self._L = _lib()
-        if _handle is not None:
-            self._h, self.n = _handle
-            return
+    def __init__(self, pos, vel, mu, t0, dt, direction, count, degree, method="QuinlanTremaine12"):
         pos, vel, mu = _f64(pos), _f64(vel), _f64(mu)
         count = np.ascontiguousarray(count, dtype=np.uint32)
         degree = np.ascontiguousarray(degree, dtype=np.uint32)
         self.n = len(mu)
-        h_ = C.c_void_p()
-        st = self._L.eph_prop_create(self.n, _p(pos), _p(vel), _p(mu), float(t0), float(dt), int(direction),
-                                     method.encode(), _p(count, _u32p), _p(degree, _u32p), C.byref(h_))
-        _check(st, "eph_prop_create")
-        self._h = h_
+        self._bind(_new_handle("eph_prop_create", self.n, _p(pos), _p(vel), _p(mu), float(t0), float(dt), int(direction),
+                               method.encode(), _p(count, _u32p), _p(degree, _u32p)))
 
     @classmethod
     def from_system(cls, system, direction=FORWARD, method="QuinlanTremaine12"):
@@ -614,86 +414,68 @@ class NBodyPropagator:
     def shard(self, rank, world, unique_id=None, exchange=None):
         """eph_prop_shard: partition the propagator's system by target body over the ranks (right after creation, on
         every rank); arguments as NBodyIntegration.shard."""
-        self._exchange_cb = _shard_call(self._L.eph_prop_shard, "eph_prop_shard", self._h, rank, world, unique_id,
-                                        exchange)
+        self._exchange_cb = _shard_call("eph_prop_shard", self._h, rank, world, unique_id, exchange)
         return self
 
     def shard_peer(self, peer):
         """eph_prop_shard_peer: eph_prop_shard with the direct-write transport (a connected PeerTransport)."""
-        _check(self._L.eph_prop_shard_peer(self._h, peer._h), "eph_prop_shard_peer")
+        _call("eph_prop_shard_peer", self._h, peer._h)
         self._peer = peer
         return self
 
-    def _step_status(self, st, where):
-        st = _check(st, where)
-        if st:
-            raise StepError(st)
-
     def step(self):
-        self._step_status(self._L.eph_prop_step(self._h), "eph_prop_step")
+        _step("eph_prop_step", self._h)
 
     def step_n(self, n):
-        self._step_status(self._L.eph_prop_step_n(self._h, int(n)), "eph_prop_step_n")
+        _step("eph_prop_step_n", self._h, int(n))
 
     def step_to(self, t):
-        self._step_status(self._L.eph_prop_step_to(self._h, float(t)), "eph_prop_step_to")
+        _step("eph_prop_step_to", self._h, float(t))
 
     def time(self):
         t = C.c_double()
-        _check(self._L.eph_prop_time(self._h, C.byref(t)), "eph_prop_time")
+        _call("eph_prop_time", self._h, C.byref(t))
         return t.value
 
     def has_reached(self, t):
         f = C.c_int32()
-        _check(self._L.eph_prop_has_reached(self._h, float(t), C.byref(f)), "eph_prop_has_reached")
+        _call("eph_prop_has_reached", self._h, float(t), C.byref(f))
         return bool(f.value)
 
     def integrator_time(self):
         t = C.c_double()
-        _check(self._L.eph_prop_integrator_time(self._h, C.byref(t)), "eph_prop_integrator_time")
+        _call("eph_prop_integrator_time", self._h, C.byref(t))
         return t.value
 
     def state(self):
         pos, vel = np.zeros((self.n, 3)), np.zeros((self.n, 3))
         t, sc = C.c_double(), C.c_uint32()
-        _check(self._L.eph_prop_get_state(self._h, _p(pos), _p(vel), C.byref(t), C.byref(sc)), "eph_prop_get_state")
+        _call("eph_prop_get_state", self._h, _p(pos), _p(vel), C.byref(t), C.byref(sc))
         return pos, vel, t.value, sc.value
 
     def take_solution(self):
-        h_ = C.c_void_p()
-        _check(self._L.eph_prop_take_solution(self._h, C.byref(h_)), "eph_prop_take_solution")
-        return Solution(h_)
+        return Solution._adopt(_new_handle("eph_prop_take_solution", self._h), n=self.n)
 
     def propagate(self, to):
-        h_ = C.c_void_p()
-        self._step_status(self._L.eph_prop_propagate(self._h, float(to), C.byref(h_)), "eph_prop_propagate")
-        return Solution(h_)
+        h = C.c_void_p()
+        _step("eph_prop_propagate", self._h, float(to), C.byref(h))
+        return Solution._adopt(h, n=self.n)
 
     def integration(self):
         """the NBodyIntegration inside (borrowed)"""
-        return NBodyIntegration(None, None, None, 0, 0, _handle=(C.c_void_p(self._L.eph_prop_integrator(self._h)), self.n),
-                                _owned=False)
+        return NBodyIntegration._adopt(C.c_void_p(self._L.eph_prop_integrator(self._h)), owned=False, n=self.n)
 
     def clone(self):
-        h_ = C.c_void_p()
-        _check(self._L.eph_prop_clone(self._h, C.byref(h_)), "eph_prop_clone")
-        return NBodyPropagator(None, None, None, 0, 0, 0, None, None, _handle=(h_, self.n))
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._L.eph_prop_destroy(self._h)
-            self._h = None
+        return self._clone("eph_prop_clone")
 
 
-class Ephemeris:
+class Ephemeris(_Handle):
     """Device-resident table of the massive bodies' UniformSplines (what `Bodies` holds in the app)."""
+    _DESTROY = "eph_ephemeris_destroy"
 
     def __init__(self, solution, mu):
-        self._L = _lib()
         mu = _f64(mu)
-        h_ = C.c_void_p()
-        _check(self._L.eph_ephemeris_create(solution._h, _p(mu), C.byref(h_)), "eph_ephemeris_create")
-        self._h = h_
+        self._bind(_new_handle("eph_ephemeris_create", solution._h, _p(mu)))
         self.n_bodies = len(mu)
 
     # ---- the table is LIVE, like the reference's Arc<RwLock<PredictionTrajectory>> (dynamics/mod.rs:84-85): every batch bound to
@@ -701,44 +483,40 @@ class Ephemeris:
     def append(self, tail, direction=FORWARD):
         """UniformSpline::append (FORWARD) / prepend (BACKWARD) for every body (trajectory.rs:515-534); raises ValueError where the
         reference's assert_eq! would panic, the table untouched."""
-        st = self._L.eph_ephemeris_append(self._h, tail._h, int(direction))
-        if st == ERR_BAD_ARGUMENT:
-            raise ValueError("eph_ephemeris_append: not contiguous (trajectory.rs:517-518,530-531)")
-        _check(st, "eph_ephemeris_append")
+        _contiguous("eph_ephemeris_append", "eph_ephemeris_append: not contiguous (trajectory.rs:517-518,530-531)", self._h, tail._h,
+                    int(direction))
         return self
 
     def merge(self, propagated, direction=FORWARD):
         """PredictionTarget::merge for the bodies (dynamics/celestial.rs:198-204 Forward, :220-226 Backward)."""
-        st = self._L.eph_ephemeris_merge(self._h, propagated._h, int(direction))
-        if st == ERR_BAD_ARGUMENT:
-            raise ValueError("eph_ephemeris_merge: not contiguous (trajectory.rs:517-518,530-531)")
-        _check(st, "eph_ephemeris_merge")
+        _contiguous("eph_ephemeris_merge", "eph_ephemeris_merge: not contiguous (trajectory.rs:517-518,530-531)", self._h,
+                    propagated._h, int(direction))
         return self
 
     def clear_before(self, at, body=-1):
-        _check(self._L.eph_ephemeris_clear(self._h, int(body), float(at), 0), "eph_ephemeris_clear")
+        _call("eph_ephemeris_clear", self._h, int(body), float(at), 0)
         return self
 
     def clear_after(self, at, body=-1):
-        _check(self._L.eph_ephemeris_clear(self._h, int(body), float(at), 1), "eph_ephemeris_clear")
+        _call("eph_ephemeris_clear", self._h, int(body), float(at), 1)
         return self
 
     def info(self, body):
         """(start, interval, npoly) of one body's spline as it is now"""
         s_, iv, npoly = C.c_double(), C.c_double(), C.c_int64()
-        _check(self._L.eph_ephemeris_info(self._h, int(body), C.byref(s_), C.byref(iv), C.byref(npoly), None), "eph_ephemeris_info")
+        _call("eph_ephemeris_info", self._h, int(body), C.byref(s_), C.byref(iv), C.byref(npoly), None)
         return s_.value, iv.value, npoly.value
 
     @property
     def revision(self):
         r = C.c_uint64()
-        _check(self._L.eph_ephemeris_info(self._h, -1, None, None, None, C.byref(r)), "eph_ephemeris_info")
+        _call("eph_ephemeris_info", self._h, -1, None, None, None, C.byref(r))
         return r.value
 
     def is_valid_at(self, t):
         """Bodies::is_valid_at (dynamics/spacecraft.rs:206-208)"""
         f = C.c_int32()
-        _check(self._L.eph_ephemeris_is_valid_at(self._h, float(t), C.byref(f)), "eph_ephemeris_is_valid_at")
+        _call("eph_ephemeris_is_valid_at", self._h, float(t), C.byref(f))
         return bool(f.value)
 
     def export_image(self):
@@ -746,90 +524,61 @@ class Ephemeris:
         need = C.c_uint64()
         self._L.eph_ephemeris_export(self._h, None, 0, C.byref(need))
         buf = np.empty(need.value, dtype=np.uint8)
-        _check(self._L.eph_ephemeris_export(self._h, buf.ctypes.data_as(C.c_void_p), need.value, C.byref(need)), "eph_ephemeris_export")
+        _call("eph_ephemeris_export", self._h, _p(buf, C.c_void_p), need.value, C.byref(need))
         return buf
 
     @classmethod
     def from_image(cls, image):
         image = np.ascontiguousarray(image, dtype=np.uint8)
-        L = _lib()
-        h_ = C.c_void_p()
-        _check(L.eph_ephemeris_import(image.ctypes.data_as(C.c_void_p), image.size, C.byref(h_)), "eph_ephemeris_import")
-        e = object.__new__(cls)
-        e._L, e._h = L, h_
-        e.n_bodies = int(np.frombuffer(image[8:16].tobytes(), dtype=np.uint64)[0])
-        return e
+        return cls._adopt(_new_handle("eph_ephemeris_import", _p(image, C.c_void_p), image.size),
+                          n_bodies=int(np.frombuffer(image[8:16].tobytes(), dtype=np.uint64)[0]))
 
     def interpolation_errors(self, integration, n_steps):
         """debug.rs:182-238: advance `integration` (NBodyIntegration over the same bodies) up to n_steps steps, or to its
         bound, and return (max |position - spline position| per body in metres, steps taken)."""
         err = np.zeros(self.n_bodies)
         done = C.c_int64()
-        _check(self._L.eph_ephemeris_interpolation_errors(self._h, integration._h, int(n_steps), _p(err),
-                                                          C.byref(done)), "eph_ephemeris_interpolation_errors")
+        _call("eph_ephemeris_interpolation_errors", self._h, integration._h, int(n_steps), _p(err), C.byref(done))
         return err, done.value
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._L.eph_ephemeris_destroy(self._h)
-            self._h = None
 
-
-class SpacecraftBatch:
+class SpacecraftBatch(_Handle):
     """n independent SpacecraftPropagator<[StateVector;1], ReferenceFrame, Bodies, <adaptive ERK pair>,
     CubicHermiteSplineSolout>, one device thread each. burns[i] = list of (start, end, acc[3], ref_body or -1)."""
+    _DESTROY = "eph_craft_batch_destroy"
 
     def __init__(self, ephemeris, t0, pos, vel, method="Verner87", params=None, burns=None, max_knots=4096):
-        self._L = _lib()
         self.ephemeris = ephemeris
         pos, vel = _f64(pos).reshape(-1, 3), _f64(vel).reshape(-1, 3)
         self.n = len(pos)
         t0 = _f64(np.broadcast_to(np.asarray(t0, dtype=np.float64), (self.n,)))
         self.params = params or AdaptiveParams.default()
         burns = burns if burns is not None else [[] for _ in range(self.n)]
-        off = np.zeros(self.n + 1, dtype=np.int64)
-        flat = []
-        for i, bl in enumerate(burns):
-            flat.extend(bl)
-            off[i + 1] = len(flat)
-        bs = _f64([b[0] for b in flat] or [0.0])
-        be = _f64([b[1] for b in flat] or [0.0])
-        ba = _f64([b[2] for b in flat] or [[0.0, 0.0, 0.0]])
-        br = np.ascontiguousarray([b[3] for b in flat] or [0], dtype=np.int32)
-        h_ = C.c_void_p()
-        st = self._L.eph_craft_batch_create(ephemeris._h, self.n, _p(t0), _p(pos), _p(vel), method.encode(),
-                                            C.byref(self.params), _p(off, _i64p), _p(bs), _p(be), _p(ba), _p(br, _i32p),
-                                            int(max_knots), C.byref(h_))
-        _check(st, "eph_craft_batch_create")
-        self._h = h_
+        self._bind(_new_handle("eph_craft_batch_create", ephemeris._h, self.n, _p(t0), _p(pos), _p(vel), method.encode(),
+                               C.byref(self.params), *_burn_csr(burns, self.n), int(max_knots)))
 
     def step_n(self, n_steps=1):
         """IncrementalPropagator::step n_steps times for every craft (one knot per step)."""
-        _check(self._L.eph_craft_batch_step_n(self._h, int(n_steps)), "eph_craft_batch_step_n")
+        _call("eph_craft_batch_step_n", self._h, int(n_steps))
 
     def clone(self):
         """SpacecraftPropagator: Clone -- a deep copy (state, knots, events) that can be resumed independently."""
-        h_ = C.c_void_p()
-        _check(self._L.eph_craft_batch_clone(self._h, C.byref(h_)), "eph_craft_batch_clone")
-        c = object.__new__(SpacecraftBatch)
-        c._L, c.ephemeris, c.n, c.params, c._h = self._L, self.ephemeris, self.n, self.params, h_
-        return c
+        return self._clone("eph_craft_batch_clone")
 
     def retry_failed(self):
         """Re-arm: the NEXT propagate / step_n steps the craft whose last step returned a StepError too -- the reference's next
         step() on a propagator that returned Err (how a stored ship propagator resumes once the ephemeris has grown)."""
-        _check(self._L.eph_craft_batch_retry_failed(self._h), "eph_craft_batch_retry_failed")
+        _call("eph_craft_batch_retry_failed", self._h)
         return self
 
     def propagate(self, t_end):
         """step_to(t_end) for every craft; per-craft outcomes in status()"""
-        _check(self._L.eph_craft_batch_propagate(self._h, float(t_end)), "eph_craft_batch_propagate")
+        _call("eph_craft_batch_propagate", self._h, float(t_end))
 
     def status(self):
         st, nk = np.zeros(self.n, np.int32), np.zeros(self.n, np.int32)
         at, sp = np.zeros(self.n, np.uint32), np.zeros(self.n, np.uint32)
-        _check(self._L.eph_craft_batch_status(self._h, _p(st, _i32p), _p(nk, _i32p), _p(at, _u32p), _p(sp, _u32p)),
-               "eph_craft_batch_status")
+        _call("eph_craft_batch_status", self._h, _p(st, _i32p), _p(nk, _i32p), _p(at, _u32p), _p(sp, _u32p))
         return dict(status=st, nknots=nk, attempts=at, steps=sp)
 
     RECORD = np.dtype([("t", "f8"), ("pos", "f8", 3), ("vel", "f8", 3), ("next_h", "f8"), ("status", "i4"), ("nknots", "i4"),
@@ -838,11 +587,8 @@ class SpacecraftBatch:
     def set_body_order(self, order):
         """The order in which the massive bodies' terms are added in the acceleration (eph_craft_batch_set_body_order):
         a permutation of range(n_bodies), or None for the table's order."""
-        if order is None:
-            _check(self._L.eph_craft_batch_set_body_order(self._h, None), "eph_craft_batch_set_body_order")
-        else:
-            o = np.ascontiguousarray(order, dtype=np.int32)
-            _check(self._L.eph_craft_batch_set_body_order(self._h, o.ctypes.data_as(C.POINTER(C.c_int32))), "eph_craft_batch_set_body_order")
+        o = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+        _call("eph_craft_batch_set_body_order", self._h, _p_or_null(o, _i32p))
         return self
 
     def summary(self, out=None):
@@ -851,19 +597,19 @@ class SpacecraftBatch:
         has its pages mapped already: the copy into a fresh 21 MB allocation pays a page fault per 4 KB)."""
         rec = np.empty(self.n, dtype=self.RECORD) if out is None else out
         assert rec.itemsize == 80 and rec.shape == (self.n,) and rec.flags.c_contiguous
-        _check(self._L.eph_craft_batch_summary(self._h, rec.ctypes.data_as(C.c_void_p)), "eph_craft_batch_summary")
+        _call("eph_craft_batch_summary", self._h, rec.ctypes.data_as(C.c_void_p))
         return rec
 
     def state(self):
         t, h = np.zeros(self.n), np.zeros(self.n)
         p, v = np.zeros((self.n, 3)), np.zeros((self.n, 3))
-        _check(self._L.eph_craft_batch_state(self._h, _p(t), _p(p), _p(v), _p(h)), "eph_craft_batch_state")
+        _call("eph_craft_batch_state", self._h, _p(t), _p(p), _p(v), _p(h))
         return dict(t=t, pos=p, vel=v, next_h=h)
 
     def knots(self, craft, nknots=None):
         nk = int(self.status()["nknots"][craft]) if nknots is None else int(nknots)
         t, p, v = np.zeros(nk), np.zeros((nk, 3)), np.zeros((nk, 3))
-        _check(self._L.eph_craft_batch_knots(self._h, int(craft), _p(t), _p(p), _p(v)), "eph_craft_batch_knots")
+        _call("eph_craft_batch_knots", self._h, int(craft), _p(t), _p(p), _p(v))
         return t, p, v
 
     def knot_slabs(self, first_knot=0, n_knots=None):
@@ -873,8 +619,7 @@ class SpacecraftBatch:
             n_knots = int(self.status()["nknots"].max()) - first_knot
         t = np.zeros((n_knots, self.n))
         y = np.zeros((n_knots, 6, self.n))
-        _check(self._L.eph_craft_batch_knot_slabs(self._h, int(first_knot), int(n_knots), _p(t), _p(y)),
-               "eph_craft_batch_knot_slabs")
+        _call("eph_craft_batch_knot_slabs", self._h, int(first_knot), int(n_knots), _p(t), _p(y))
         return t, y
 
     def eval(self, at, reference_body=-1, raw=False):
@@ -891,8 +636,7 @@ class SpacecraftBatch:
         m = at.shape[0]
         y = np.zeros((m, 6, self.n))
         inside = np.zeros((m, self.n), dtype=np.uint8)
-        _check(self._L.eph_craft_batch_eval(self._h, m, _p(at), 1 if at.ndim == 2 else 0, int(reference_body), _p(y),
-                                            _p(inside, _u8p)), "eph_craft_batch_eval")
+        _call("eph_craft_batch_eval", self._h, m, _p(at), 1 if at.ndim == 2 else 0, int(reference_body), _p(y), _p(inside, _u8p))
         inside = inside.astype(bool)
         if raw:
             return y, inside
@@ -903,27 +647,12 @@ class SpacecraftBatch:
         (None: plot p is craft p), read from the knot slabs on the device. view and requests as in plot_points(), the
         requests without source_body / knots (the source is the craft); one dict may be given for all plots.
         -> list of (status, failed_at, t[k], xyz[k, 3] float32), what plot_points() returns for the craft's knots."""
-        crafts = None if craft is None else np.ascontiguousarray(craft, dtype=np.int64).ravel()
-        if isinstance(requests, dict):
-            requests = [requests] * (self.n if crafts is None else len(crafts))
+        requests, (crafts,) = _per_request("SpacecraftBatch.plot_points: one craft per request", self.n, requests, craft)
         n = len(requests)
-        if crafts is not None and len(crafts) != n:
-            raise ValueError("SpacecraftBatch.plot_points: one craft per request")
-        v = _plot_view(view)
-        arr = (PlotRequest * max(n, 1))()
-        cap = 1
-        for i, r in enumerate(requests):
-            if "source_body" in r or "knots" in r:
-                raise ValueError("SpacecraftBatch.plot_points: the source is the craft (no source_body / knots)")
-            arr[i] = PlotRequest(-1, int(r.get("reference_body", -1)), 0, 0, float(r["start"]), float(r["end"]), int(r.get("bound", 0)),
-                                 int(r.get("enabled", 1)), float(r["tan2_angular_resolution"]), int(r["max_points"]))
-            cap = max(cap, int(r["max_points"]))
-        ot, ox = np.zeros((max(n, 1), cap)), np.zeros((max(n, 1), cap, 3), dtype=np.float32)
-        cnt, st, fail = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1))
-        _check(self._L.eph_craft_batch_plot_points(self._h, C.byref(v), n, arr, None if crafts is None else _p(crafts, _i64p), cap,
-                                                   _p(ot), ox.ctypes.data_as(C.POINTER(C.c_float)), _p(cnt, _i64p), _p(st, _i32p),
-                                                   _p(fail)), "eph_craft_batch_plot_points")
-        return [(int(st[i]), float(fail[i]), ot[i, :cnt[i]].copy(), ox[i, :cnt[i]].copy()) for i in range(n)]
+        arr, cap = _plot_requests(requests, craft_source=True)
+        out = _PlotOut(n, cap)
+        _call("eph_craft_batch_plot_points", self._h, C.byref(_plot_view(view)), n, arr, _p_or_null(crafts, _i64p), *out.args())
+        return out.rows(n)
 
     def closest_separation(self, requests, craft=None, target_craft=None):
         """The closest-separation search of target plotting on the batch's own knots (eph_craft_batch_closest_separation):
@@ -932,22 +661,12 @@ class SpacecraftBatch:
         requests: list of dict(target_body, left, right, precision, max_iterations, metric), or one dict for all.
         -> list of dict(found, time, distance, iterations, status, failed_at), what closest_separation() returns for the
         knots of the two craft."""
-        crafts = None if craft is None else np.ascontiguousarray(craft, dtype=np.int64).ravel()
-        targets = None if target_craft is None else np.ascontiguousarray(target_craft, dtype=np.int64).ravel()
-        if isinstance(requests, dict):
-            requests = [requests] * (self.n if crafts is None else len(crafts))
+        requests, (crafts, targets) = _per_request("SpacecraftBatch.closest_separation: one craft (and one target craft) per request",
+                                                   self.n, requests, craft, target_craft)
         n = len(requests)
-        if (crafts is not None and len(crafts) != n) or (targets is not None and len(targets) != n):
-            raise ValueError("SpacecraftBatch.closest_separation: one craft (and one target craft) per request")
-        arr = (SeparationRequest * max(n, 1))()
-        for i, r in enumerate(requests):
-            if "source_body" in r or "source_knots" in r or "target_knots" in r:
-                raise ValueError("SpacecraftBatch.closest_separation: source and target craft are the batch's (no source_body / knots)")
-            arr[i] = _separation_request(r)
         out = _SeparationOut(n)
-        _check(self._L.eph_craft_batch_closest_separation(self._h, n, arr, None if crafts is None else _p(crafts, _i64p),
-                                                          None if targets is None else _p(targets, _i64p), *out.args()),
-               "eph_craft_batch_closest_separation")
+        _call("eph_craft_batch_closest_separation", self._h, n, _separation_requests(requests, craft_source=True),
+              _p_or_null(crafts, _i64p), _p_or_null(targets, _i64p), *out.args())
         return out.rows(n)
 
     UNSELECTED = np.iinfo(np.int32).min     # restart(): the outcome entry of a craft `which` did not select (never written)
@@ -960,12 +679,6 @@ class SpacecraftBatch:
         an unselected craft's entries are NaN and UNSELECTED."""
         if len(burns) != self.n:
             raise ValueError("SpacecraftBatch.restart: one burn list per craft")
-        off = np.zeros(self.n + 1, dtype=np.int64)
-        flat = []
-        for i, bl in enumerate(burns):
-            flat.extend(bl)
-            off[i + 1] = len(flat)
-        _, bs, be, ba, br = _burn_arrays(flat)
         pe = None if plan_end is None else _f64(np.broadcast_to(np.asarray(plan_end, dtype=np.float64), (self.n,)))
         sel = None
         if which is not None:
@@ -977,33 +690,29 @@ class SpacecraftBatch:
                 sel[w.astype(np.int64)] = 1
         epoch = np.full(self.n, np.nan)
         outcome = np.full(self.n, self.UNSELECTED, dtype=np.int32)
-        _check(self._L.eph_craft_batch_restart(self._h, None if sel is None else _p(sel, _u8p), _p(off, _i64p), _p(bs), _p(be), _p(ba),
-                                               _p(br, _i32p), None if pe is None else _p(pe),
-                                               None if params is None else C.byref(params), _p(epoch), _p(outcome, _i32p)),
-               "eph_craft_batch_restart")
+        _call("eph_craft_batch_restart", self._h, _p_or_null(sel, _u8p), *_burn_csr(burns, self.n), _p_or_null(pe),
+              None if params is None else C.byref(params), _p(epoch), _p(outcome, _i32p))
         if params is not None:
             self.params = params
         return epoch, outcome
 
     def reset_knots(self):
         """Keep only the newest knot of every craft (as knot 0) and clear KNOTS_FULL: the drain point of a long run."""
-        _check(self._L.eph_craft_batch_reset_knots(self._h), "eph_craft_batch_reset_knots")
+        _call("eph_craft_batch_reset_knots", self._h)
 
     def reset_events(self):
         """Keep only the newest SOI transition of every craft, drop the apsides, clear EVENTS_FULL (after reading)."""
-        _check(self._L.eph_craft_batch_reset_events(self._h), "eph_craft_batch_reset_events")
+        _call("eph_craft_batch_reset_events", self._h)
 
     def enable_events(self, soi_radius, max_transitions=64, max_apsides=1024):
         """Switch to the app's SpacecraftSolout: SOI transitions + apsides per accepted step (call before propagate)."""
         r = _f64(soi_radius)
-        _check(self._L.eph_craft_batch_enable_events(self._h, _p(r), int(max_transitions), int(max_apsides)),
-               "eph_craft_batch_enable_events")
+        _call("eph_craft_batch_enable_events", self._h, _p(r), int(max_transitions), int(max_apsides))
         return self
 
     def event_counts(self):
         ntr, nap, st = (np.zeros(self.n, dtype=np.int32) for _ in range(3))
-        _check(self._L.eph_craft_batch_event_counts(self._h, _p(ntr, _i32p), _p(nap, _i32p), _p(st, _i32p)),
-               "eph_craft_batch_event_counts")
+        _call("eph_craft_batch_event_counts", self._h, _p(ntr, _i32p), _p(nap, _i32p), _p(st, _i32p))
         return ntr, nap, st
 
     def events(self, craft, counts=None):
@@ -1012,20 +721,14 @@ class SpacecraftBatch:
         a, b = max(int(ntr[craft]), 1), max(int(nap[craft]), 1)
         tt, tb = np.zeros(a), np.zeros(a, dtype=np.int32)
         at, ad, ab, ak = np.zeros(b), np.zeros(b), np.zeros(b, dtype=np.int32), np.zeros(b, dtype=np.int32)
-        _check(self._L.eph_craft_batch_events(self._h, int(craft), _p(tt), _p(tb, _i32p), _p(at), _p(ad),
-                                              _p(ab, _i32p), _p(ak, _i32p)), "eph_craft_batch_events")
+        _call("eph_craft_batch_events", self._h, int(craft), _p(tt), _p(tb, _i32p), _p(at), _p(ad), _p(ab, _i32p), _p(ak, _i32p))
         k, m = int(ntr[craft]), int(nap[craft])
         return (tt[:k], tb[:k]), (at[:m], ad[:m], ab[:m], ak[:m])
 
     def kernel_ms(self):
         ms = C.c_double()
-        _check(self._L.eph_craft_batch_kernel_time(self._h, C.byref(ms)), "eph_craft_batch_kernel_time")
+        _call("eph_craft_batch_kernel_time", self._h, C.byref(ms))
         return ms.value
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._L.eph_craft_batch_destroy(self._h)
-            self._h = None
 
 
 def _burn_arrays(burns):
@@ -1037,15 +740,46 @@ def _burn_arrays(burns):
     return n, bs, be, ba, br
 
 
+def _burn_args(burns):
+    """a list of burns as the C ABI takes it: count, start, end, acceleration, reference body"""
+    n, bs, be, ba, br = _burn_arrays(burns)
+    return n, _p(bs), _p(be), _p(ba), _p(br, _i32p)
+
+
+def _burn_csr(burns, n):
+    """n per-craft burn lists as the C ABI takes them: offsets[n + 1], then start / end / acceleration / reference body per burn"""
+    off = np.zeros(n + 1, dtype=np.int64)
+    flat = []
+    for i, bl in enumerate(burns):
+        flat.extend(bl)
+        off[i + 1] = len(flat)
+    return (_p(off, _i64p), *_burn_args(flat)[1:])
+
+
+def _knot_arrays(knots):
+    """a (t, pos, vel) knot triple, or None for no knots -> the C ABI's (count, t[k], pos[k][3], vel[k][3])"""
+    if knots is None:
+        knots = np.zeros(0), np.zeros((0, 3)), np.zeros((0, 3))
+    t, pos, vel = _f64(knots[0]).ravel(), _f64(knots[1]).reshape(-1, 3), _f64(knots[2]).reshape(-1, 3)
+    return len(t), _p(t), _p(pos), _p(vel)
+
+
+def _per_request(mismatch, n_craft, requests, *craft_lists):
+    """The conventions of the batch readers: one dict stands for all requests, and every optional craft index list has one
+    entry per request (ValueError(mismatch) otherwise) -> (requests, the lists as int64 arrays or None)."""
+    lists = [None if c is None else np.ascontiguousarray(c, dtype=np.int64).ravel() for c in craft_lists]
+    if isinstance(requests, dict):
+        requests = [requests] * (n_craft if lists[0] is None else len(lists[0]))
+    if any(c is not None and len(c) != len(requests) for c in lists):
+        raise ValueError(mismatch)
+    return requests, lists
+
+
 def timeline_divergence_time(old_burns, new_burns, before):
     """Timeline::divergence_time_before (spacecraft.rs:179-213) of new_burns against old_burns; burns are
     (start, end, acc[3], ref_body or -1). The epoch a flight plan restarts from (flight_plan.rs:263-303)."""
-    no, os_, oe, oa, or_ = _burn_arrays(list(old_burns))
-    nn, ns, ne, na, nr = _burn_arrays(list(new_burns))
     out = C.c_double()
-    _check(_lib().eph_timeline_divergence_time(no, _p(os_), _p(oe), _p(oa), _p(or_, _i32p), nn, _p(ns), _p(ne), _p(na),
-                                               _p(nr, _i32p), float(before), C.byref(out)),
-           "eph_timeline_divergence_time")
+    _call("eph_timeline_divergence_time", *_burn_args(list(old_burns)), *_burn_args(list(new_burns)), float(before), C.byref(out))
     return out.value
 
 
@@ -1055,8 +789,7 @@ def hermite_eval(t, pos, vel, at, with_velocity=True):
     m = len(at)
     op, ov = np.zeros((m, 3)), np.zeros((m, 3))
     inside = np.zeros(m, dtype=np.uint8)
-    _check(_lib().eph_hermite_eval(len(t), _p(t), _p(pos), _p(vel), m, _p(at), _p(op), _p(ov) if with_velocity else None,
-                                   _p(inside, _u8p)), "eph_hermite_eval")
+    _call("eph_hermite_eval", len(t), _p(t), _p(pos), _p(vel), m, _p(at), _p(op), _p(ov) if with_velocity else None, _p(inside, _u8p))
     return op, (ov if with_velocity else None), inside.astype(bool)
 
 
@@ -1078,39 +811,57 @@ def plot_points(ephemeris, view, requests, knots=None):
     requests: list of dict(source_body | knots=(first, count), reference_body, start, end, bound, enabled,
     tan2_angular_resolution, max_points); knots: (t, pos, vel) arrays the hermite sources index into.
     -> list of (status, failed_at, t[k], xyz[k, 3] float32)."""
-    v = PlotView()
-    v.camera_position[:] = [float(x) for x in view["camera_position"]]
-    m = np.asarray(view.get("grid_matrix3", np.eye(3)), dtype=np.float64)
-    v.grid_matrix3[:] = [float(m[r, c]) for c in range(3) for r in range(3)]          # column major
-    v.grid_translation[:] = [float(x) for x in view.get("grid_translation", (0.0, 0.0, 0.0))]
-    v.cell_offset[:] = [float(x) for x in view.get("cell_offset", (0.0, 0.0, 0.0))]
-    v.current = float(view["current"])
     n = len(requests)
-    arr = (PlotRequest * max(n, 1))()
+    arr, cap = _plot_requests(requests)
+    out = _PlotOut(n, cap)
+    _call("eph_plot_points", ephemeris._h, C.byref(_plot_view(view)), n, arr, *_knot_arrays(knots), *out.args())
+    return out.rows(n)
+
+
+def _plot_requests(requests, craft_source=False):
+    """-> (the eph_plot_request array, the point capacity the outputs need). craft_source: the batch's form, whose source is the
+    craft itself."""
+    arr = (PlotRequest * max(len(requests), 1))()
     cap = 1
     for i, r in enumerate(requests):
+        if craft_source and ("source_body" in r or "knots" in r):
+            raise ValueError("SpacecraftBatch.plot_points: the source is the craft (no source_body / knots)")
         first, count = r.get("knots", (0, 0))
         arr[i] = PlotRequest(int(r.get("source_body", -1)), int(r.get("reference_body", -1)), int(first), int(count),
                              float(r["start"]), float(r["end"]), int(r.get("bound", 0)), int(r.get("enabled", 1)),
                              float(r["tan2_angular_resolution"]), int(r["max_points"]))
         cap = max(cap, int(r["max_points"]))
-    kt, kp, kv = (np.zeros(0), np.zeros((0, 3)), np.zeros((0, 3))) if knots is None else (_f64(knots[0]).ravel(),
-                                                                                        _f64(knots[1]).reshape(-1, 3),
-                                                                                        _f64(knots[2]).reshape(-1, 3))
-    ot, ox = np.zeros((max(n, 1), cap)), np.zeros((max(n, 1), cap, 3), dtype=np.float32)
-    cnt, st, fail = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1))
-    _check(_lib().eph_plot_points(ephemeris._h, C.byref(v), n, arr, len(kt), _p(kt), _p(kp), _p(kv), cap, _p(ot),
-                                  ox.ctypes.data_as(C.POINTER(C.c_float)), _p(cnt, _i64p), _p(st, _i32p), _p(fail)),
-           "eph_plot_points")
-    return [(int(st[i]), float(fail[i]), ot[i, :cnt[i]].copy(), ox[i, :cnt[i]].copy()) for i in range(n)]
+    return arr, cap
 
 
-def _separation_request(r):
-    sf, sc = r.get("source_knots", (0, 0))
-    tf, tc = r.get("target_knots", (0, 0))
-    return SeparationRequest(int(r.get("source_body", -1)), int(r.get("target_body", -1)), int(sf), int(sc), int(tf), int(tc),
-                             float(r["left"]), float(r["right"]), float(r.get("precision", 0.001)), int(r.get("max_iterations", 1000)),
-                             int(r.get("metric", 0)))
+class _PlotOut:
+    """the point capacity and the five output arrays of the two plot calls"""
+
+    def __init__(self, n, cap):
+        m = max(n, 1)
+        self.cap, self.t, self.xyz = cap, np.zeros((m, cap)), np.zeros((m, cap, 3), dtype=np.float32)
+        self.count, self.status, self.failed_at = np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m)
+
+    def args(self):
+        return self.cap, _p(self.t), _p(self.xyz, _fp), _p(self.count, _i64p), _p(self.status, _i32p), _p(self.failed_at)
+
+    def rows(self, n):
+        return [(int(self.status[i]), float(self.failed_at[i]), self.t[i, :self.count[i]].copy(), self.xyz[i, :self.count[i]].copy())
+                for i in range(n)]
+
+
+def _separation_requests(requests, craft_source=False):
+    """-> the eph_separation_request array. craft_source: the batch's form, whose source and target craft are its own."""
+    arr = (SeparationRequest * max(len(requests), 1))()
+    for i, r in enumerate(requests):
+        if craft_source and ("source_body" in r or "source_knots" in r or "target_knots" in r):
+            raise ValueError("SpacecraftBatch.closest_separation: source and target craft are the batch's (no source_body / knots)")
+        sf, sc = r.get("source_knots", (0, 0))
+        tf, tc = r.get("target_knots", (0, 0))
+        arr[i] = SeparationRequest(int(r.get("source_body", -1)), int(r.get("target_body", -1)), int(sf), int(sc), int(tf), int(tc),
+                                   float(r["left"]), float(r["right"]), float(r.get("precision", 0.001)),
+                                   int(r.get("max_iterations", 1000)), int(r.get("metric", 0)))
+    return arr
 
 
 class _SeparationOut:
@@ -1138,27 +889,19 @@ def closest_separation(ephemeris, requests, knots=None):
     precision=0.001, max_iterations=1000, metric=0 (distance_squared_at) | 1 (distance_at)); knots: (t, pos, vel) arrays the
     Hermite trajectories index into. -> list of dict(found, time, distance, iterations, status, failed_at)."""
     n = len(requests)
-    arr = (SeparationRequest * max(n, 1))()
-    for i, r in enumerate(requests):
-        arr[i] = _separation_request(r)
-    kt, kp, kv = (np.zeros(0), np.zeros((0, 3)), np.zeros((0, 3))) if knots is None else (_f64(knots[0]).ravel(),
-                                                                                        _f64(knots[1]).reshape(-1, 3),
-                                                                                        _f64(knots[2]).reshape(-1, 3))
     out = _SeparationOut(n)
-    _check(_lib().eph_closest_separation(ephemeris._h, n, arr, len(kt), _p(kt), _p(kp), _p(kv), *out.args()), "eph_closest_separation")
+    _call("eph_closest_separation", ephemeris._h, n, _separation_requests(requests), *_knot_arrays(knots), *out.args())
     return out.rows(n)
 
 
 def hermite_join(lhs, rhs):
     """SpacecraftPropagator::join(lhs, rhs) (ephemeris/src/propagators/spacecraft.rs:558-561) on (t, pos, vel) knot
     arrays -> the joined (t, pos, vel). Host only."""
-    lt, lp, lv = _f64(lhs[0]).ravel(), _f64(lhs[1]).reshape(-1, 3), _f64(lhs[2]).reshape(-1, 3)
-    rt, rp, rv = _f64(rhs[0]).ravel(), _f64(rhs[1]).reshape(-1, 3), _f64(rhs[2]).reshape(-1, 3)
-    cap = len(lt) + len(rt)
+    lhs, rhs = _knot_arrays(lhs), _knot_arrays(rhs)
+    cap = lhs[0] + rhs[0]
     t, p, v = np.zeros(max(cap, 1)), np.zeros((max(cap, 1), 3)), np.zeros((max(cap, 1), 3))
     n = C.c_int64()
-    _check(_lib().eph_hermite_join(len(lt), _p(lt), _p(lp), _p(lv), len(rt), _p(rt), _p(rp), _p(rv), cap, _p(t), _p(p),
-                                   _p(v), C.byref(n)), "eph_hermite_join")
+    _call("eph_hermite_join", *lhs, *rhs, cap, _p(t), _p(p), _p(v), C.byref(n))
     return t[:n.value].copy(), p[:n.value].copy(), v[:n.value].copy()
 
 
@@ -1171,8 +914,8 @@ def transitions_join(lhs, rhs, at):
     cap = len(lt) + len(rt)
     t, b = np.zeros(max(cap, 1)), np.zeros(max(cap, 1), dtype=np.int32)
     n = C.c_int64()
-    _check(_lib().eph_transitions_join(len(lt), _p(lt), _p(lb, _i32p), len(rt), _p(rt), _p(rb, _i32p), float(at), cap, _p(t),
-                                       _p(b, _i32p), C.byref(n)), "eph_transitions_join")
+    _call("eph_transitions_join", len(lt), _p(lt), _p(lb, _i32p), len(rt), _p(rt), _p(rb, _i32p), float(at), cap, _p(t),
+          _p(b, _i32p), C.byref(n))
     return t[:n.value].copy(), b[:n.value].copy()
 
 
@@ -1188,7 +931,6 @@ def apsides_join(lhs, rhs, at):
     m = max(cap, 1)
     t, d, k, b = np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
     n = C.c_int64()
-    _check(_lib().eph_apsides_join(len(lt), _p(lt), _p(ld), _p(lk, _i32p), _p(lb, _i32p), len(rt), _p(rt), _p(rd), _p(rk, _i32p),
-                                   _p(rb, _i32p), float(at), cap, _p(t), _p(d), _p(k, _i32p), _p(b, _i32p), C.byref(n)),
-           "eph_apsides_join")
+    _call("eph_apsides_join", len(lt), _p(lt), _p(ld), _p(lk, _i32p), _p(lb, _i32p), len(rt), _p(rt), _p(rd), _p(rk, _i32p),
+          _p(rb, _i32p), float(at), cap, _p(t), _p(d), _p(k, _i32p), _p(b, _i32p), C.byref(n))
     return t[:n.value].copy(), d[:n.value].copy(), k[:n.value].copy(), b[:n.value].copy()

@@ -87,8 +87,7 @@ def run_live(system_dir, years=2.0, chunk_days=30.0, margin_days=40.0):
         try:
             ship = load_ship(path)
             try:
-                burns = [(b.start, b.start + b.duration, b.acceleration,
-                          system.names.index(b.reference) if b.reference else -1) for b in ship.burns]
+                burns = ship.burn_tuples(system.names)
             except ValueError as e:
                 slots[k] = (ship, None, None, f"burn reference not in this system: {e}")
                 return
@@ -157,8 +156,7 @@ def run(system_dir, years=2.0, backward=True):
     for path in ships:
         ship = load_ship(path)
         try:
-            burns = [(b.start, b.start + b.duration, b.acceleration,
-                      system.names.index(b.reference) if b.reference else -1) for b in ship.burns]
+            burns = ship.burn_tuples(system.names)
         except ValueError as e:
             r.ships.append((ship, None, None, f"burn reference not in this system: {e}"))
             continue

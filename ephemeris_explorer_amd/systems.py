@@ -186,6 +186,11 @@ class Ship:
     vel: np.ndarray
     burns: list
 
+    def burn_tuples(self, names):
+        """The burns as SpacecraftBatch (and the oracle's Craft) take them: (start, end, acceleration, index of the reference body in
+        `names` or -1 for an inertial burn). ValueError (list.index) for a reference that is not among `names`."""
+        return [(b.start, b.start + b.duration, b.acceleration, names.index(b.reference) if b.reference else -1) for b in self.burns]
+
 
 def load_ship(path):
     d = json.loads(Path(path).read_text())

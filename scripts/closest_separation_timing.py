@@ -173,7 +173,7 @@ def frame_case(args):
     eph = ea.Ephemeris(sol, s.mu)
     n = 8
     rng = np.random.default_rng(8)
-    burns = [(b.start, b.start + b.duration, b.acceleration, s.names.index(b.reference) if b.reference else -1) for b in ship.burns]
+    burns = ship.burn_tuples(s.names)
     batch = ea.SpacecraftBatch(eph, ship.start, ship.pos + rng.normal(0.0, 1.0, (n, 3)), np.tile(ship.vel, (n, 1)), ship.integrator,
                                ea.AdaptiveParams.default(ship.tolerance), [burns] * n, max_knots=20000)
     batch.propagate(parse_epoch("1951-01-01 00:00:00"))

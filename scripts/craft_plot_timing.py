@@ -150,7 +150,7 @@ def frame_case(args):
     sol = ea.NBodyPropagator.from_system(s).propagate(parse_epoch("1952-01-01 00:00:00"))
     eph = ea.Ephemeris(sol, s.mu)
     n = 8
-    burns = [(b.start, b.start + b.duration, b.acceleration, s.names.index(b.reference) if b.reference else -1) for b in ship.burns]
+    burns = ship.burn_tuples(s.names)
     batch = ea.SpacecraftBatch(eph, ship.start, np.tile(ship.pos, (n, 1)), np.tile(ship.vel, (n, 1)), ship.integrator,
                                ea.AdaptiveParams.default(ship.tolerance), [burns] * n, max_knots=20000)
     batch.propagate(parse_epoch("1951-01-01 00:00:00"))

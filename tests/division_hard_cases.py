@@ -12,12 +12,7 @@ puts a / p within |k| * 2^-106 / B (relative: about |k| 2^-107) of the midpoint 
 `hard_numerators(p)` solves these congruences; tests run them through the device sequence against IEEE division, and
 `emulate()` is the same sequence in exact rational arithmetic (checked here on the CPU for every case generated)."""
 import math
-import struct
 from fractions import Fraction
-
-
-def bits(x):
-    return struct.unpack("<Q", struct.pack("<d", x))[0]
 
 
 def p_of(x):

@@ -33,6 +33,46 @@ def test_library_exports_every_declared_symbol(product_lib):
     assert all(f[-2] == "T" for f in table), [f for f in table if f[-2] != "T"][:5]
 
 
+def header_prototypes():
+    """name -> (return type, [parameter declarations]) for every function include/ephemeris_amd.h declares"""
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "ephemeris_amd.h").read_text(), flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"^([\w \t*]+?)\b(eph_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        params = [" ".join(q.split()) for q in params.split(",")]
+        protos[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return protos
+
+
+def test_ctypes_signatures_match_the_header(product_lib):
+    """Every declared function is bound with the header's signature: as many argtypes as parameters, a pointer type wherever the
+    header has a pointer, an array or the callback, the exact fixed-width type for every scalar, and the declared kind of return."""
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64,
+               "double": ctypes.c_double}
+    protos = header_prototypes()
+    assert sorted(protos) == header_functions()
+    L = product_lib._lib()
+    for name, (ret, params) in protos.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, f"{name}: no argtypes"
+        assert len(fn.argtypes) == len(params), f"{name}: {len(fn.argtypes)} argtypes for {len(params)} parameters"
+        for k, (decl, ct) in enumerate(zip(params, fn.argtypes)):
+            if "*" in decl or "[" in decl or decl.split()[0] == "eph_exchange_fn":
+                assert ct in (ctypes.c_void_p, ctypes.c_char_p, product_lib.EXCHANGE_FN) or issubclass(ct, ctypes._Pointer), \
+                    f"{name} parameter {k} ({decl}): {ct} is not a pointer type"
+            else:
+                kind = [w for w in decl.split()[:-1] if w != "const"]
+                assert len(kind) == 1 and kind[0] in scalars, f"{name} parameter {k} ({decl}): a scalar type this test does not know"
+                assert ct is scalars[kind[0]], f"{name} parameter {k} ({decl}): {ct}"
+        if ret == "void":
+            assert fn.restype is None, name
+        elif ret == "const char *":
+            assert fn.restype is ctypes.c_char_p, name
+        elif ret == "eph_nbody *":
+            assert fn.restype is ctypes.c_void_p, name
+        else:
+            assert ret == "int32_t" and fn.restype in (ctypes.c_int32, ctypes.c_int), (name, ret, fn.restype)
+
+
 def test_code_object_is_gfx950(product_lib):
     blob = product_lib.LIB_PATH.read_bytes()
     assert b"gfx950" in blob and b"k_lm_step" in blob and b"k_lm_persistent" in blob

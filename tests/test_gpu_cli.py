@@ -6,13 +6,10 @@ import numpy as np
 import pytest
 
 from conftest import SYSTEMS
+from craft_cases import bits
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_cli_run_matches_the_restatement(gpu):

@@ -11,21 +11,15 @@ import numpy as np
 import pytest
 
 import closest_separation_restatement as cs
-from conftest import ROOT, SYSTEMS, load_system
+from conftest import ROOT, load_system
+from craft_cases import DAY, SHIP, bits, gathered_knots, perturbed, propagated, snapshot_of_slabs
 from ephemeris_explorer_amd.systems import load_ship, parse_epoch
 from oracle import orc
-from test_gpu_craft_plot import gathered_knots, perturbed, ship_burns, snapshot
 
 pytestmark = pytest.mark.gpu
 
-SHIP = SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json"
-DAY = 86400.0
 KEYS = ("found", "time", "distance", "iterations", "status", "failed_at")
 INF = math.inf
-
-
-def bits(x):
-    return np.float64(x).view(np.uint64)
 
 
 def same(a, b):
@@ -79,22 +73,11 @@ def host_driven():
     return mod.host_driven_search
 
 
-def propagated(gpu, name, end):
-    s = load_system(name)
-    sol = gpu.NBodyPropagator.from_system(s).propagate(end)
-    o = orc.Propagator(s.pos, s.vel, s.mu, s.epoch, s.dt, 1, s.count, s.degree)
-    assert o.step_to(end) == 0
-    osol = o.take_solution()
-    for b in range(s.n):
-        assert sol.info(b) == osol.info(b)
-    return s, gpu.Ephemeris(sol, s.mu), osol
-
-
 @pytest.fixture(scope="module")
 def scene(gpu):
     """simple_solar_system_2433282.5 to 1951-03-01; the Mars Transfer Ship without burns for 300 days (62 103 knots) and a perturbed
     second ship, in one batch of two (the wave form)"""
-    s, eph, osol = propagated(gpu, "simple_solar_system_2433282.5", parse_epoch("1951-03-01 00:00:00"))
+    s, _, eph, osol = propagated(gpu, "simple_solar_system_2433282.5", parse_epoch("1951-03-01 00:00:00"))
     ship = load_ship(SHIP)
     assert ship.start == s.epoch
     pos, vel = perturbed(ship, 2, 20261017)
@@ -151,7 +134,7 @@ def wave_case(gpu, scene):
     n = 6
     pos, vel = perturbed(ship, n, 31)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance),
-                                [ship_burns(ship, s.names)] * n, max_knots=20000)
+                                [ship.burn_tuples(s.names)] * n, max_knots=20000)
     batch.propagate(ship.start + 150 * DAY)
     st = batch.status()
     assert (st["status"] == 0).all()
@@ -200,7 +183,7 @@ def thread_case(gpu, scene):
     n = 16384
     pos, vel = perturbed(ship, n, 20261017)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance),
-                                [ship_burns(ship, s.names)] * n, max_knots=4096)
+                                [ship.burn_tuples(s.names)] * n, max_knots=4096)
     batch.propagate(ship.start + 1.5 * DAY)
     st = batch.status()
     assert (st["status"] == 0).all()
@@ -260,22 +243,22 @@ def test_the_batch_is_untouched(gpu, scene):
     s, eph, ship = scene["s"], scene["eph"], scene["ship"]
     n = 40
     pos, vel = perturbed(ship, n, 11)
-    burns = ship_burns(ship, s.names)
+    burns = ship.burn_tuples(s.names)
     mid, end = ship.start + 20 * DAY, ship.start + 30 * DAY
     a, b = (gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance), [burns] * n,
                                 max_knots=20000).enable_events(soi_radii(s)) for _ in range(2))
     a.propagate(mid)
     b.propagate(mid)
-    before = snapshot(a)
+    before = snapshot_of_slabs(a)
     crafts, targets, requests = mixed_requests(s, n, np.random.default_rng(4), 200, 20)
     got = a.closest_separation(requests, craft=crafts, target_craft=targets)
-    assert snapshot(a) == before == snapshot(b)
+    assert snapshot_of_slabs(a) == before == snapshot_of_slabs(b)
     assert_same(a.clone().closest_separation(requests, craft=crafts, target_craft=targets), got, "clone")
     assert_same(b.closest_separation(requests, craft=crafts, target_craft=targets), got, "the twin")
     assert sum(g["found"] for g in got) > 100
     a.propagate(end)
     b.propagate(end)
-    assert snapshot(a) == snapshot(b)
+    assert snapshot_of_slabs(a) == snapshot_of_slabs(b)
 
 
 def test_live_table(gpu):
@@ -296,7 +279,7 @@ def test_live_table(gpu):
     n = 6
     pos, vel = perturbed(ship, n, 81)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance),
-                                [ship_burns(ship, s.names)] * n, max_knots=20000)
+                                [ship.burn_tuples(s.names)] * n, max_knots=20000)
     batch.propagate(s.epoch + 150 * DAY)
     assert (batch.status()["status"] == 0).all()
     mars = s.names.index("Mars")

@@ -7,35 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import SYSTEMS, load_system
+from craft_cases import bits, simple_system  # noqa: F401  (the fixture)
 from ephemeris_explorer_amd.systems import load_ship, parse_epoch
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-@pytest.fixture(scope="module")
-def simple_system(gpu):
-    """10-body 1950 system, QuinlanTremaine12 6 h, two years of ephemeris: on the GPU and in the oracle (bit-identical,
-    test_gpu_parity.py), like ephemeris/tests/spacecraft_propagation.rs:401-409."""
-    s = load_system("simple_solar_system_2433282.5")
-    end = parse_epoch("1952-01-01 00:00:00")
-    g = gpu.NBodyPropagator.from_system(s)
-    sol = g.propagate(end)
-    o = orc.Propagator(s.pos, s.vel, s.mu, s.epoch, s.dt, 1, s.count, s.degree)
-    assert o.step_to(end) == 0
-    osol = o.take_solution()
-    for b in range(s.n):
-        assert sol.info(b) == osol.info(b)
-    return s, sol, gpu.Ephemeris(sol, s.mu), osol
-
-
-def ship_burns(ship, names):
-    return [(b.start, b.start + b.duration, b.acceleration, names.index(b.reference) if b.reference else -1)
-            for b in ship.burns]
 
 
 def compare_knots(g, o, what):
@@ -55,7 +31,7 @@ def test_mars_transfer_scenario(gpu, simple_system):
     Earth / Sun / Mars TNB frames; asserts of ephemeris/tests/spacecraft_propagation.rs:476-480."""
     s, sol, eph, osol = simple_system
     ship = load_ship(SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json")
-    burns = ship_burns(ship, s.names)
+    burns = ship.burn_tuples(s.names)
     end = parse_epoch("1951-01-01 00:00:00")
     params = gpu.AdaptiveParams.default(ship.tolerance)
     batch = gpu.SpacecraftBatch(eph, ship.start, [ship.pos], [ship.vel], ship.integrator, params, [burns], max_knots=20000)
@@ -89,7 +65,7 @@ def test_mars_transfer_scenario(gpu, simple_system):
 def test_every_embedded_pair(gpu, simple_system, method):
     s, sol, eph, osol = simple_system
     ship = load_ship(SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json")
-    burns = ship_burns(ship, s.names)[:2]
+    burns = ship.burn_tuples(s.names)[:2]
     end = ship.start + 3 * 86400.0
     batch = gpu.SpacecraftBatch(eph, ship.start, [ship.pos], [ship.vel], method, gpu.AdaptiveParams.default(1e-3),
                                 [burns], max_knots=20000)
@@ -106,7 +82,7 @@ def test_erkn_tsitouras75nystrom(gpu, simple_system):
     to the oracle's separate restatement of ERKN::advance. Both kernel forms (one wave per craft / thread per craft)."""
     s, sol, eph, osol = simple_system
     ship = load_ship(SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json")
-    relative = ship_burns(ship, s.names)[:2]
+    relative = ship.burn_tuples(s.names)[:2]
     inertial = [(b0, b1, acc, -1) for b0, b1, acc, _ in relative]
     end = ship.start + 3 * 86400.0
     with pytest.raises(gpu.EphemerisError):                    # a TNB burn needs the velocity: not a SecondOrderODE
@@ -132,7 +108,7 @@ def test_batch_of_perturbed_craft_and_resume(gpu, simple_system):
     n = 96
     pos = ship.pos + rng.normal(0.0, 100.0, size=(n, 3))
     vel = ship.vel + rng.normal(0.0, 0.01, size=(n, 3))
-    burns = [ship_burns(ship, s.names)[:1] if i % 3 == 0 else [] for i in range(n)]
+    burns = [ship.burn_tuples(s.names)[:1] if i % 3 == 0 else [] for i in range(n)]
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, "Verner87", burns=burns, max_knots=8192)
     mid, end = ship.start + 2 * 86400.0, ship.start + 5 * 86400.0   # low Earth orbit: ~50 accepted steps per revolution
     batch.propagate(mid)            # step_to(mid), then resume to `end`: same knots as going straight through
@@ -153,7 +129,7 @@ def test_errors_are_per_craft_values(gpu, simple_system):
     # craft 1 runs past the end of the ephemeris -> EvalFailed (spacecraft.rs:264-281); craft 0 is fine;
     # craft 2 fills its knot slab
     far = parse_epoch("1953-01-01 00:00:00")
-    burns = ship_burns(ship, s.names)          # the transfer leaves Earth orbit, so steps grow to hours
+    burns = ship.burn_tuples(s.names)          # the transfer leaves Earth orbit, so steps grow to hours
     batch = gpu.SpacecraftBatch(eph, ship.start, [ship.pos] * 2, [ship.vel] * 2, "Verner87", burns=[burns, burns],
                                 max_knots=100000)
     batch.propagate(ship.start + 86400.0)
@@ -221,7 +197,7 @@ def test_spacecraft_solout_events(gpu, simple_system):
     s, sol, eph, osol = simple_system
     soi = soi_radii(s)
     ship = load_ship(SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json")
-    burns = ship_burns(ship, s.names)
+    burns = ship.burn_tuples(s.names)
     end = parse_epoch("1951-01-01 00:00:00")
     params = gpu.AdaptiveParams.default(ship.tolerance)
     c = orc.Craft(osol, s.mu, ship.start, ship.pos, ship.vel, ship.integrator, tol_pos=ship.tolerance,
@@ -488,7 +464,7 @@ def test_committed_spacecraft_knots(gpu, simple_system, method):
     gm = json.loads((GOLDEN / "craft_golden.json").read_text())["methods"][method]
     ship = load_ship(SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json")
     batch = gpu.SpacecraftBatch(eph, ship.start, [ship.pos], [ship.vel], method, gpu.AdaptiveParams.default(ship.tolerance),
-                                [ship_burns(ship, s.names)], max_knots=40000).enable_events(soi_radii(s), 16, 8192)
+                                [ship.burn_tuples(s.names)], max_knots=40000).enable_events(soi_radii(s), 16, 8192)
     batch.propagate(parse_epoch("1951-01-01 00:00:00"))
     st = batch.status()
     assert st["status"][0] == 0
@@ -511,7 +487,7 @@ def test_single_steps(gpu, simple_system):
     across burn boundaries, equal to the oracle's step(); then step_n(25) == 25 x step()."""
     s, sol, eph, osol = simple_system
     ship = load_ship(SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json")
-    burns = ship_burns(ship, s.names)
+    burns = ship.burn_tuples(s.names)
     batch = gpu.SpacecraftBatch(eph, ship.start, [ship.pos, ship.pos + 10.0], [ship.vel, ship.vel], "Verner87",
                                 burns=[burns, []], max_knots=256)
     cs = [orc.Craft(osol, s.mu, ship.start, ship.pos, ship.vel, "Verner87", burns=burns),

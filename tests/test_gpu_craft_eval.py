@@ -9,45 +9,13 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, SYSTEMS, load_system
+from conftest import ROOT, load_system
+from craft_cases import SHIP, bits, perturbed, simple_system  # noqa: F401  (the fixture)
 from ephemeris_explorer_amd.systems import load_ship, parse_epoch
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
 
-SHIP = SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json"
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def ship_burns(ship, names):
-    return [(b.start, b.start + b.duration, b.acceleration, names.index(b.reference) if b.reference else -1)
-            for b in ship.burns]
-
-
-@pytest.fixture(scope="module")
-def simple_system(gpu):
-    """10-body 1950 system, QuinlanTremaine12 6 h, two years of ephemeris: on the GPU and in the oracle (as test_gpu_craft.py)."""
-    s = load_system("simple_solar_system_2433282.5")
-    end = parse_epoch("1952-01-01 00:00:00")
-    sol = gpu.NBodyPropagator.from_system(s).propagate(end)
-    o = orc.Propagator(s.pos, s.vel, s.mu, s.epoch, s.dt, 1, s.count, s.degree)
-    assert o.step_to(end) == 0
-    osol = o.take_solution()
-    for b in range(s.n):
-        assert sol.info(b) == osol.info(b)
-    return s, sol, gpu.Ephemeris(sol, s.mu), osol
-
-
-def perturbed(ship, n, seed):
-    """craft 0 is the ship itself; the others differ by normal(0, 1 km / 1e-4 km/s) per component"""
-    rng = np.random.default_rng(seed)
-    pos = ship.pos + rng.normal(0.0, 1.0, size=(n, 3))
-    vel = ship.vel + rng.normal(0.0, 1e-4, size=(n, 3))
-    pos[0], vel[0] = ship.pos, ship.vel
-    return pos, vel
 
 
 def shared_epochs(t0, t_end, knots0, seed):
@@ -115,7 +83,7 @@ def wave_case(gpu, simple_system):
     ship = load_ship(SHIP)
     n = 192
     pos, vel = perturbed(ship, n, 20261016)
-    burns = ship_burns(ship, s.names)
+    burns = ship.burn_tuples(s.names)
     end = parse_epoch("1951-01-01 00:00:00")
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance), [burns] * n,
                                 max_knots=20000)
@@ -135,7 +103,7 @@ def thread_case(gpu, simple_system):
     ship = load_ship(SHIP)
     n = 16384
     pos, vel = perturbed(ship, n, 20261017)
-    burns = ship_burns(ship, s.names)
+    burns = ship.burn_tuples(s.names)
     end = ship.start + 220 * 86400.0
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance), [burns] * n,
                                 max_knots=4096)
@@ -294,7 +262,7 @@ def test_eval_does_not_disturb_the_batch(gpu, simple_system):
     ship = load_ship(SHIP)
     n = 200
     pos, vel = perturbed(ship, n, 11)
-    burns = [ship_burns(ship, s.names)[:2]] * n
+    burns = [ship.burn_tuples(s.names)[:2]] * n
     mid, end = ship.start + 1.5 * 86400.0, ship.start + 3 * 86400.0
     a, b = (gpu.SpacecraftBatch(eph, ship.start, pos, vel, "Verner87", burns=burns, max_knots=2048).enable_events(soi_radii(s), 16, 512)
             for _ in range(2))

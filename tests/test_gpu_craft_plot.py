@@ -1,5 +1,5 @@
 """-m gpu: eph_craft_batch_plot_points -- the adaptive plot sampler on the knot slabs of a spacecraft batch -- against the Python
-restatement of compute_plot_points_parallel / PlotPoints::new (oracle_plot of test_gpu_plot.py, evaluations by the C oracle) on the
+restatement of compute_plot_points_parallel / PlotPoints::new (oracle_plot of craft_cases.py, evaluations by the C oracle) on the
 knots batch.knots(c) returns, and against eph_plot_points fed with those knots. Every comparison is on bit patterns (u64 epochs,
 u32 points); there is no tolerance anywhere."""
 import ctypes as C
@@ -7,32 +7,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from conftest import SYSTEMS, load_system
+from conftest import load_system
+from craft_cases import DAY, SHIP, gathered_knots, oracle_plot, perturbed, simple_system, snapshot_of_slabs  # noqa: F401  (the fixture)
 from ephemeris_explorer_amd.systems import load_ship, parse_epoch
 from oracle import orc
-from test_gpu_plot import oracle_plot
 
 pytestmark = pytest.mark.gpu
 
-SHIP = SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json"
-DAY = 86400.0
 RES = float(np.float32(1.0) * np.float32(0.000290888) * np.float32(0.7853982))          # threshold * ARC_MINUTE * fov
 ROT = np.array([[0.36, 0.48, -0.8], [-0.8, 0.6, 0.0], [0.48, 0.64, 0.6]])
 N_DRAWING = 5                                                                           # the first five requests of requests_for()
 CAPPED = 4
-
-
-def ship_burns(ship, names):
-    return [(b.start, b.start + b.duration, b.acceleration, names.index(b.reference) if b.reference else -1) for b in ship.burns]
-
-
-def perturbed(ship, n, seed):
-    """craft 0 is the ship itself; the others differ by normal(0, 1 km / 1e-4 km/s) per component"""
-    rng = np.random.default_rng(seed)
-    pos = ship.pos + rng.normal(0.0, 1.0, size=(n, 3))
-    vel = ship.vel + rng.normal(0.0, 1e-4, size=(n, 3))
-    pos[0], vel[0] = ship.pos, ship.vel
-    return pos, vel
 
 
 def views_for(t0):
@@ -91,20 +76,6 @@ def by_plot_points(gpu, eph, batch, crafts, view, requests):
 
 
 @pytest.fixture(scope="module")
-def simple_system(gpu):
-    """10-body 1950 system, QuinlanTremaine12 6 h, two years of ephemeris: on the GPU and in the oracle (as test_gpu_craft_eval.py)"""
-    s = load_system("simple_solar_system_2433282.5")
-    end = parse_epoch("1952-01-01 00:00:00")
-    sol = gpu.NBodyPropagator.from_system(s).propagate(end)
-    o = orc.Propagator(s.pos, s.vel, s.mu, s.epoch, s.dt, 1, s.count, s.degree)
-    assert o.step_to(end) == 0
-    osol = o.take_solution()
-    for b in range(s.n):
-        assert sol.info(b) == osol.info(b)
-    return s, sol, gpu.Ephemeris(sol, s.mu), osol
-
-
-@pytest.fixture(scope="module")
 def thread_case(gpu, simple_system):
     """the thread form with dealt lanes: 16 384 perturbed copies over the first 220 days (all four burns), max_knots = 4096"""
     s, sol, eph, osol = simple_system
@@ -112,7 +83,7 @@ def thread_case(gpu, simple_system):
     n = 16384
     pos, vel = perturbed(ship, n, 20261017)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance),
-                                [ship_burns(ship, s.names)] * n, max_knots=4096)
+                                [ship.burn_tuples(s.names)] * n, max_knots=4096)
     batch.propagate(ship.start + 220 * DAY)
     st = batch.status()
     assert np.isin(st["status"], (0, gpu.KNOTS_FULL)).all() and st["status"][0] == 0
@@ -127,7 +98,7 @@ def test_wave_form_every_plot_against_the_restatement(gpu, simple_system):
     assert ship.start == s.epoch
     pos, vel = perturbed(ship, n, 20261016)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance),
-                                [ship_burns(ship, s.names)] * n, max_knots=20000)
+                                [ship.burn_tuples(s.names)] * n, max_knots=20000)
     batch.propagate(parse_epoch("1951-01-01 00:00:00"))
     st = batch.status()
     assert (st["status"] == 0).all()
@@ -153,27 +124,6 @@ def test_wave_form_every_plot_against_the_restatement(gpu, simple_system):
                 done += 1
     assert done == 2 * len(requests) * n                                                # no plot is left out
     assert cut > 0                                                                      # the cap does cut
-
-
-def gathered_knots(batch, nknots):
-    """every craft's knots as eph_plot_points wants them -- concatenated [knot] / [knot][3] arrays with (first, count) per craft --
-    from one bulk read of the slab's first rows plus one eph_craft_batch_knots call for each of the few long craft"""
-    n = batch.n
-    rows = min(int(nknots.max()), 512)
-    t, y = batch.knot_slabs(0, rows)
-    live = (np.arange(rows)[None, :] < nknots[:, None])                                 # [craft][k]
-    first = np.concatenate([[0], np.cumsum(nknots)[:-1]]).astype(np.int64)
-    kt, kp, kv = np.zeros(int(nknots.sum())), np.zeros((int(nknots.sum()), 3)), np.zeros((int(nknots.sum()), 3))
-    short = nknots <= rows
-    dest = (first[:, None] + np.arange(rows)[None, :])[live & short[:, None]]
-    yt = y.transpose(2, 0, 1)                                                           # [craft][k][6]
-    kt[dest] = t.T[live & short[:, None]]
-    kp[dest] = yt[live & short[:, None]][:, :3]
-    kv[dest] = yt[live & short[:, None]][:, 3:]
-    for c in np.flatnonzero(~short):
-        ct, cp, cv = batch.knots(int(c), nknots[c])
-        kt[first[c]:first[c] + nknots[c]], kp[first[c]:first[c] + nknots[c]], kv[first[c]:first[c] + nknots[c]] = ct, cp, cv
-    return (kt, kp, kv), first, nknots.astype(np.int64)
 
 
 def test_thread_form_dealt_lanes(gpu, simple_system, thread_case):
@@ -239,16 +189,6 @@ def test_more_than_one_pass(gpu, simple_system, thread_case):
     assert_same_plots(whole, parts, "multi-pass")
 
 
-def snapshot(batch):
-    rec = batch.summary()
-    t, y = batch.knot_slabs()
-    live = np.arange(t.shape[0])[:, None] < rec["nknots"][None, :]
-    counts = batch.event_counts()
-    ev = [batch.events(c, counts) for c in range(batch.n)]
-    return (rec.tobytes(), t[live].tobytes(), y[np.broadcast_to(live[:, None, :], y.shape)].tobytes(), [np.asarray(x).tobytes() for x in counts],
-            [np.asarray(a).tobytes() for e in ev for part in e for a in part])
-
-
 def test_the_batch_is_untouched(gpu, simple_system):
     """4. summary, knot slabs, events and a following propagate are bit-equal with and without a plot call in between; a clone plots the
     same; after reset_knots and after a restart of a subset the plot is eph_plot_points on the new knots; one knot draws nothing"""
@@ -257,7 +197,7 @@ def test_the_batch_is_untouched(gpu, simple_system):
     ship = load_ship(SHIP)
     n = 40
     pos, vel = perturbed(ship, n, 11)
-    burns = ship_burns(ship, s.names)
+    burns = ship.burn_tuples(s.names)
     requests = requests_for(s)
     view = views_for(s.epoch)[1]
     mid, end = ship.start + 60 * DAY, ship.start + 80 * DAY
@@ -267,15 +207,15 @@ def test_the_batch_is_untouched(gpu, simple_system):
     assert all(g[0] == 0 and len(g[2]) == 0 for g in fresh)
     a.propagate(mid)
     b.propagate(mid)
-    before = snapshot(a)
+    before = snapshot_of_slabs(a)
     crafts = np.repeat(np.arange(n), len(requests))
     got = a.plot_points(view, requests * n, craft=crafts)
-    assert snapshot(a) == before == snapshot(b)
+    assert snapshot_of_slabs(a) == before == snapshot_of_slabs(b)
     assert_same_plots(got, by_plot_points(gpu, eph, a, crafts, view, requests * n), "before")
     assert_same_plots(a.clone().plot_points(view, requests * n, craft=crafts), got, "clone")
     a.propagate(end)
     b.propagate(end)
-    assert snapshot(a) == snapshot(b)
+    assert snapshot_of_slabs(a) == snapshot_of_slabs(b)
     # a restart of a subset: the selected craft's plots follow their new knots
     news = [list(burns) for _ in range(n)]
     sel = np.arange(n) % 3 == 0
@@ -322,7 +262,7 @@ def test_live_table(gpu):
     n = 6
     pos, vel = perturbed(ship, n, 81)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, gpu.AdaptiveParams.default(ship.tolerance),
-                                [ship_burns(ship, s.names)] * n, max_knots=20000)
+                                [ship.burn_tuples(s.names)] * n, max_knots=20000)
     batch.propagate(s.epoch + 150 * DAY)
     assert (batch.status()["status"] == 0).all()
     earth = s.names.index("Earth")

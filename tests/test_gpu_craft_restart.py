@@ -10,30 +10,17 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, SYSTEMS, load_system
+from conftest import ROOT, load_system
+from craft_cases import DAY, SHIP, bits, perturbed, same, simple_system, snapshot_of_knots  # noqa: F401  (the fixture)
 from ephemeris_explorer_amd.systems import load_ship, parse_epoch, soi_radii
 from oracle import orc
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
-SHIP = SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json"
-DAY = 86400.0
 T1 = parse_epoch("1950-08-01 00:00:00")
 T2 = parse_epoch("1950-08-20 00:00:00")
 EVENTS_FULL = 7
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def ship_burns(ship, names):
-    return [(b.start, b.start + b.duration, b.acceleration, names.index(b.reference) if b.reference else -1) for b in ship.burns]
 
 
 def edit(burns, e):
@@ -57,15 +44,6 @@ def edits(burns, n):
     plans = [edit(burns, c % 6) for c in range(n)]
     ends = np.array([np.inf if p[1] is None else p[1] for p in plans])
     return [p[0] for p in plans], ends
-
-
-def perturbed(ship, n, seed):
-    """craft 0 is the ship itself; the others differ by normal(0, 1 km / 1e-4 km/s) per component"""
-    rng = np.random.default_rng(seed)
-    pos = ship.pos + rng.normal(0.0, 1.0, size=(n, 3))
-    vel = ship.vel + rng.normal(0.0, 1e-4, size=(n, 3))
-    pos[0], vel[0] = ship.pos, ship.vel
-    return pos, vel
 
 
 def restart_epoch(kt, old, new, plan_end, params_changed=False):
@@ -139,19 +117,6 @@ def raw(a):
     return np.ascontiguousarray(a).view(np.uint8)
 
 
-def snapshot(batch):
-    """everything a restart may change: the summary records, every craft's knots and (if enabled) event lists"""
-    rec = batch.summary().tobytes()
-    nk = batch.status()["nknots"]
-    kn = [tuple(bits(x).tobytes() for x in batch.knots(c, nk[c])) for c in range(batch.n)]
-    try:
-        counts = batch.event_counts()
-    except Exception:
-        return rec, kn, None
-    ev = [tuple(np.asarray(x).tobytes() for part in batch.events(c, counts) for x in part) for c in range(batch.n)]
-    return rec, kn, (tuple(x.tobytes() for x in counts), ev)
-
-
 def restart_epochs_pyoracle(batch, crafts, old, news, ends):
     """restart_epoch per craft from the batch's own (undrained) knots and pyoracle"""
     out = []
@@ -159,20 +124,6 @@ def restart_epochs_pyoracle(batch, crafts, old, news, ends):
         kt = batch.knots(int(c))[0]
         out.append(restart_epoch(kt, old, news[c], ends[c]))
     return np.array(out)
-
-
-@pytest.fixture(scope="module")
-def simple_system(gpu):
-    """10-body 1950 system, QuinlanTremaine12 6 h, two years of ephemeris: on the GPU and in the oracle (as test_gpu_craft.py)."""
-    s = load_system("simple_solar_system_2433282.5")
-    end = parse_epoch("1952-01-01 00:00:00")
-    sol = gpu.NBodyPropagator.from_system(s).propagate(end)
-    o = orc.Propagator(s.pos, s.vel, s.mu, s.epoch, s.dt, 1, s.count, s.degree)
-    assert o.step_to(end) == 0
-    osol = o.take_solution()
-    for b in range(s.n):
-        assert sol.info(b) == osol.info(b)
-    return s, sol, gpu.Ephemeris(sol, s.mu), osol
 
 
 def test_wave_form_with_events(gpu, simple_system):
@@ -183,7 +134,7 @@ def test_wave_form_with_events(gpu, simple_system):
     soi = soi_radii(s)
     n = 192
     pos, vel = perturbed(ship, n, 20261016)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     news, ends = edits(old, n)
     params = gpu.AdaptiveParams.default(ship.tolerance)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, params, [old] * n, max_knots=20000).enable_events(soi)
@@ -214,7 +165,7 @@ def test_thread_form_dealt_lanes(gpu, simple_system):
     ship = load_ship(SHIP)
     n = 16384
     pos, vel = perturbed(ship, n, 20261017)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     news, ends = edits(old, n)
     params = gpu.AdaptiveParams.default(ship.tolerance)
     t1 = ship.start + 220 * DAY
@@ -264,7 +215,7 @@ def test_fsal_and_nystrom_forms(gpu, simple_system, method):
     ship = load_ship(SHIP)
     n = 12
     pos, vel = perturbed(ship, n, 31)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     news, ends = edits(old, n)
     params = gpu.AdaptiveParams.default(ship.tolerance)
     t1, t2 = ship.start + 70 * DAY, ship.start + 75 * DAY
@@ -288,7 +239,7 @@ def test_subset_and_clones(gpu, simple_system):
     soi = soi_radii(s)
     n = 30
     pos, vel = perturbed(ship, n, 41)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     news, ends = edits(old, n)
     params = gpu.AdaptiveParams.default(ship.tolerance)
     t1, t2 = ship.start + 70 * DAY, ship.start + 90 * DAY
@@ -296,13 +247,13 @@ def test_subset_and_clones(gpu, simple_system):
     batch.propagate(t1)
     keep = batch.clone()
     other = batch.clone()
-    before = snapshot(batch)
+    before = snapshot_of_knots(batch)
     # a clone restarted: the original is unchanged
     scratch = batch.clone()
     e_all, o_all = scratch.restart(news, plan_end=ends)
     assert (o_all == 0).all()
     del scratch
-    assert snapshot(batch) == before
+    assert snapshot_of_knots(batch) == before
     sel = np.arange(n) % 3 == 0
     epoch, outcome = batch.restart(news, plan_end=ends, which=sel)
     assert (outcome[sel] == 0).all() and (outcome[~sel] == gpu.SpacecraftBatch.UNSELECTED).all()
@@ -333,7 +284,7 @@ def test_drains(gpu, simple_system):
     soi = soi_radii(s)
     n = 6
     pos, vel = perturbed(ship, n, 51)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     params = gpu.AdaptiveParams.default(ship.tolerance)
     plan3 = [edit(old, 3)[0]] * n
     a = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, params, [old] * n, max_knots=20000).enable_events(soi)
@@ -341,14 +292,14 @@ def test_drains(gpu, simple_system):
     full_knots = [a.knots(c)[0] for c in range(n)]
     a.reset_knots()
     keep = a.clone()
-    before = snapshot(a)
+    before = snapshot_of_knots(a)
     epoch, outcome = a.restart(plan3)
     assert (outcome == gpu.EVAL_FAILED).all()
     assert same(epoch, [restart_epoch(full_knots[c], old, plan3[c], np.inf) for c in range(n)])
-    assert snapshot(a) == before
+    assert snapshot_of_knots(a) == before
     a.propagate(T1 + 2 * DAY)
     keep.propagate(T1 + 2 * DAY)
-    assert snapshot(a) == snapshot(keep)
+    assert snapshot_of_knots(a) == snapshot_of_knots(keep)
     # (b)
     plan1 = [edit(old, 1)[0]] * n
     b = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, params, [old] * n, max_knots=20000)
@@ -379,7 +330,7 @@ def test_events_lagging(gpu, simple_system):
     soi = soi_radii(s)
     n = 8
     pos, vel = perturbed(ship, n, 20261016)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     plan0 = [edit(old, 0)[0]] * n
     params = gpu.AdaptiveParams.default(ship.tolerance)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, params, [old] * n,
@@ -387,10 +338,10 @@ def test_events_lagging(gpu, simple_system):
     batch.propagate(T1)
     ntr, nap, est = batch.event_counts()
     assert (est == EVENTS_FULL).all() and (ntr == 2).all()
-    before = snapshot(batch)
+    before = snapshot_of_knots(batch)
     epoch, outcome = batch.restart(plan0)
     assert (outcome == EVENTS_FULL).all()
-    assert snapshot(batch) == before
+    assert snapshot_of_knots(batch) == before
     hist = [([], []) for _ in range(n)]                     # the caller's event history: (transitions, apsides) per craft
 
     def absorb():
@@ -440,7 +391,7 @@ def test_parameter_change(gpu, simple_system):
     ship = load_ship(SHIP)
     n = 12
     pos, vel = perturbed(ship, n, 71)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     news, ends = edits(old, n)
     params, tighter = gpu.AdaptiveParams.default(ship.tolerance), gpu.AdaptiveParams.default(5e-4)
     t1, t2 = ship.start + 62 * DAY, ship.start + 66 * DAY
@@ -483,7 +434,7 @@ def test_live_table_flow(gpu, simple_system):
     eph, olive = gpu.Ephemeris(pieces[0][0], s.mu), pieces[0][1].clone()
     n = 6
     pos, vel = perturbed(ship, n, 81)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     news, ends = edits(old, n)
     params = gpu.AdaptiveParams.default(ship.tolerance)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, params, [old] * n, max_knots=20000)
@@ -516,12 +467,12 @@ def test_refusals_and_edge_cases(gpu, simple_system):
     soi = soi_radii(s)
     n = 6
     pos, vel = perturbed(ship, n, 91)
-    old = ship_burns(ship, s.names)
+    old = ship.burn_tuples(s.names)
     news, ends = edits(old, n)
     params = gpu.AdaptiveParams.default(ship.tolerance)
     batch = gpu.SpacecraftBatch(eph, ship.start, pos, vel, ship.integrator, params, [old] * n, max_knots=4096).enable_events(soi)
     batch.propagate(ship.start + DAY)
-    before = snapshot(batch)
+    before = snapshot_of_knots(batch)
     L, h = batch._L, batch._h
     dp, i32p, i64p, u8p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
     off = np.array([0, 1, 2, 3, 4, 5, 6], dtype=np.int64)
@@ -544,17 +495,17 @@ def test_refusals_and_edge_cases(gpu, simple_system):
     assert call(r=np.array([-1, -2, -1, -1, -1, -1], dtype=np.int32)) == bad
     assert call(w=which, pr=tighter) == bad                                     # params belong to the whole batch
     assert (epoch == -7.25).all() and (outcome == 0x5A5A).all()
-    assert snapshot(batch) == before
+    assert snapshot_of_knots(batch) == before
     assert batch.params.tol_position == ship.tolerance
     # Tsitouras75Nystrom: inertial burns only, as at creation
     inertial = [[(b[0], b[1], b[2], -1) for b in old]] * n
     ny = gpu.SpacecraftBatch(eph, ship.start, pos, vel, "Tsitouras75Nystrom", params, inertial, max_knots=4096)
     ny.propagate(ship.start + 3600.0)
-    nbefore = snapshot(ny)
+    nbefore = snapshot_of_knots(ny)
     with pytest.raises(gpu.EphemerisError) as e:
         ny.restart([old] * n)
     assert e.value.status == gpu.ERR_UNSUPPORTED
-    assert snapshot(ny) == nbefore
+    assert snapshot_of_knots(ny) == nbefore
     # an empty batch
     empty = gpu.SpacecraftBatch(eph, ship.start, np.zeros((0, 3)), np.zeros((0, 3)), ship.integrator, params)
     e0, o0 = empty.restart([])
@@ -567,7 +518,7 @@ def test_refusals_and_edge_cases(gpu, simple_system):
     t = ship.start + 70 * DAY
     fresh_old.propagate(t)
     created.propagate(t)
-    assert snapshot(fresh_old) == snapshot(created)
+    assert snapshot_of_knots(fresh_old) == snapshot_of_knots(created)
 
 
 def test_cpp_example_prints_the_python_calls_bits(gpu, tmp_path):

@@ -26,18 +26,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, SYSTEMS, load_system
+from craft_cases import bits, same
 from ephemeris_explorer_amd.systems import load_ship, parse_epoch
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def random_system(n, seed):

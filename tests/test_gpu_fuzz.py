@@ -12,18 +12,11 @@ import numpy as np
 import pytest
 
 from conftest import SYSTEMS, load_system
+from craft_cases import bits, same
 from ephemeris_explorer_amd.systems import load_ship
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 FIXED_METHODS = ["QuinlanTremaine12", "Stormer13", "BlanesMoan6B", "BlanesMoan11B", "BlanesMoan14A", "ForestRuth", "McLachlanO4",

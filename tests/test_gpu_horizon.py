@@ -15,15 +15,12 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from craft_cases import bits
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
 H = 1.0 / 1024.0
 AU_KM = 1.495978707e8
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def sha(a):

@@ -20,20 +20,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, SYSTEMS, load_system
+from craft_cases import bits, same
 from ephemeris_explorer_amd.systems import load_ship, soi_radii
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
 DAY = 86400.0
 METHODS = ["Verner87", "DormandPrince54", "Fine45"]          # no FSAL | FSAL | FSAL on SecondOrderState (ERKNG)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 @pytest.fixture(scope="module")

@@ -3,13 +3,10 @@ import numpy as np
 import pytest
 
 from conftest import load_system
+from craft_cases import bits
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def assert_same_bits(a, b, what=""):

@@ -5,9 +5,9 @@ import numpy as np
 import pytest
 
 from conftest import SYSTEMS, load_system
+from craft_cases import oracle_plot
 from ephemeris_explorer_amd.systems import load_ship, parse_epoch
 from oracle import orc
-from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
@@ -25,54 +25,6 @@ def scene(gpu):
     c = orc.Craft(osol, s.mu, ship.start, ship.pos, ship.vel, "Verner87")
     assert c.step_to(ship.start + 20 * 86400.0) == 0
     return s, gpu.Ephemeris(sol, s.mu), osol, c.knots()
-
-
-def oracle_plot(s, osol, knots, view, rq):
-    """compute_plot_points_parallel :318-374 for one plot, evaluations by the oracle."""
-    def bounds(body):
-        st, iv, n = osol.info(body)
-        return st, st + iv * float(n), n
-    if rq.get("source_body", -1) >= 0:
-        tb = bounds(rq["source_body"])
-    else:
-        first, count = rq["knots"]
-        kt = knots[0][first:first + count]
-        tb = (kt[0], kt[-1], len(kt) - 1) if len(kt) else (po.EPOCH_MIN, po.EPOCH_MAX, 0)
-    ref = rq.get("reference_body", -1)
-    rb = bounds(ref) if ref >= 0 else None
-    if not rq.get("enabled", 1):
-        return "ok", []
-    win = po.plot_window(tb, rb, rq["start"], rq["end"], rq.get("bound", 0), view["current"])
-    if win is None:
-        return "ok", []
-    tr = po.Vec(0.0, 0.0, 0.0)
-    if ref >= 0:
-        tc = min(max(view["current"], rb[0]), rb[1])
-        tr = po.Vec(*osol.eval(ref, tc, with_velocity=False))
-    m = np.asarray(view.get("grid_matrix3", np.eye(3)), dtype=np.float64)
-    ax = [po.Vec(*m[:, c]) for c in range(3)]
-    gt, cell = po.Vec(*view.get("grid_translation", (0.0,) * 3)), po.Vec(*view.get("cell_offset", (0.0,) * 3))
-    mul = lambda v: (ax[0] * v[0] + ax[1] * v[1]) + ax[2] * v[2]      # noqa: E731  glam DMat3::mul_vec3
-
-    def evaluate(t):
-        rp, rv = po.Vec(0.0, 0.0, 0.0), po.Vec(0.0, 0.0, 0.0)
-        if ref >= 0:
-            r = osol.eval(ref, t)
-            if r is None:
-                return None
-            rp, rv = po.Vec(*r[0]), po.Vec(*r[1])
-        if rq.get("source_body", -1) >= 0:
-            r = osol.eval(rq["source_body"], t)
-        else:
-            first, count = rq["knots"]
-            r = orc.hermite_eval(knots[0][first:first + count], knots[1][first:first + count], knots[2][first:first + count], t)
-        if r is None:
-            return None
-        pos = (po.Vec(*r[0]) - rp) + tr
-        vel = (po.Vec(*r[1]) - rv) + po.Vec(0.0, 0.0, 0.0)
-        return mul(pos - cell) + gt, mul(vel)
-    return po.plot_points_new(evaluate, win[0], win[1], po.Vec(*view["camera_position"]), rq["tan2_angular_resolution"],
-                              rq["max_points"])
 
 
 def test_plot_points_match_the_restatement(gpu, scene):

@@ -16,16 +16,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, SYSTEMS, load_system
+from craft_cases import bits
 from ephemeris_explorer_amd.systems import load_ship
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
 DAY = 86400.0
 REPS = 20
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_cpp_threads_program(gpu, tmp_path):

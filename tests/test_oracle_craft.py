@@ -30,8 +30,7 @@ def scenario():
     assert pr.step_to(parse_epoch("1952-01-01 00:00:00")) == 0
     eph = pr.take_solution()
     ship = load_ship(SYSTEMS / "full_solar_system_2433282.5" / "ships" / "Mars Transfer Ship.json")
-    burns = [(b.start, b.start + b.duration, b.acceleration, s.names.index(b.reference) if b.reference else -1)
-             for b in ship.burns]
+    burns = ship.burn_tuples(s.names)
     return s, eph, ship, burns
 
 
