@@ -10,10 +10,19 @@
 // layouts: profiles/r02_step_kernel_evidence.md, profiles/r03_step_kernel_evidence.md; the retired code: step_wg_retired.inc,
 // compiled only with -DEPH_EXPERIMENTS):
 //   * 16 bodies per workgroup, TWELVE waves, three per SIMD (waves go to the four SIMDs round-robin: wave k -> SIMD k % 4),
-//     <= 168 VGPRs each: SIMDs 1-3 carry pair waves of 2 / 2 / 1 bodies, SIMD 0 a one-body pair wave, the chain wave (at raised
-//     issue priority) and the tail wave;
-//   * ONE s_barrier per 128 sources (two 64-source tiles; the first two tiles go singly so the chain wave starts early), six
-//     25 KB LDS tile buffers: pair waves run one 128-source "big tile" ahead of the chain wave;
+//     <= 168 VGPRs each: on SIMDs 1-3 three pair waves that carry the SAME five bodies (1-5, 6-10, 11-15) and take one source
+//     tile each of a three-tile phase (round 7: pair work dealt by source tile); SIMD 0 a one-body pair wave (body 0, all
+//     three tiles), the chain wave (at raised issue priority) and the tail wave;
+//   * ONE s_barrier per 192 sources (three 64-source tiles; the first two tiles go singly so the chain wave starts early): 23
+//     barriers for the 64 tiles of N = 4096. Six 25 KB LDS tile buffers as two sets of three: the pair waves write one phase
+//     while the chain wave sums the one before. Rounds 2-6 had one barrier per 128 sources (three sets of two buffers, pair
+//     waves of 2 / 2 / 1 bodies against two tiles, 34 barriers): 36.02-36.09 us per step at N = 4096 against 33.16-33.31 for this
+//     form, same box, alternating, 3 x 5 blocks of 500 steps each (profiles/r07_step_kernel_evidence.md); pair side alone
+//     31.1 (was 34.4), chain side alone 25.35 (was 26.55). The dealing WITHOUT the cadence (128-source schedule, two five-body
+//     waves per SIMD and one idle) was 36.40-36.48 against the parent's 35.98-36.11: the gain is the barriers, not the equal-shaped waves
+//     (scripts/experiments/wg_deal128.patch). Keeping a phase's results in registers across the barrier and issuing the ds_writes
+//     at the head of the NEXT phase (nothing drains before the barrier; the chain wave one phase further behind) was built
+//     and measured as well: bit-identical and 1.4 us slower (35.53-35.63 against 34.15-34.25 for the same build without it);
 //   * the tail wave (k_lm_step_wg) loads the 2 L history values while the others work, receives the new acceleration through
 //     LDS and does Cowell's velocity, the solout sample and the predictor;
 //   * 8- and 4-body workgroups for target counts that would leave CUs without a 16-body workgroup (<= 2048 / <= 1024 targets): the
@@ -42,13 +51,13 @@
 #define EPH_WG_ABLATE 0
 #endif
 #define WG_LOOP_BARRIER() do { if constexpr (!(EPH_WG_ABLATE & 2)) __syncthreads(); } while (0)
-// PREPARED, NOT MEASURED (-DEPH_EXPERIMENTS=1 -DEPH_WG_DIAG_PATCH=1): the interval that holds the workgroup's own tile takes the
-// IEEE form for BOTH of its tiles on every pair wave (n2 = 0 on the self lanes fails the range test of the whole wave): about 1.8 x
-// the instructions for one interval of 33, up to 0.5 us per step at N = 4096 if the pair side is the longer one there. With the
-// switch the self lanes get in-range operands instead (n2 = 1; their contribution is read and discarded by chain_masked) and the
-// interval stays on the seeded sequences. Round 2 measured the same idea on the barrier-per-tile kernel (40.1 vs 40.0 us, no
-// gain): to be re-measured on this one (scripts/experiment.sh TAG -l product -l diagpatch sizes 2048 4096, and
-// EPH_AMD_LIBRARY=...exp_diagpatch.so pytest tests/test_gpu_parity.py tests/test_gpu_horizon.py for the bits).
+// MEASURED, NOT THE DEFAULT (-DEPH_EXPERIMENTS=1 -DEPH_WG_DIAG_PATCH=1): the pair waves that meet the workgroup's own tile take the
+// IEEE form for it (n2 = 0 on the self lanes fails the range test of the whole wave): about 1.8 x the instructions for that wave in
+// one phase. With the switch the self lanes get in-range operands instead (n2 = 1; their contribution is read and discarded by
+// chain_masked) and the wave stays on the seeded sequences. Round 2 measured the idea on the barrier-per-tile kernel (40.1 vs
+// 40.0 us, no gain); round 7 on the 192-source schedule, five bodies on the wave that meets the own tile: bit-identical
+// (tests/test_gpu_step_phases.py) and SLOWER, 35.19-35.30 against 33.53-33.64 us per step at N = 4096 -- the lane compares and
+// selects sit in front of every tile of every wave, the IEEE form in one phase of 23 (profiles/r07_step_kernel_evidence.md).
 #if EPH_EXPERIMENTS && defined(EPH_WG_DIAG_PATCH)
 #define EPH_WG_DIAG_PATCH_ON 1
 #else
@@ -192,7 +201,7 @@ __device__ __forceinline__ void wg_pair_tile2(const double (&xi)[NB], const doub
     }
 }
 
-// Layout 3 barrier schedule. The 64-source tiles are grouped into "big" tiles, one barrier each: big tiles 0 and 1 are
+// Layout 3 barrier schedule (the 8-body workgroups; the 16-body one: phase_start below). The 64-source tiles are grouped into "big" tiles, one barrier each: big tiles 0 and 1 are
 // single tiles (so the chain wave starts after two tiles, not four: its wait for the first barrier was 2.7 us of a
 // 42 us launch), every later one is two tiles. Every wave executes TB + 1 barriers: B_0 after big tiles 0 and 1 are
 // in LDS; iteration K: pair waves produce big tile K + 2 while the chain wave sums big tile K (and prefetches the head
@@ -259,6 +268,189 @@ __device__ __forceinline__ void wg_idle_wave(int tiles) {
     for (int T = 0; T < big_count(tiles); ++T) WG_LOOP_BARRIER();
 }
 
+// ---- the 16-body workgroup: pair work dealt by SOURCE TILE, one barrier per 192 sources ------------------------------------------
+// The same six tile buffers as two sets of three: phases 0 and 1 are the single tiles 0 and 1 (the chain wave starts as early as
+// before), phase P >= 2 is the tiles 3 P - 4 .. 3 P - 2. Tile t lives in buffer t % 6, so even phases >= 2 own buffers {2, 3, 4}, odd
+// ones {5, 0, 1}; the single tiles (buffers 0 and 1) have been summed two barriers before phase 3 writes there. The chain wave sums
+// phase P while the pair waves write phase P + 1. Every wave executes phase_count(tiles) barriers: B_0 after tile 0 is in LDS, then
+// one behind every phase but the last (which the chain wave sums alone; the buffers are dead after it).
+__device__ __forceinline__ int phase_start(int P) { return P < 2 ? P : 3 * P - 4; }
+__device__ __forceinline__ int phase_count(int tiles) { return tiles <= 2 ? tiles : 2 + (tiles - 2 + 2) / 3; }
+__device__ __forceinline__ int phase_tiles(int P, int tiles) { return P < 2 ? 1 : min(3, tiles - phase_start(P)); }
+__device__ __forceinline__ void wg_idle_wave_phases(int tiles) {
+    __syncthreads();
+    for (int P = 1; P < phase_count(tiles); ++P) WG_LOOP_BARRIER();
+}
+
+// the staged term for M = MA + MB interactions in two runs (the division orders 4 and 6 carry six more doubles per interaction
+// through the stages: five at once do not fit 168 VGPRs)
+template <int MA, int MB>
+__device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA + MB], const double (&mu)[MA + MB], double (&c)[3 * (MA + MB)]) {
+    PairPre pa[MA], pb[MB];
+    double ma[MA], mb[MB], ca[3 * MA], cb[3 * MB];
+#pragma unroll
+    for (int k = 0; k < MA; ++k) { pa[k] = pre[k]; ma[k] = mu[k]; }
+#pragma unroll
+    for (int k = 0; k < MB; ++k) { pb[k] = pre[MA + k]; mb[k] = mu[MA + k]; }
+    pair_finish_staged<MA>(pa, ma, ca);
+    pair_finish_staged<MB>(pb, mb, cb);
+#pragma unroll
+    for (int k = 0; k < 3 * MA; ++k) c[k] = ca[k];
+#pragma unroll
+    for (int k = 0; k < 3 * MB; ++k) c[3 * MA + k] = cb[k];
+}
+
+// NB bodies (local indices b0..) against NT 64-source tiles: NB * NT independent interactions behind ONE range test, the staged
+// arithmetic (pair_finish_staged, pair_term.h), then the write burst. self[s]: EPH_WG_DIAG_PATCH only -- the lane that holds body
+// b0 as a source of tile s (far off: none).
+template <int NB, int NT>
+__device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
+                                              const Body4 (&pj)[NT], bool ieee, double *const (&tile)[NT], int b0, int lane,
+                                              const int (&self)[NT]) {
+    constexpr int M = NB * NT;
+    PairPre pre[M];
+    double mus[M];
+    unsigned worst = ieee ? kRangeSpan : 0u, low = ~0u;
+#pragma unroll
+    for (int s = 0; s < NT; ++s) {
+        worst = max(worst, mu_key(pj[s].mu));
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int k = s * NB + b;
+            pre[k] = pair_pre(xi[b], yi[b], zi[b], pj[s]);
+            mus[k] = pj[s].mu;
+            if constexpr (EPH_WG_DIAG_PATCH_ON) {
+                if (lane == self[s] + b) { pre[k].n2 = 1.0; pre[k].lo = 0x3ff00000u; }
+            }
+            worst = max(worst, range_key(pre[k].n2));
+            low = min(low, pre[k].lo);
+        }
+    }
+    worst = max(worst, low_key(low));
+    double c[3 * M];
+    if (__builtin_amdgcn_ballot_w64(worst >= kRangeSpan) == 0) {
+        if constexpr (kPairStaged && M == 5 && (kPairVariant == 4 || kPairVariant == 6)) {
+            pair_finish_staged_split<3, 2>(pre, mus, c);
+        } else if constexpr (kPairStaged) {
+            pair_finish_staged<M>(pre, mus, c);
+        } else {
+#pragma unroll
+            for (int k = 0; k < M; ++k) pair_finish<true>(pre[k], mus[k], c[3 * k], c[3 * k + 1], c[3 * k + 2]);
+        }
+    } else {   // the tile holding the workgroup's own bodies (n2 = 0 on the self lane) or an operand outside the guarded ranges
+#pragma unroll
+        for (int k = 0; k < M; ++k) pair_finish<false>(pre[k], mus[k], c[3 * k], c[3 * k + 1], c[3 * k + 2]);
+    }
+#pragma unroll
+    for (int s = 0; s < NT; ++s) {
+#pragma unroll
+        for (int q = 0; q < 3 * NB; ++q) {
+            if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(c[3 * NB * s + q]));
+            else tile[s][(3 * b0 + q) * kRow + lane] = c[3 * NB * s + q];
+        }
+    }
+}
+
+// A pair wave of SIMDs 1-3: the five bodies b0.. of its SIMD group against ONE tile of every phase, the tile given by the wave's
+// rank among the three waves of its SIMD -- three waves of identical shape and work, one source tile loaded per wave and phase.
+// In the single-tile phases rank 0 has the tile and the other two only meet the barrier.
+template <typename PosPtr>
+__device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int b0, int rank, double *C, int lane, int tiles, int tdiag, int wbuf) {
+    constexpr int NB = 5;
+    double xi[NB], yi[NB], zi[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int ii = min(i0 + b0 + b, n - 1);
+        xi[b] = pos[ii].x;
+        yi[b] = pos[ii].y;
+        zi[b] = pos[ii].z;
+    }
+    // (the wave's own positions are wave-uniform and the compiler keeps them in scalar registers; pinned into vector registers
+    // instead: 34.20-34.34 against 33.16-33.31 us per step at N = 4096, alternating on one box)
+    auto load_src = [&](int t) -> Body4 {
+        const int j = min(t, tiles - 1) * kTile + lane;
+        return pos[j < n ? j : n - 1];
+    };
+    auto tile_of = [&](int P) { return P < 2 ? (rank == 0 ? P : tiles) : phase_start(P) + rank; };   // >= tiles: none
+    auto produce = [&](int t, const Body4 &pj) {
+        if (t >= tiles || EPH_WG_SIDE == 2) return;
+        const Body4 src[1] = {pj};
+        double *const dst[1] = {C + (t % kWgTileBufs) * wbuf};
+        // (bodies beyond n are clamped copies of body n - 1: never diagonal lanes)
+        const int self[1] = {EPH_WG_DIAG_PATCH_ON && t == tdiag ? i0 + b0 - t * kTile : -64};
+        wg_pair_block<NB, 1>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self);
+    };
+    const int NP = phase_count(tiles);
+    Body4 pj = load_src(tile_of(0)), pjn = load_src(tile_of(1));
+    produce(tile_of(0), pj);
+    __syncthreads();
+    for (int P = 1; P < NP; ++P) {
+        pj = pjn;
+        pjn = load_src(tile_of(P + 1));
+        produce(tile_of(P), pj);
+        WG_LOOP_BARRIER();
+    }
+}
+// The one-body pair wave of the chain wave's SIMD: body 0 against every tile of the phase (three interactions at once)
+template <typename PosPtr>
+__device__ __forceinline__ void wg_pair_wave_solo(PosPtr pos, int n, int i0, double *C, int lane, int tiles, int tdiag, int wbuf) {
+    const int ii = min(i0, n - 1);
+    const double xi[1] = {pos[ii].x}, yi[1] = {pos[ii].y}, zi[1] = {pos[ii].z};
+    auto load_src = [&](int t) -> Body4 {
+        const int j = min(t, tiles - 1) * kTile + lane;
+        return pos[j < n ? j : n - 1];
+    };
+    auto load_phase = [&](int P, Body4 (&s)[3]) {
+        const int t = phase_start(P);
+        s[0] = load_src(t);
+        if (P >= 2) { s[1] = load_src(t + 1); s[2] = load_src(t + 2); }
+    };
+    const int NP = phase_count(tiles);
+    auto produce = [&](int P, const Body4 (&s)[3]) {
+        if (P >= NP || EPH_WG_SIDE == 2) return;
+        const int t = phase_start(P), cnt = phase_tiles(P, tiles);
+        if (cnt == 3) {
+            double *const dst[3] = {C + (t % kWgTileBufs) * wbuf, C + ((t + 1) % kWgTileBufs) * wbuf, C + ((t + 2) % kWgTileBufs) * wbuf};
+            const bool own = tdiag >= t && tdiag < t + 3;
+            int self[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) self[k] = EPH_WG_DIAG_PATCH_ON && tdiag == t + k ? i0 - (t + k) * kTile : -64;
+            wg_pair_block<1, 3>(xi, yi, zi, s, !EPH_WG_DIAG_PATCH_ON && own, dst, 0, lane, self);
+        } else {   // the single tiles and a short last phase
+            auto one = [&](int k, const Body4 &pj) {
+                const Body4 src[1] = {pj};
+                double *const dst[1] = {C + ((t + k) % kWgTileBufs) * wbuf};
+                const int self[1] = {EPH_WG_DIAG_PATCH_ON && tdiag == t + k ? i0 - (t + k) * kTile : -64};
+                wg_pair_block<1, 1>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && tdiag == t + k, dst, 0, lane, self);
+            };
+            one(0, s[0]);
+            if (cnt > 1) one(1, s[1]);
+        }
+    };
+    Body4 s[3], sn[3];
+    load_phase(0, s);
+    load_phase(1, sn);
+    produce(0, s);
+    __syncthreads();
+    for (int P = 1; P < NP; ++P) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] = sn[k];
+        load_phase(P + 1, sn);
+        produce(P, s);
+        WG_LOOP_BARRIER();
+    }
+}
+
+// chain over a full tile whose first two chunks are already in q[0], q[1], nothing prefetched behind it (the last tile of a phase:
+// the next phase's buffers are being written until the barrier)
+__device__ __forceinline__ double chain_full_q(const double *row, double2 (&q)[4][8], double acc) {
+    load_chunk(row, 2, q[2]);
+    acc = add_chunk(q[0], acc);
+    load_chunk(row, 3, q[3]);
+    acc = add_chunk(q[1], acc);
+    acc = add_chunk(q[2], acc);
+    return add_chunk(q[3], acc);
+}
 // chain over a full tile whose first two chunks are already in q[0], q[1]; leaves the first two chunks of the
 // NEXT tile (row_next, complete since the previous barrier) in q[0], q[1]
 __device__ __forceinline__ double chain_full_pf(const double *row, const double *row_next, double2 (&q)[4][8],
@@ -364,16 +556,15 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
         if (body >= 0) { wg_pair_wave_big<1>(pos, n, i0, body, C, lane, tiles, tdiag, kBuf); return 0.0; }
         if (wave != kWgChainWave) { wg_idle_wave(tiles); return 0.0; }
     } else {
-        // Roles of the twelve waves (wave k runs on SIMD k % 4): pair waves of 2 / 2 / 1 bodies on SIMDs 1-3, a one-body pair wave
-        // on SIMD 0 beside the chain wave (4) and the tail wave (8). ONE copy of the pair loop per body count, the role's first
-        // body a run-time scalar: inlining the loop once per role (ten copies, round 2-3) measured 0.15 us slower at N = 4096
-        // (36.20 against 36.04 us, profiles/r04_step_kernel_evidence.md) and is 40 KB more code per evaluation order.
+        // Roles of the twelve waves (wave k runs on SIMD k % 4, so waves k and k + 4 share a SIMD whatever the start of the
+        // hardware's cyclic order): wave id = 1, 2, 3 (mod 4) are the pair waves of SIMD group id % 4 -- bodies 1-5, 6-10, 11-15 --
+        // and take the tile of the phase given by their rank id >> 2; wave 0 is the one-body pair wave (body 0) beside the chain
+        // wave (4) and the tail wave (8). ONE copy of the five-body pair loop, the first body and the rank run-time scalars
+        // (inlining the loop once per role measured 0.15 us slower in round 4 and is 40 KB more code per evaluation order).
         const int w = __builtin_amdgcn_readfirstlane(wave);
-        const int nb = (w == kWgChainWave || w == kWgTailWave) ? 0 : ((w == 0 || w >= 9) ? 1 : 2);
-        const int b0 = w == 0 ? 0 : w == 1 ? 1 : w == 5 ? 3 : w == 9 ? 5 : w == 2 ? 6 : w == 6 ? 8 : w == 10 ? 10 : w == 3 ? 11 : w == 7 ? 13 : 15;
-        if (nb == 2) { wg_pair_wave_big<2>(pos, n, i0, b0, C, lane, tiles, tdiag, kBuf); return 0.0; }
-        if (nb == 1) { wg_pair_wave_big<1>(pos, n, i0, b0, C, lane, tiles, tdiag, kBuf); return 0.0; }
-        if (w == kWgTailWave) { wg_idle_wave(tiles); return 0.0; }   // (k_lm_step_wg gives this wave the integrator's work instead)
+        if (w == 0) { wg_pair_wave_solo(pos, n, i0, C, lane, tiles, tdiag, kBuf); return 0.0; }
+        if (w & 3) { wg_pair_wave_deal(pos, n, i0, 5 * (w & 3) - 4, w >> 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
+        if (w == kWgTailWave) { wg_idle_wave_phases(tiles); return 0.0; }   // (k_lm_step_wg gives this wave the integrator's work instead)
     }
     // chain wave. Its dependent adds issue ahead of the one-body pair wave of its SIMD (s_setprio; the same library with and
     // without, alternating on one box: 36.3 against 36.8 us per step at N = 4096 on two boxes of the pool, 36.2 either way on a
@@ -384,8 +575,44 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
     const int li = (i0 % kTile) + ch / 3;
     double acc = init, accL = 0.0;
     double2 q[4][8];
-    const int TB = big_count(tiles);
     if constexpr (WB == kWgBodies || DUO) __builtin_amdgcn_s_setprio(3);
+    if constexpr (WB == kWgBodies && !DUO) {
+        // phases of up to three tiles. Until the barrier that ends phase P every buffer outside P is being written, so a phase
+        // opens with the load of its own first two chunks; inside a phase tile t + 1 is prefetched while tile t is summed.
+        const int NP = phase_count(tiles);
+        __syncthreads();                              // B_0: tile 0 ready
+        for (int P = 0; P < NP; ++P) {
+            const int t0 = phase_start(P), nt = phase_tiles(P, tiles);
+            // three whole tiles of other workgroups' bodies (all but a handful of phases): written out, the prefetch registers
+            // never change hands. (As a loop over the tiles of the phase with the masked form inside, the optimiser left it rolled
+            // and rotated the 128 prefetch registers through moves behind an lgkmcnt(0): 40.3 us per step at N = 4096.)
+            const bool whole = nt == 3 && (tdiag < t0 || tdiag > t0 + 2) && n - (t0 + 2) * kTile >= kTile;
+            if constexpr (EPH_WG_SIDE == 1) {
+            } else if (whole) {
+                const double *r0 = row + (t0 % kWgTileBufs) * kBuf, *r1 = row + ((t0 + 1) % kWgTileBufs) * kBuf;
+                const double *r2 = row + ((t0 + 2) % kWgTileBufs) * kBuf;
+                load_chunk(r0, 0, q[0]);
+                load_chunk(r0, 1, q[1]);
+                acc = chain_full_pf(r0, r1, q, acc);
+                acc = chain_full_pf(r1, r2, q, acc);
+                acc = chain_full_q(r2, q, acc);
+            } else {   // the single tiles, the phase with the workgroup's own tile, a short or ragged last phase
+                for (int t = t0; t < t0 + nt; ++t) {
+                    const double *r = row + (t % kWgTileBufs) * kBuf;
+                    const int cnt = min(kTile, n - t * kTile);
+                    if (t != tdiag && cnt == kTile) { acc = chain_full(r, acc); continue; }
+                    // (li made opaque per tile: hoisted out of this loop, the 64 "is this source my own body" lane masks of
+                    // chain_masked are 128 scalar registers held across the whole kernel)
+                    int lit = li;
+                    asm volatile("" : "+v"(lit));
+                    chain_masked<WB>(r, cnt, t == tdiag ? gself : -1, lit, acc, accL);
+                }
+            }
+            if (P + 1 < NP) WG_LOOP_BARRIER();        // phase P consumed, phase P + 1 ready
+        }
+        return accL + acc;
+    }
+    const int TB = big_count(tiles);
     __syncthreads();                                  // B_0: tiles 0 and 1 ready
     load_chunk(row, 0, q[0]);
     load_chunk(row, 1, q[1]);
@@ -468,6 +695,8 @@ k_lm_step_wg(const LmArgs a) {
         const int tiles = (a.n + kTile - 1) / kTile;
         if constexpr (wg_tile_split(WB) && !DUO) {
             for (int t = 0; t <= tiles; ++t) __syncthreads();                             // one barrier per tile there
+        } else if constexpr (WB == kWgBodies && !DUO) {
+            wg_idle_wave_phases(tiles);
         } else {
             wg_idle_wave(tiles);
         }
