@@ -15,8 +15,8 @@ import ctypes as C
 import numpy as np
 
 from . import systems  # noqa: F401  (state.json / ephemeris.json / ships readers)
-from ._abi import (ABI_SYMBOLS, EXCHANGE_FN, LIB_PATH, AdaptiveParams, PlotRequest, PlotView,  # noqa: F401  (the package's names)
-                   SeparationRequest, _dp, _fp, _i32p, _i64p, _lib, _u8p, _u32p, hip_runtime)
+from ._abi import (ABI_SYMBOLS, EXCHANGE_FN, LIB_PATH, AdaptiveParams, OrbitPlotConfig, PlotRequest,  # noqa: F401  (the package's names)
+                   PlotSegment, PlotView, SeparationRequest, _dp, _fp, _i32p, _i64p, _lib, _u8p, _u32p, hip_runtime)
 
 FORWARD, BACKWARD = 1, -1
 PATH_FAST = 4
@@ -654,6 +654,44 @@ class SpacecraftBatch(_Handle):
         _call("eph_craft_batch_plot_points", self._h, C.byref(_plot_view(view)), n, arr, _p_or_null(crafts, _i64p), *out.args())
         return out.rows(n)
 
+    SEGMENT = np.dtype([("plot", "i8"), ("transition", "i4"), ("timeline_segment", "i4"), ("soi_body", "i4"), ("reference_body", "i4"),
+                        ("kind", "i4"), ("is_burn", "i4"), ("overlapping", "i4"), ("start", "f8"), ("end", "f8")], align=True)  # eph_plot_segment
+
+    def plot_segments(self, view, configs, body_parent, craft=None):
+        """setup_segment_plotting (ephemeris_explorer/src/analysis.rs:159-296) on the device, ending in the sampler of
+        plot_points() (eph_craft_batch_plot_segments): entry p splits craft craft[p] (None: entry p is craft p) at its SOI
+        transitions and at the boundaries of its timeline, as the batch holds them now (events must be enabled).
+        configs: list of dict(start, end, bound=0, enabled=1, tan2_angular_resolution, max_points_per_segment,
+        reference_body=-1 (Primary) | body), or one dict for all entries; body_parent: soi_parents(system).
+        -> (segments, plots): segments a record array (SEGMENT: plot, transition, timeline_segment, soi_body, reference_body,
+        kind, is_burn, overlapping, start, end) in spawn order, entry by entry; plots[s] what plot_points() returns for
+        segment s, or None with view=None (records only). Sizes with the records-only call, then fills."""
+        configs, (crafts,) = _per_request("SpacecraftBatch.plot_segments: one craft per config", self.n, configs, craft)
+        n = len(configs)
+        arr = (OrbitPlotConfig * max(n, 1))()
+        cap = 1
+        for i, c in enumerate(configs):
+            arr[i] = OrbitPlotConfig(float(c["start"]), float(c["end"]), int(c.get("bound", 0)), int(c.get("enabled", 1)),
+                                     float(c["tan2_angular_resolution"]), int(c["max_points_per_segment"]), int(c.get("reference_body", -1)))
+            cap = max(cap, int(c["max_points_per_segment"]))
+        parents = np.ascontiguousarray(body_parent, dtype=np.int32).ravel()
+        first = np.zeros(n + 1, dtype=np.int64)
+        head = (self._h, n, arr, _p_or_null(crafts, _i64p), _p(parents, _i32p))
+        st = _lib().eph_craft_batch_plot_segments(*head, 0, None, _p(first, _i64p), None, 0, None, None, None, None, None)
+        total = int(first[n])
+        if st != ERR_BAD_ARGUMENT or total == 0:        # (a sizing call that is refused has written the total it needs)
+            _check(st, "eph_craft_batch_plot_segments")
+        segments = np.zeros(total, dtype=self.SEGMENT)
+        if total == 0:
+            return segments, (None if view is None else [])
+        records = segments.ctypes.data_as(C.POINTER(PlotSegment))
+        if view is None:
+            _call("eph_craft_batch_plot_segments", *head, total, records, _p(first, _i64p), None, 0, None, None, None, None, None)
+            return segments, None
+        out = _PlotOut(total, cap)
+        _call("eph_craft_batch_plot_segments", *head, total, records, _p(first, _i64p), C.byref(_plot_view(view)), *out.args())
+        return segments, out.rows(total)
+
     def closest_separation(self, requests, craft=None, target_craft=None):
         """The closest-separation search of target plotting on the batch's own knots (eph_craft_batch_closest_separation):
         request p searches craft craft[p] (None: request p is craft p) against body requests[p]["target_body"] of the live
@@ -848,6 +886,15 @@ class _PlotOut:
     def rows(self, n):
         return [(int(self.status[i]), float(self.failed_at[i]), self.t[i, :self.count[i]].copy(), self.xyz[i, :self.count[i]].copy())
                 for i in range(n)]
+
+
+SEGMENT_KINDS = ("Capture", "Escape", "Flyby", "Transit", "Orbit")      # PlotSegment, analysis.rs:144-151, by eph_plot_segment.kind
+
+
+def segment_name(names, segment):
+    """The Name setup_segment_plotting gives a plot (analysis.rs:212,245-290), e.g. "Mars Flyby Burn": names in table order,
+    segment one record of SpacecraftBatch.plot_segments."""
+    return f"{names[int(segment['soi_body'])]} {SEGMENT_KINDS[int(segment['kind'])]}" + (" Burn" if int(segment["is_burn"]) else "")
 
 
 def _separation_requests(requests, craft_source=False):

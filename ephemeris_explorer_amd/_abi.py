@@ -36,6 +36,19 @@ class PlotRequest(C.Structure):
                 ("enabled", C.c_int32), ("tan2_angular_resolution", C.c_double), ("max_points", C.c_int64)]
 
 
+class OrbitPlotConfig(C.Structure):
+    """eph_orbit_plot_config = OrbitPlotConfig (ephemeris_explorer/src/analysis.rs:132-142) without its colour."""
+    _fields_ = [("start", C.c_double), ("end", C.c_double), ("bound", C.c_int32), ("enabled", C.c_int32),
+                ("tan2_angular_resolution", C.c_double), ("max_points_per_segment", C.c_int64), ("reference_body", C.c_int32)]
+
+
+class PlotSegment(C.Structure):
+    """eph_plot_segment: one plot setup_segment_plotting spawns (analysis.rs:229-292)."""
+    _fields_ = [("plot", C.c_int64), ("transition", C.c_int32), ("timeline_segment", C.c_int32), ("soi_body", C.c_int32),
+                ("reference_body", C.c_int32), ("kind", C.c_int32), ("is_burn", C.c_int32), ("overlapping", C.c_int32),
+                ("start", C.c_double), ("end", C.c_double)]
+
+
 class SeparationRequest(C.Structure):
     """eph_separation_request: one closest-separation search of target plotting (ephemeris_explorer/src/analysis.rs:344-348)."""
     _fields_ = [("source_body", C.c_int32), ("target_body", C.c_int32), ("source_knot_first", C.c_int64),
@@ -59,6 +72,7 @@ class AdaptiveParams(C.Structure):
 def _signatures():
     vp, i32, i64, u32, u64, f64, text = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double, C.c_char_p
     view, plots, searches, params = C.POINTER(PlotView), C.POINTER(PlotRequest), C.POINTER(SeparationRequest), C.POINTER(AdaptiveParams)
+    configs, segments = C.POINTER(OrbitPlotConfig), C.POINTER(PlotSegment)
     knots = [i64, _dp, _dp, _dp]                                  # a (count, t, pos, vel) knot triple
     separation_out = [_u8p, _dp, _dp, _i32p, _i32p, _dp]          # found, time, distance, iterations, status, failed_at
     plot_out = [i64, _dp, _fp, _i64p, _i32p, _dp]                 # capacity, t, xyz, count, status, failed_at
@@ -156,6 +170,7 @@ def _signatures():
         "eph_craft_batch_knot_slabs": (i32, [vp, i32, i32, _dp, _dp]),
         "eph_craft_batch_eval": (i32, [vp, i64, _dp, i32, i32, _dp, _u8p]),
         "eph_craft_batch_plot_points": (i32, [vp, view, i64, plots, _i64p, *plot_out]),
+        "eph_craft_batch_plot_segments": (i32, [vp, i64, configs, _i64p, _i32p, i64, segments, _i64p, view, *plot_out]),
         "eph_craft_batch_closest_separation": (i32, [vp, i64, searches, _i64p, _i64p, *separation_out]),
         "eph_craft_batch_restart": (i32, [vp, _u8p, _i64p, *burns, _dp, params, _dp, _i32p]),
         "eph_craft_batch_reset_knots": (i32, [vp]),

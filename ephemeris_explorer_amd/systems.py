@@ -167,6 +167,29 @@ def soi_radii(system):
     return np.array([radius[i] for i in range(system.n)], dtype=np.float64)
 
 
+def soi_parents(system):
+    """The body whose sphere of influence each body is in at the system's epoch, in body order, -1 for a body in no other
+    body's sphere (the reference's SystemRoot): setup_static_soi_transition / find_soi_query
+    (ephemeris_explorer/src/analysis.rs:101-124,446-461) over find_soi (dynamics/spacecraft.rs:205-216) with the radii of
+    soi_radii(). The body itself is excluded; inside means d^2 < r^2; the closest sphere's centre wins, the first on ties.
+    This is the body_parent of SpacecraftBatch.plot_segments."""
+    radius = soi_radii(system)
+    parents = []
+    for i in range(system.n):
+        best, best_d2 = -1, 0.0
+        for j in range(system.n):
+            if j == i:
+                continue
+            d = system.pos[i] - system.pos[j]
+            d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+            if not d2 < radius[j] * radius[j]:
+                continue
+            if best < 0 or d2 < best_d2:                                  # min_by keeps the first minimum
+                best, best_d2 = j, d2
+        parents.append(best)
+    return np.array(parents, dtype=np.int32)
+
+
 @dataclass
 class Burn:
     start: float

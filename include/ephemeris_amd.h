@@ -544,6 +544,72 @@ int32_t eph_craft_batch_plot_points(eph_craft_batch *b, const eph_plot_view *vie
                                     const eph_plot_request *requests, const int64_t *craft, int64_t capacity,
                                     double *out_t, float *out_xyz, int64_t *out_count, int32_t *out_status,
                                     double *out_failed_at);
+/* ---- segment plotting: which plots a ship gets (ephemeris_explorer/src/analysis.rs:159-296) -------------------------
+ * setup_segment_plotting for ships that live in an eph_craft_batch, one device thread per (ship, OrbitPlotConfig) entry,
+ * ending in the sampler above: a new plot at every SOI transition and at every boundary of the ship's Timeline, each
+ * relative to the body whose sphere the ship is in, tagged Capture / Escape / Flyby / Transit / Orbit, burn pieces
+ * dashed, a flyby drawn a second time relative to the parent body. Names, colours and despawn_related stay with the
+ * caller. */
+typedef struct eph_orbit_plot_config {      /* OrbitPlotConfig, analysis.rs:132-142 */
+    double start, end;
+    int32_t bound;                          /* PlotBound 0 None, 1 Start, 2 End */
+    int32_t enabled;
+    double tan2_angular_resolution;         /* as in eph_plot_request, from config.resolution */
+    int64_t max_points_per_segment;
+    int32_t reference_body;                 /* OrbitPlotReference: -1 = Primary, >= 0 = Entity(body), table order */
+} eph_orbit_plot_config;
+typedef struct eph_plot_segment {           /* one spawned (PlotSource, PlotConfig, PlotSegment, markers) */
+    int64_t plot;                           /* p: the entry of configs / craft that spawned it */
+    int32_t transition;                     /* i, index into the craft's SoiTransitions */
+    int32_t timeline_segment;               /* index into the craft's Timeline */
+    int32_t soi_body;                       /* b: the body whose name prefixes the segment's Name */
+    int32_t reference_body;                 /* PlotSource.reference */
+    int32_t kind;                           /* PlotSegment in declaration order: 0 Capture 1 Escape 2 Flyby 3 Transit 4 Orbit */
+    int32_t is_burn;                        /* BurnPlotSegment = PlotConfig.dashed */
+    int32_t overlapping;                    /* OverlappingPlotSegment (the caller applies alpha * 0.2) */
+    double start, end;                      /* PlotConfig.start / .end of the piece */
+} eph_plot_segment;
+/* Entry p reads craft craft[p] of the batch (craft == NULL: entry p is craft p, so n_plots <= n_craft; a craft may appear
+ * in several entries) under configs[p]: the craft's SoiTransitions as the batch holds them now (after
+ * eph_craft_batch_reset_events the newest one only; for a craft whose event status is EPH_EVENTS_FULL the entries found
+ * so far; a craft whose search has not run has none and spawns nothing) and its current Timeline (after
+ * eph_craft_batch_restart the new one), both read on the device. body_parent[n_bodies] is the static hierarchy of
+ * setup_static_soi_transition (:101-124): the body whose sphere body b is in, or -1 for a body in no other body's sphere
+ * (the reference's SystemRoot entity, which is not a body: -1 never equals a transition's body).
+ * For each transition i = (t_i, b) in order (:204-225): skipped if t_i > config.end or if a next transition exists with
+ * t_{i+1} < config.start; otherwise start = max(t_i, config.start), end = min(t_{i+1}, config.end) (config.end without a
+ * next transition), and every Timeline segment of segments_between(start, end) = [partition_point(seg.end <= start),
+ * partition_point(seg.start < end)) (ephemeris/src/propagators/spacecraft.rs:165-177) spawns one record with start =
+ * max(seg.start, start), end = min(seg.end, end), is_burn from the segment and reference_body = config.reference_body
+ * >= 0 ? config.reference_body : b. Where the first index exceeds the second the reference's slice panics; here the
+ * transition spawns nothing. kind (:227-291) with b_parent = body_parent[b]: from = the previous transition's body ==
+ * b_parent, to = the next transition's body == b_parent; both Flyby, from only Capture, to only Escape, neither Transit
+ * if the craft has another transition and Orbit if it has none. A Flyby under config.reference_body == -1 is followed at
+ * once by its copy with reference_body = b_parent and overlapping = 1 (:254-266). A record is emitted even when its
+ * window is empty (start >= end) and when the config is disabled: such a record draws nothing.
+ * out_first[n_plots + 1] is the exclusive prefix sum of records per entry, out_first[n_plots] the total; it is written
+ * whenever the arguments are valid. If the total exceeds segment_capacity nothing else is written and the status is
+ * EPH_ERR_BAD_ARGUMENT (eph_hermite_join's convention: the needed length comes back); segment_capacity == 0 with
+ * out_segments == NULL is the sizing call. Otherwise out_segments[s] is record s (its padding bytes zero).
+ * view == NULL: records only; capacity and the five point outputs are ignored and nothing is sampled. With a view record
+ * s is drawn as the request {source_body -1, reference_body, knot_first 0, knot_count 0, start, end, config.bound,
+ * config.enabled, config.tan2_angular_resolution, max_points = config.max_points_per_segment} on the record's craft: row
+ * s of out_t, out_xyz, out_count, out_status and out_failed_at is bit for bit what eph_craft_batch_plot_points returns
+ * for that request and craft (capacity >= every max_points_per_segment; entries at or beyond out_count[s] are not
+ * written; the same passes of at most 256 MB). Records and requests are composed on the device and never exist on the
+ * host before the sampler runs; one 4-byte count per entry comes back in between.
+ * Does not change the batch; works on clones; reads the LIVE table as it is when the call starts. n_plots == 0 or an
+ * empty batch: EPH_OK, nothing written. EPH_ERR_BAD_ARGUMENT (nothing written, no device work): NULL batch; a batch
+ * without eph_craft_batch_enable_events; n_plots < 0; NULL configs, body_parent or out_first with entries to do;
+ * craft[p] outside 0 .. n_craft - 1; craft == NULL with n_plots > n_craft; reference_body < -1 or >= n_bodies;
+ * body_parent[b] < -1, >= n_bodies or == b; NaN start or end; bound outside 0..2; max_points_per_segment < 0;
+ * segment_capacity < 0; NULL out_segments with segment_capacity > 0; with a view: capacity < 0, NULL out_count,
+ * out_status or out_failed_at, NULL out_t / out_xyz with capacity > 0, max_points_per_segment > capacity. */
+int32_t eph_craft_batch_plot_segments(eph_craft_batch *b, int64_t n_plots, const eph_orbit_plot_config *configs,
+                                      const int64_t *craft, const int32_t *body_parent,
+                                      int64_t segment_capacity, eph_plot_segment *out_segments, int64_t *out_first,
+                                      const eph_plot_view *view, int64_t capacity, double *out_t, float *out_xyz,
+                                      int64_t *out_count, int32_t *out_status, double *out_failed_at);
 
 /* ---- target plotting: the closest-separation search (ephemeris_explorer/src/analysis.rs:308-371) -------------------
  * setup_target_plotting for a batch of (trajectory, OrbitTarget) pairs, one device thread per request:

@@ -511,6 +511,57 @@ public:
         }
         return out;
     }
+    // setup_segment_plotting (ephemeris_explorer/src/analysis.rs:159-296) for ships that live in the batch, on the device: entry p splits
+    // craft craft[p] (craft empty: entry p is craft p) under configs[p] at its SOI transitions and at the boundaries of its Timeline, as the
+    // batch holds them now (enable_events first), and draws every piece with the sampler of plot_points. body_parent: the static hierarchy
+    // of setup_static_soi_transition (:101-124), the body whose sphere each body is in or -1. segments: the spawned plots in order, entry by
+    // entry (first[p] .. first[p + 1]); points[s]: what plot_points returns for segment s. draw = false: the records only (points empty).
+    struct PlotSegments {
+        std::vector<eph_plot_segment> segments;
+        std::vector<int64_t> first;
+        std::vector<PlotPoints> points;
+    };
+    static const char *segment_kind(int32_t kind) {                // PlotSegment (:144-151)
+        static const char *const names[] = {"Capture", "Escape", "Flyby", "Transit", "Orbit"};
+        return kind >= 0 && kind < 5 ? names[kind] : "?";
+    }
+    PlotSegments plot_segments(const eph_plot_view &view, const std::vector<eph_orbit_plot_config> &configs, const std::vector<int32_t> &body_parent,
+                               const std::vector<int64_t> &craft = {}, bool draw = true) const {
+        const size_t np = configs.size();
+        if (!craft.empty() && craft.size() != np) throw std::invalid_argument("SpacecraftBatch::plot_segments: one craft per config");
+        if (craft.empty() && np > static_cast<size_t>(n_)) throw std::invalid_argument("SpacecraftBatch::plot_segments: more configs than craft");
+        const int64_t *cr = craft.empty() ? nullptr : craft.data();
+        PlotSegments out;
+        out.first.assign(np + 1, 0);
+        // the sizing call: refused with the needed total in first[np] unless nothing is spawned
+        const int32_t st = eph_craft_batch_plot_segments(h_, static_cast<int64_t>(np), configs.data(), cr, body_parent.data(), 0, nullptr, out.first.data(),
+                                                         nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+        const size_t total = static_cast<size_t>(out.first[np]);
+        if (st != EPH_ERR_BAD_ARGUMENT || total == 0) detail::check(st, "eph_craft_batch_plot_segments");
+        if (total == 0) return out;
+        out.segments.resize(total);
+        int64_t capacity = 1;
+        for (const eph_orbit_plot_config &c : configs) capacity = c.max_points_per_segment > capacity ? c.max_points_per_segment : capacity;
+        const size_t cap = static_cast<size_t>(capacity);
+        std::vector<double> t(draw ? total * cap : 0), failed(total);
+        std::vector<float> xyz(draw ? total * cap * 3 : 0);
+        std::vector<int64_t> count(total);
+        std::vector<int32_t> status(total);
+        detail::check(eph_craft_batch_plot_segments(h_, static_cast<int64_t>(np), configs.data(), cr, body_parent.data(), static_cast<int64_t>(total),
+                                                    out.segments.data(), out.first.data(), draw ? &view : nullptr, capacity, t.data(), xyz.data(),
+                                                    count.data(), status.data(), failed.data()),
+                      "eph_craft_batch_plot_segments");
+        if (!draw) return out;
+        out.points.resize(total);
+        for (size_t s = 0; s < total; ++s) {
+            const size_t k = static_cast<size_t>(count[s]);
+            out.points[s].status = status[s];
+            out.points[s].failed_at = failed[s];
+            out.points[s].t.assign(t.begin() + static_cast<std::ptrdiff_t>(s * cap), t.begin() + static_cast<std::ptrdiff_t>(s * cap + k));
+            out.points[s].xyz.assign(xyz.begin() + static_cast<std::ptrdiff_t>(s * cap * 3), xyz.begin() + static_cast<std::ptrdiff_t>((s * cap + k) * 3));
+        }
+        return out;
+    }
     // setup_target_plotting's search (ephemeris_explorer/src/analysis.rs:344-366) for ships that live in the batch, on the device, from
     // the knots the batch holds: RelativeTrajectory::closest_separation_between(left, right, precision, max_iterations, distance) of
     // craft craft[p] (craft empty: request p is craft p) against body requests[p].target_body of the ephemeris or craft
