@@ -475,22 +475,8 @@ int32_t eph_solution_append(eph_solution *s, const eph_solution *tail, int32_t d
     // s == tail would insert a deque's own iterator range into itself (undefined behaviour); the reference's
     // append takes `other` by value, so aliasing cannot be expressed there
     if (!s || !tail || s == tail || s->s.splines.size() != tail->s.splines.size()) return EPH_ERR_BAD_ARGUMENT;
-    // check every spline first so a failure leaves `s` untouched (the reference would have panicked)
-    for (size_t b = 0; b < s->s.splines.size(); ++b) {
-        const UniformSpline &x = s->s.splines[b], &y = tail->s.splines[b];
-        if (x.interval != y.interval) return EPH_ERR_BAD_ARGUMENT;
-        if (direction > 0 ? (x.end() != y.start) : (x.start != y.end())) return EPH_ERR_BAD_ARGUMENT;
-    }
-    for (size_t b = 0; b < s->s.splines.size(); ++b) {
-        UniformSpline &x = s->s.splines[b];
-        const UniformSpline &y = tail->s.splines[b];
-        if (direction > 0) {   // append  trajectory.rs:528-534
-            x.polynomials.insert(x.polynomials.end(), y.polynomials.begin(), y.polynomials.end());
-        } else {               // prepend trajectory.rs:515-526
-            x.start = y.start;
-            x.polynomials.insert(x.polynomials.begin(), y.polynomials.begin(), y.polynomials.end());
-        }
-    }
+    if (!splines_contiguous(s->s.splines, tail->s.splines, direction > 0 ? 1 : -1, false)) return EPH_ERR_BAD_ARGUMENT;
+    splines_splice(s->s.splines, tail->s.splines, direction > 0 ? 1 : -1);
     return EPH_OK;
     EPH_GUARD_END
 }

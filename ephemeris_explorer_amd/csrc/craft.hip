@@ -452,6 +452,7 @@ static int32_t craft_run(eph_craft_batch *b, double t_end, unsigned step_limit) 
     // the reference's RwLock read guard (dynamics/mod.rs:84-85), held for the whole synchronous sweep: the table as it is NOW --
     // every append since the last call is seen, and none lands while the kernels read
     std::shared_lock<std::shared_mutex> table_lock(b->eph->mu);
+    StreamIdleOnExit idle(b->stream);      // (destroyed before the lock: an early error return lets no writer in under kernels in flight)
     if (!b->body_order.empty()) {
         EPH_LAUNCH("k_permute_bodies", k_permute_bodies, dim3((unsigned)((b->eph->n_bodies + 63) / 64)), dim3(64), b->stream,
                    b->eph->n_bodies, b->body_order_dev.p, b->eph->bodies.p, b->bodies_ordered.p);
@@ -464,7 +465,6 @@ static int32_t craft_run(eph_craft_batch *b, double t_end, unsigned step_limit) 
     a.coeffs = b->eph->coeffs.p; a.ncoef = b->eph->ncoef.p;
     a.time = b->time.p; a.y = b->y.p; a.next_h = b->next_h.p; a.klast = b->klast.p; a.kfirst = b->kfirst.p; a.last_knot_t = b->last_knot.p;
     a.retry = b->retry ? 1 : 0;
-    b->retry = false;
     a.n_attempts = b->n_attempts.p; a.rk_i = b->rk_i.p; a.steps = b->steps.p;
     a.cur_seg = b->cur_seg.p; a.status = b->status.p; a.nknots = b->nknots.p;
     a.seg_off = b->seg_off.p; a.segs = b->segs.p;
@@ -481,9 +481,11 @@ static int32_t craft_run(eph_craft_batch *b, double t_end, unsigned step_limit) 
     EPH_HIP(hipEventRecord(b->ev0, b->stream));
     int st = craft_launch(b->pv, b->stream, a, b->heterogeneous);
     if (st) return st;
+    b->retry = false;                      // consumed by a sweep that was launched: a failed launch leaves the batch re-armed
     if (b->events && (st = craft_events_search(b, b->stream))) return st;   // the app's SpacecraftSolout on the steps just taken
     EPH_HIP(hipEventRecord(b->ev1, b->stream));
     EPH_HIP(hipEventSynchronize(b->ev1));
+    idle.disarm();
     float ms = 0;
     EPH_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
     b->kernel_ms += ms;
@@ -568,10 +570,16 @@ int32_t eph_craft_batch_set_body_order(eph_craft_batch *b, const int32_t *order)
         // the sweep kernels walk a.bodies front to back: a permuted COPY of the ephemeris's table costs the kernels nothing (an index
         // array read inside the body loop cost the thread-per-craft kernel 5 %: 35.0 against 33.4 ms); craft_run re-gathers it from
         // the live table before every sweep (k_permute_bodies)
+        // built aside and swapped in: on any failure the batch keeps the order it had, or none
         int st;
-        if ((st = b->bodies_ordered.alloc((size_t)std::max(n, 1))) || (st = b->body_order_dev.alloc((size_t)std::max(n, 1)))) return st;
-        b->body_order.assign(order, order + n);
-        if (n) EPH_HIP(hipMemcpy(b->body_order_dev.p, order, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+        DevBuf<BodyEntry> ordered;
+        DevBuf<int> order_dev;
+        if ((st = ordered.alloc((size_t)std::max(n, 1))) || (st = order_dev.alloc((size_t)std::max(n, 1)))) return st;
+        std::vector<int32_t> host(order, order + n);
+        if (n) EPH_HIP(hipMemcpy(order_dev.p, order, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+        b->bodies_ordered.swap(ordered);
+        b->body_order_dev.swap(order_dev);
+        b->body_order.swap(host);
         return EPH_OK;
     EPH_GUARD_END
 }

@@ -238,8 +238,7 @@ int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which, const 
         off[(size_t)n] = (long long)segs.size();
         if (!segs.empty()) EPH_HIP(hipMemcpy(d_segs.p, segs.data(), sizeof(SegmentDev) * segs.size(), hipMemcpyHostToDevice));
         EPH_HIP(hipMemcpy(b->seg_off.p, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
-        std::swap(b->segs.p, d_segs.p);
-        std::swap(b->segs.count, d_segs.count);
+        b->segs.swap(d_segs);
         b->h_seg_off = std::move(off);
         b->h_segs = std::move(segs);
         b->params = next;

@@ -69,6 +69,7 @@ int32_t eph_debug_wg_cycles(int64_t *out8) {
 int32_t eph_debug_div(int64_t n, const double *a, const double *b, double *fast, double *ieee) { return debug_div_device(n, a, b, fast, ieee); }
 int32_t eph_debug_rsq(int64_t n, const double *x, double *rsq, double *h) { return debug_rsq_device(n, x, rsq, h); }
 int32_t eph_debug_pow(int64_t n, const double *x, double y, double *out) { return debug_pow_device(n, x, y, out); }
+int32_t eph_debug_fail_alloc(int32_t nth) { return debug_fail_alloc(nth); }
 
 }  // extern "C"
 #pragma GCC visibility pop

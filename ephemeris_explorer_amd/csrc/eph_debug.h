@@ -30,6 +30,10 @@ int32_t eph_debug_inv_r3_sweep(uint64_t seed, int64_t n, uint64_t *mismatches, u
 /* Tuning hook: zeros from the product library. A build with -DEPH_EXPERIMENTS=1 (scripts/build_exp.sh) returns the
  * single-workgroup kernel's per-phase tick accounting of its last launch (EPH_DEBUG_SMALL=4). */
 int32_t eph_debug_wg_cycles(int64_t *out8);
+/* Test hook: the nth device allocation the library makes on THIS thread from now (nth >= 1) returns EPH_ERR_OUT_OF_MEMORY with
+ * last-error text "injected allocation failure", before any HIP call, and the countdown disarms itself; 0 disarms it. A host
+ * function returns an error code: no device is touched. Returns what was left of the previous countdown (0 = it was disarmed). */
+int32_t eph_debug_fail_alloc(int32_t nth);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
-// ephemeris_table.hip -- the LIVE device table behind an eph_ephemeris (ephemeris_table.h): layout, incremental follow-up of the host
-// splines, and the eph_ephemeris_* entry points that create, grow, truncate, query and ship it.
+// ephemeris_table.hip -- the LIVE device table behind an eph_ephemeris (ephemeris_table.h): its one writer (plan, upload aside,
+// commit), and the eph_ephemeris_* entry points that create, grow, truncate, query and ship it.
 //
 // Mirrors (paths relative to the reference repository root):
 //   UniformSpline::{append, prepend, clear_before, clear_after, contains}   ephemeris/src/trajectory.rs:437-441,515-549
@@ -37,110 +37,103 @@ static void eph_fill_row(const Polynomial &p, double *row, int *nc) {
     std::memcpy(row, &p.c[0][0], sizeof(double) * 3 * (size_t)std::min(std::max(p.ncoef, 0), kDiv));
     *nc = p.ncoef;
 }
-// polynomials [first, first + count) of body b's host spline -> device rows starting at `row`
-static int eph_upload_rows(eph_ephemeris *e, int b, size_t first, size_t count, long long row) {
-    if (count == 0) return EPH_OK;
+// What a writer is about to do to the host splines, decided before anything is touched: per body the counts (the plan's input)
+// and the spline's start afterwards; `add` holds the incoming polynomials (null: a clear), which go behind (direction > 0) or in
+// front. Nothing here changes the handle.
+struct TableEdit {
+    std::vector<BodyUpdate> up;
+    std::vector<double> start;
+    const std::vector<UniformSpline> *add = nullptr;
+    int direction = 0;
+    explicit TableEdit(const eph_ephemeris *e) : up(e->splines.size()), start(e->splines.size()) {
+        for (size_t b = 0; b < start.size(); ++b) start[b] = e->splines[b].start;
+    }
+    void adds(const std::vector<UniformSpline> &ys, int dir) {
+        add = &ys; direction = dir;
+        for (size_t b = 0; b < up.size(); ++b) {
+            (dir > 0 ? up[b].add_back : up[b].add_front) = (long long)ys[b].polynomials.size();
+            if (dir < 0) start[b] = ys[b].start;
+        }
+    }
+    // polynomial i of body b's spline as it will be: an incoming one, or one of the kept range of the host spline
+    const Polynomial &at(const eph_ephemeris *e, size_t b, long long i) const {
+        const BodyUpdate &u = up[b];
+        const long long kept = (long long)e->splines[b].polynomials.size() - u.drop_front - u.drop_back;
+        if (i < u.add_front) return (*add)[b].polynomials[(size_t)i];
+        if (i >= u.add_front + kept) return (*add)[b].polynomials[(size_t)(i - u.add_front - kept)];
+        return e->splines[b].polynomials[(size_t)(i - u.add_front + u.drop_front)];
+    }
+};
+// one row range of the plan -> device rows of `coeffs` / `ncoef` (the table's own, or fresh ones nobody reads yet)
+static int eph_upload_rows(const eph_ephemeris *e, const TableEdit &ed, const RowUpload &r, double *coeffs, int *ncoef) {
+    const size_t count = (size_t)r.count;
     std::vector<double> co(count * kDiv * 3);
     std::vector<int> nc(count);
-    const UniformSpline &u = e->splines[(size_t)b];
-    for (size_t k = 0; k < count; ++k) eph_fill_row(u.polynomials[first + k], &co[k * kDiv * 3], &nc[k]);
-    EPH_HIP(hipMemcpy(e->coeffs.p + (size_t)row * kDiv * 3, co.data(), sizeof(double) * co.size(), hipMemcpyHostToDevice));
-    EPH_HIP(hipMemcpy(e->ncoef.p + row, nc.data(), sizeof(int) * nc.size(), hipMemcpyHostToDevice));
+    for (size_t k = 0; k < count; ++k) eph_fill_row(ed.at(e, (size_t)r.body, r.first + (long long)k), &co[k * kDiv * 3], &nc[k]);
+    EPH_HIP(hipMemcpy(coeffs + (size_t)r.row * kDiv * 3, co.data(), sizeof(double) * co.size(), hipMemcpyHostToDevice));
+    EPH_HIP(hipMemcpy(ncoef + r.row, nc.data(), sizeof(int) * nc.size(), hipMemcpyHostToDevice));
     return EPH_OK;
 }
-// host_bodies -> the device table (+ the refined reciprocals of the intervals, formed on the device like the sweep kernels would)
-static int eph_upload_bodies(eph_ephemeris *e) {
+// the entries of the table as it will be -> bodies_next (+ the refined reciprocals of the intervals, formed on the device like the
+// sweep kernels would); complete on the device when this returns
+static int eph_upload_bodies(eph_ephemeris *e, const TableEdit &ed, const std::vector<BodyRegion> &layout, const double *coeffs) {
     const int nb = e->n_bodies;
-    for (int b = 0; b < nb; ++b) {
-        const UniformSpline &u = e->splines[(size_t)b];
-        BodyEntry &be = e->host_bodies[(size_t)b];
-        be.start = u.start; be.interval = u.interval; be.mu = e->gm[(size_t)b];
-        be.npoly = (long long)u.polynomials.size();
-        be.span = u.interval * (double)u.polynomials.size();     // interval.scaled(len): the product UniformSpline::span() forms
-        be.rinv = 0.0; be.rows = e->coeffs.p + (size_t)be.coeff_off * kDiv * 3;
-    }
     if (!nb) return EPH_OK;
-    EPH_HIP(hipMemcpy(e->bodies.p, e->host_bodies.data(), sizeof(BodyEntry) * (size_t)nb, hipMemcpyHostToDevice));
-    EPH_LAUNCH("k_body_reciprocals", k_body_reciprocals, dim3((nb + 63) / 64), dim3(64), nullptr, nb, e->bodies.p);
+    std::vector<BodyEntry> host((size_t)nb);
+    for (int b = 0; b < nb; ++b) {
+        BodyEntry &be = host[(size_t)b];
+        be.start = ed.start[(size_t)b]; be.interval = e->splines[(size_t)b].interval; be.mu = e->gm[(size_t)b];
+        be.npoly = layout[(size_t)b].npoly;
+        be.span = be.interval * (double)be.npoly;                // interval.scaled(len): the product UniformSpline::span() forms
+        be.coeff_off = layout[(size_t)b].first_row();
+        be.rinv = 0.0; be.rows = coeffs + (size_t)be.coeff_off * kDiv * 3;
+    }
+    EPH_HIP(hipMemcpy(e->bodies_next.p, host.data(), sizeof(BodyEntry) * (size_t)nb, hipMemcpyHostToDevice));
+    EPH_LAUNCH("k_body_reciprocals", k_body_reciprocals, dim3((nb + 63) / 64), dim3(64), nullptr, nb, e->bodies_next.p);
     EPH_HIP(hipStreamSynchronize(nullptr));
     return EPH_OK;
 }
-// lay the table out afresh from the host splines: every body's region gets room for as many polynomials again behind it (and in
-// front, for a body that grows backwards)
-static int eph_rebuild(eph_ephemeris *e) {
-    const int nb = e->n_bodies;
-    e->host_bodies.assign((size_t)std::max(nb, 0), BodyEntry{});
-    e->base.assign((size_t)nb, 0);
-    e->cap.assign((size_t)nb, 0);
-    long long total = 0;
-    for (int b = 0; b < nb; ++b) {
-        const long long np = (long long)e->splines[(size_t)b].polynomials.size();
-        const long long room = std::max<long long>(np, 32);
-        const long long front = e->grows_front[(size_t)b] ? room : 0;
-        e->base[(size_t)b] = total;
-        e->cap[(size_t)b] = front + np + room;
-        e->host_bodies[(size_t)b].coeff_off = total + front;
-        total += e->cap[(size_t)b];
-    }
+// THE writer (ephemeris_table.h): plan from counts, do everything that can fail where no reader looks, commit. The caller holds the
+// exclusive lock and has validated `ed`; any error return leaves the handle exactly as it was.
+static int eph_write(eph_ephemeris *e, const TableEdit &ed) {
+    const bool live = e->coeffs.p != nullptr;                    // (a table being created has no rows yet, and stays revision 0)
+    TablePlan plan;
+    plan.fits = false;
+    if (live) plan = follow(e->layout, ed.up);
+    const bool afresh = !plan.fits;
     DevBuf<double> co;
     DevBuf<int> nc;
     int st;
-    if ((st = co.alloc((size_t)std::max<long long>(total, 1) * kDiv * 3)) || (st = nc.alloc((size_t)std::max<long long>(total, 1)))) return st;
-    std::swap(e->coeffs.p, co.p); std::swap(e->coeffs.count, co.count);
-    std::swap(e->ncoef.p, nc.p); std::swap(e->ncoef.count, nc.count);
-    if (!e->bodies.p && (st = e->bodies.alloc((size_t)std::max(nb, 1)))) return st;
-    for (int b = 0; b < nb; ++b)
-        if ((st = eph_upload_rows(e, b, 0, e->splines[(size_t)b].polynomials.size(), e->host_bodies[(size_t)b].coeff_off))) return st;
-    return eph_upload_bodies(e);
-}
-// the device table after the host splines changed: `back[b]` / `front[b]` polynomials were added behind / in front of body b,
-// `dropped_front[b]` removed from its front (clear_before); a truncation (clear_after) needs no row traffic at all
-static int eph_follow(eph_ephemeris *e, const std::vector<long long> &front, const std::vector<long long> &back,
-                      const std::vector<long long> &dropped_front) {
-    const int nb = e->n_bodies;
-    bool fits = true;
-    for (int b = 0; b < nb && fits; ++b) {
-        const BodyEntry &be = e->host_bodies[(size_t)b];
-        const long long off = be.coeff_off - e->base[(size_t)b] + dropped_front[(size_t)b];
-        const long long np = (long long)e->splines[(size_t)b].polynomials.size();     // already the new count
-        if (front[(size_t)b] > off || off - front[(size_t)b] + np > e->cap[(size_t)b]) fits = false;
+    if (afresh) {     // every body's region gets room for as many polynomials again, in buffers of their own
+        std::vector<long long> npoly;
+        std::vector<char> grows_front;
+        counts_after(e->layout, ed.up, &npoly, &grows_front);
+        plan = lay_out_afresh(npoly, grows_front);
+        if ((st = co.alloc((size_t)std::max<long long>(plan.total, 1) * kDiv * 3)) || (st = nc.alloc((size_t)std::max<long long>(plan.total, 1)))) return st;
+        const size_t nb = (size_t)std::max(e->n_bodies, 1);
+        if (!live && ((st = e->bodies.alloc(nb)) || (st = e->bodies_next.alloc(nb)))) return st;
     }
-    if (!fits) return eph_rebuild(e);
-    int st;
-    for (int b = 0; b < nb; ++b) {
-        BodyEntry &be = e->host_bodies[(size_t)b];
-        be.coeff_off += dropped_front[(size_t)b] - front[(size_t)b];
-        const size_t np = e->splines[(size_t)b].polynomials.size();
-        if ((st = eph_upload_rows(e, b, 0, (size_t)front[(size_t)b], be.coeff_off))) return st;
-        if ((st = eph_upload_rows(e, b, np - (size_t)back[(size_t)b], (size_t)back[(size_t)b], be.coeff_off + (long long)np - back[(size_t)b]))) return st;
+    double *coeffs = afresh ? co.p : e->coeffs.p;
+    int *ncoef = afresh ? nc.p : e->ncoef.p;
+    for (const RowUpload &r : plan.uploads)
+        if ((st = eph_upload_rows(e, ed, r, coeffs, ncoef))) return st;
+    if ((st = eph_upload_bodies(e, ed, plan.regions, coeffs))) return st;
+    // ---- commit: the insertions first (all bodies or none, host.h), then nothing that can fail
+    if (ed.add) splines_splice(e->splines, *ed.add, ed.direction);
+    for (size_t b = 0; b < e->splines.size(); ++b) {
+        std::deque<Polynomial> &x = e->splines[b].polynomials;
+        const BodyUpdate &u = ed.up[b];
+        const auto kept_end = x.end() - (std::ptrdiff_t)u.add_back;
+        x.erase(kept_end - (std::ptrdiff_t)u.drop_back, kept_end);       // (Polynomial is trivially copyable: closing the gap cannot throw)
+        const auto kept_begin = x.begin() + (std::ptrdiff_t)u.add_front;
+        x.erase(kept_begin, kept_begin + (std::ptrdiff_t)u.drop_front);
+        e->splines[b].start = ed.start[b];
     }
-    return eph_upload_bodies(e);
-}
-
-// The host splines have changed already when the device table follows them: if the incremental update fails half way (a copy, an
-// allocation), the table is laid out afresh from the host copy once before the error is reported, so that the two do not stay apart.
-static int eph_follow_or_rebuild(eph_ephemeris *e, const std::vector<long long> &front, const std::vector<long long> &back,
-                                 const std::vector<long long> &dropped_front) {
-    const int st = eph_follow(e, front, back, dropped_front);
-    if (st == EPH_OK) return st;
-    (void)hipGetLastError();
-    return eph_rebuild(e) == EPH_OK ? EPH_OK : st;
-}
-
-// UniformSpline::append (direction > 0) / prepend of `y` on body b's host spline (trajectory.rs:515-534, asserts checked by the caller);
-// counts the polynomials added behind / in front for eph_follow
-static void eph_splice(eph_ephemeris *e, size_t b, const UniformSpline &y, int direction, std::vector<long long> &front,
-                       std::vector<long long> &back) {
-    UniformSpline &x = e->splines[b];
-    if (direction > 0) {
-        x.polynomials.insert(x.polynomials.end(), y.polynomials.begin(), y.polynomials.end());
-        back[b] = (long long)y.polynomials.size();
-    } else {
-        x.start = y.start;
-        x.polynomials.insert(x.polynomials.begin(), y.polynomials.begin(), y.polynomials.end());
-        front[b] = (long long)y.polynomials.size();
-        if (front[b]) e->grows_front[b] = 1;
-    }
+    if (afresh) { e->coeffs.swap(co); e->ncoef.swap(nc); }
+    e->bodies.swap(e->bodies_next);
+    e->layout = std::move(plan.regions);
+    if (live) e->revision += 1;
+    return EPH_OK;
 }
 
 #pragma GCC visibility push(default)
@@ -159,8 +152,9 @@ int32_t eph_ephemeris_create(const eph_solution *s, const double *mu, eph_epheme
         for (const UniformSpline &u : e->splines)
             if (u.ghost) return EPH_ERR_BAD_ARGUMENT;             // (only inside a propagator; never in a Solution handed out)
         e->gm.assign(mu, mu + nb);
-        e->grows_front.assign((size_t)nb, 0);
-        if ((st = eph_rebuild(e.get()))) return st;
+        e->layout.assign((size_t)nb, BodyRegion{});              // no rows yet: the first write lays the table out
+        for (int b = 0; b < nb; ++b) e->layout[(size_t)b].npoly = (long long)e->splines[(size_t)b].polynomials.size();
+        if ((st = eph_write(e.get(), TableEdit(e.get())))) return st;
         *out = e.release();
         return EPH_OK;
     EPH_GUARD_END
@@ -171,19 +165,13 @@ void eph_ephemeris_destroy(eph_ephemeris *e) { delete e; }
 // with the table untouched
 int32_t eph_ephemeris_append(eph_ephemeris *e, const eph_solution *tail, int32_t direction) {
     EPH_GUARD_BEGIN
-        if (!e || !tail || direction == 0 || tail->s.splines.size() != e->splines.size()) return EPH_ERR_BAD_ARGUMENT;
+        if (!e || !tail || direction == 0) return EPH_ERR_BAD_ARGUMENT;
         std::unique_lock<std::shared_mutex> lock(e->mu);
-        const size_t nb = e->splines.size();
-        for (size_t b = 0; b < nb; ++b) {
-            const UniformSpline &x = e->splines[b], &y = tail->s.splines[b];
-            if (y.ghost || x.interval != y.interval) return EPH_ERR_BAD_ARGUMENT;
-            if (direction > 0 ? (x.end() != y.start) : (x.start != y.end())) return EPH_ERR_BAD_ARGUMENT;
-        }
+        if (!splines_contiguous(e->splines, tail->s.splines, direction, true)) return EPH_ERR_BAD_ARGUMENT;
         EPH_HIP(hipSetDevice(e->device));
-        std::vector<long long> front(nb, 0), back(nb, 0), none(nb, 0);
-        for (size_t b = 0; b < nb; ++b) eph_splice(e, b, tail->s.splines[b], direction, front, back);
-        e->revision += 1;
-        return eph_follow_or_rebuild(e, front, back, none);
+        TableEdit ed(e);
+        ed.adds(tail->s.splines, direction > 0 ? 1 : -1);
+        return eph_write(e, ed);
     EPH_GUARD_END
 }
 // UniformSpline::clear_before (after = 0, trajectory.rs:536-542) / clear_after (after != 0, :544-549) on body's spline or on all (body < 0)
@@ -192,17 +180,20 @@ int32_t eph_ephemeris_clear(eph_ephemeris *e, int32_t body, double at, int32_t a
         if (!e || body >= e->n_bodies) return EPH_ERR_BAD_ARGUMENT;
         std::unique_lock<std::shared_mutex> lock(e->mu);
         EPH_HIP(hipSetDevice(e->device));
-        const size_t nb = e->splines.size();
-        std::vector<long long> none(nb, 0), dropped(nb, 0);
-        for (size_t b = 0; b < nb; ++b) {
+        TableEdit ed(e);
+        for (size_t b = 0; b < e->splines.size(); ++b) {
             if (body >= 0 && (size_t)body != b) continue;
-            UniformSpline &u = e->splines[b];
-            const size_t before = u.polynomials.size();
-            if (after) u.clear_after(at);
-            else { u.clear_before(at); dropped[b] = (long long)(before - u.polynomials.size()); }
+            const UniformSpline &u = e->splines[b];
+            const uint64_t np = u.polynomials.size();
+            uint64_t idx;
+            if (after) {                                                               // truncate(idx)
+                if (u.get_index_local(at - u.start, &idx) && idx < np) ed.up[b].drop_back = (long long)(np - idx);
+            } else if (u.get_index_local_exclusive((at + u.interval) - u.start, &idx)) {   // drain(0..idx)
+                ed.start[b] = u.start + u.interval * (double)idx;
+                ed.up[b].drop_front = (long long)std::min(idx, np);
+            }
         }
-        e->revision += 1;
-        return eph_follow_or_rebuild(e, none, none, dropped);
+        return eph_write(e, ed);
     EPH_GUARD_END
 }
 // CelestialTrajectory::merge  ephemeris_explorer/src/dynamics/celestial.rs:198-204 (Forward: clear_after(propagated.start()) then
@@ -212,17 +203,21 @@ int32_t eph_ephemeris_merge(eph_ephemeris *e, const eph_solution *propagated, in
         if (!e || !propagated || direction == 0 || propagated->s.splines.size() != e->splines.size()) return EPH_ERR_BAD_ARGUMENT;
         std::unique_lock<std::shared_mutex> lock(e->mu);
         const size_t nb = e->splines.size();
-        // the reference's asserts, evaluated on copies of the bounds first so that a refusal leaves the table untouched
+        TableEdit ed(e);
+        // the reference's asserts, evaluated on copies of the bounds first so that a refusal leaves the table untouched; what the
+        // clear drops is counted on the way
         for (size_t b = 0; b < nb; ++b) {
             const UniformSpline &y = propagated->s.splines[b];
+            const uint64_t np = e->splines[b].polynomials.size();
             UniformSpline x;
             x.start = e->splines[b].start; x.interval = e->splines[b].interval;
-            x.ghost = e->splines[b].polynomials.size();            // bounds only: no polynomial is copied
+            x.ghost = np;                                          // bounds only: no polynomial is copied
             if (y.ghost || x.interval != y.interval) return EPH_ERR_BAD_ARGUMENT;
             if (direction > 0) {
                 uint64_t idx;
                 if (x.get_index_local(y.start - x.start, &idx) && idx < x.ghost) x.ghost = idx;       // clear_after
                 if (x.end() != y.start) return EPH_ERR_BAD_ARGUMENT;
+                ed.up[b].drop_back = (long long)(np - x.ghost);
             } else {
                 uint64_t idx;
                 if (x.get_index_local_exclusive((y.end() + x.interval) - x.start, &idx)) {             // clear_before
@@ -230,23 +225,12 @@ int32_t eph_ephemeris_merge(eph_ephemeris *e, const eph_solution *propagated, in
                     x.ghost -= std::min<uint64_t>(idx, x.ghost);
                 }
                 if (x.start != y.end()) return EPH_ERR_BAD_ARGUMENT;
+                ed.up[b].drop_front = (long long)(np - x.ghost);
             }
         }
         EPH_HIP(hipSetDevice(e->device));
-        std::vector<long long> front(nb, 0), back(nb, 0), dropped(nb, 0);
-        for (size_t b = 0; b < nb; ++b) {
-            UniformSpline &x = e->splines[b];
-            const UniformSpline &y = propagated->s.splines[b];
-            if (direction > 0) x.clear_after(y.start);
-            else {
-                const size_t before = x.polynomials.size();
-                x.clear_before(y.end());
-                dropped[b] = (long long)(before - x.polynomials.size());
-            }
-            eph_splice(e, b, y, direction, front, back);
-        }
-        e->revision += 1;
-        return eph_follow_or_rebuild(e, front, back, dropped);
+        ed.adds(propagated->s.splines, direction > 0 ? 1 : -1);
+        return eph_write(e, ed);
     EPH_GUARD_END
 }
 int32_t eph_ephemeris_info(const eph_ephemeris *e, int32_t body, double *start, double *interval, int64_t *npoly, uint64_t *revision) {

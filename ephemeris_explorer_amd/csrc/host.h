@@ -27,6 +27,9 @@ int dev_alloc(size_t bytes, void **out);
 void dev_free(void *p, size_t bytes);
 size_t release_cached_memory();
 size_t cached_memory_bytes();
+// test hook (eph_debug.h): the nth dev_alloc from now on this thread returns EPH_ERR_OUT_OF_MEMORY ("injected allocation failure")
+// before it makes any HIP call, and disarms the countdown; 0 disarms it. Returns what was left of the previous countdown.
+int debug_fail_alloc(int nth);
 // A pinned, device-mapped staging buffer taken from the library's pool for the life of the object (mem.cpp; one per concurrent user,
 // so handles driven from distinct threads do not wait for each other): a kernel stores through dev(), the host reads host() after
 // synchronising the kernel's stream. The stream must be idle with respect to the buffer before the object is destroyed.
@@ -87,6 +90,8 @@ struct DevBuf {   // owning device allocation
         return EPH_OK;
     }
     int reserve(size_t n) { return n <= count ? EPH_OK : alloc(n + n / 2); }   // grow-only scratch; contents are lost
+    // cannot fail: how a handle takes over a buffer that was allocated and filled aside (the old one leaves with `o`)
+    void swap(DevBuf &o) noexcept { std::swap(p, o.p); std::swap(count, o.count); }
 };
 // a fresh allocation holding src[0, count) (DevBuf::alloc makes an empty one one element long): a blocking copy on the null stream
 template <typename T>
@@ -340,6 +345,40 @@ struct UniformSpline {
 struct Solution {   // Vec<UniformSpline<DVec3>>
     std::vector<UniformSpline> splines;
 };
+// UniformSpline::append (direction > 0) / prepend (< 0) of ys[b] onto xs[b] for every body  trajectory.rs:515-534, in two halves so
+// that a refusal or a failure leaves `xs` untouched (the reference would have panicked).
+// The asserts: equal intervals and touching ends; `refuse_ghost`: ys must hold every polynomial its bounds count.
+inline bool splines_contiguous(const std::vector<UniformSpline> &xs, const std::vector<UniformSpline> &ys, int direction, bool refuse_ghost) {
+    if (direction == 0 || xs.size() != ys.size()) return false;
+    for (size_t b = 0; b < xs.size(); ++b) {
+        const UniformSpline &x = xs[b], &y = ys[b];
+        if ((refuse_ghost && y.ghost) || x.interval != y.interval) return false;
+        if (direction > 0 ? (x.end() != y.start) : (x.start != y.end())) return false;
+    }
+    return true;
+}
+// The splice, all bodies or none: an insertion at an end of a deque either succeeds or has no effect, so when body k throws the
+// bodies before it give back what they received (erasing at an end does not throw) and the exception goes on.
+inline void splines_splice(std::vector<UniformSpline> &xs, const std::vector<UniformSpline> &ys, int direction) {
+    size_t b = 0;
+    try {
+        for (; b < xs.size(); ++b) {
+            std::deque<Polynomial> &x = xs[b].polynomials;
+            const std::deque<Polynomial> &y = ys[b].polynomials;
+            x.insert(direction > 0 ? x.end() : x.begin(), y.begin(), y.end());
+        }
+    } catch (...) {
+        while (b-- > 0) {
+            std::deque<Polynomial> &x = xs[b].polynomials;
+            const std::ptrdiff_t k = (std::ptrdiff_t)ys[b].polynomials.size();
+            if (direction > 0) x.erase(x.end() - k, x.end());
+            else x.erase(x.begin(), x.begin() + k);
+        }
+        throw;
+    }
+    if (direction < 0)
+        for (size_t k = 0; k < xs.size(); ++k) xs[k].start = ys[k].start;
+}
 
 // SplineInterpolator   ephemeris/src/propagators/nbody.rs:309-323
 struct SplineInterpolator {

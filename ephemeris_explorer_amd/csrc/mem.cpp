@@ -60,10 +60,22 @@ void take_device_locked(int device, std::vector<void *> *out) {
     }
     g_pool_bytes[device] = 0;
 }
+// test hook (eph_debug_fail_alloc): the n-th dev_alloc from now on this thread fails; 0 = not armed
+thread_local int g_fail_alloc_in = 0;
 }  // namespace
+
+int debug_fail_alloc(int nth) {
+    const int before = g_fail_alloc_in;
+    g_fail_alloc_in = std::max(nth, 0);
+    return before;
+}
 
 int dev_alloc(size_t bytes, void **out) {
     *out = nullptr;
+    if (g_fail_alloc_in > 0 && --g_fail_alloc_in == 0) {          // one shot, before any HIP call
+        set_last_error_text("injected allocation failure");
+        return EPH_ERR_OUT_OF_MEMORY;
+    }
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= kMaxDevices) device = -1;
     if (bytes >= kPoolMinBytes && device >= 0) {

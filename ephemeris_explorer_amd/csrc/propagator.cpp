@@ -167,8 +167,8 @@ int NBodyPropagator::reserve_pending(size_t extra, hipStream_t s) {
             EPH_HIP(hipMemcpyAsync(nc.p, pend_nc_.p, sizeof(int32_t) * pend_count_, hipMemcpyDeviceToDevice, s));
             EPH_HIP(hipStreamSynchronize(s));
         }
-        std::swap(pend_co_.p, co.p); std::swap(pend_co_.count, co.count);
-        std::swap(pend_nc_.p, nc.p); std::swap(pend_nc_.count, nc.count);
+        pend_co_.swap(co);
+        pend_nc_.swap(nc);
         pend_cap_ = cap;
         return EPH_OK;
     }

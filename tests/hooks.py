@@ -33,6 +33,7 @@ class Hooks:
         L.eph_debug_div.argtypes = [i64, _dp, _dp, _dp, _dp]
         L.eph_debug_rsq.argtypes = [i64, _dp, _dp, _dp]
         L.eph_debug_wg_cycles.argtypes = [C.POINTER(C.c_int64)]
+        L.eph_debug_fail_alloc.argtypes = [C.c_int32]
         L.eph_status_string.restype = C.c_char_p
         L.eph_status_string.argtypes = [C.c_int32]
         self.L = L
@@ -93,6 +94,11 @@ class Hooks:
         out = (C.c_int64 * 8)()
         self._check(self.L.eph_debug_wg_cycles(out), "eph_debug_wg_cycles")
         return list(out)
+
+    def fail_alloc(self, nth):
+        """arm: the nth device allocation this library makes on this thread from now fails with ERR_OUT_OF_MEMORY (one shot);
+        0 disarms. -> what was left of the previous countdown (0: it was disarmed)"""
+        return int(self.L.eph_debug_fail_alloc(int(nth)))
 
 
 _cache = {}
