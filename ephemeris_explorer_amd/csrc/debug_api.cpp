@@ -71,5 +71,15 @@ int32_t eph_debug_rsq(int64_t n, const double *x, double *rsq, double *h) { retu
 int32_t eph_debug_pow(int64_t n, const double *x, double y, double *out) { return debug_pow_device(n, x, y, out); }
 int32_t eph_debug_fail_alloc(int32_t nth) { return debug_fail_alloc(nth); }
 
+// host only: the same two helpers launch_lm_step_fast and lm_step_fast call, so a test never restates the partition policy
+int32_t eph_debug_fast_partition(int32_t npad, int32_t path, int32_t *S, int32_t *slice_len) {
+    if (npad < 64 || npad % 64 || !S || !slice_len) return EPH_ERR_BAD_ARGUMENT;
+    if (path != EPH_PATH_FAST && path != EPH_PATH_FAST_RSQ && path != EPH_PATH_F32_PAIRS) return EPH_ERR_BAD_ARGUMENT;
+    const bool approx = path == EPH_PATH_FAST_RSQ, f32 = path == EPH_PATH_F32_PAIRS;
+    *S = fast_slices(npad, approx);
+    *slice_len = fast_slice_len(npad, *S, fast_unroll(), approx, f32);
+    return EPH_OK;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -34,6 +34,10 @@ int32_t eph_debug_wg_cycles(int64_t *out8);
  * last-error text "injected allocation failure", before any HIP call, and the countdown disarms itself; 0 disarms it. A host
  * function returns an error code: no device is touched. Returns what was left of the previous countdown (0 = it was disarmed). */
 int32_t eph_debug_fail_alloc(int32_t nth);
+/* Test hook: the partition of the sources that a steady step of `path` (EPH_PATH_FAST, EPH_PATH_FAST_RSQ or EPH_PATH_F32_PAIRS)
+ * uses in THIS process for a system padded to npad bodies -- S slices of slice_len consecutive sources, EPH_FAST_SLICES and
+ * EPH_FAST_UNROLL honoured. A host function: no device is touched. */
+int32_t eph_debug_fast_partition(int32_t npad, int32_t path, int32_t *S, int32_t *slice_len);
 
 #ifdef __cplusplus
 }

@@ -132,6 +132,12 @@ constexpr int kGangMaxN = 32;
 int launch_lm_small_many(int pv, hipStream_t s, const LmArgs *argv_dev, int count, int L, int64_t nsteps);
 // opt-in fast path: slice-parallel partial sums combined in slice order (NOT the reference's summation order)
 int fast_slices(int npad, bool approx = false);                     // S (the rsq form takes twice the waves)
+#ifndef EPH_F32_GROUP
+#define EPH_F32_GROUP 32
+#endif
+constexpr int kF32Group = EPH_F32_GROUP;         // EPH_PATH_F32_PAIRS: sources per conversion to f64 (slices are multiples of it)
+int fast_unroll();                               // sources per trip of the IEEE form's loop (EPH_FAST_UNROLL: 4, or 8)
+int fast_slice_len(int npad, int S, int unroll, bool approx, bool f32);     // sources per slice: npad / S rounded up to the loop's trip
 // posf: EPH_PATH_F32_PAIRS scratch, 4 floats per padded body. f32_stage 0: the whole step; 1: only the binary32 copy of rows
 // [conv_lo, conv_lo + conv_cnt) (conv_cnt < 0: all); 2: the step on a copy that is complete already (a sharded handle gathers between)
 size_t fast_partial_doubles(int npad);           // scratch of the fast paths incl. the arrival tickets behind the partial sums

@@ -23,6 +23,8 @@ namespace EPH_PV_NS {
 // by a second small launch (k_fast_finish), which also does the Cowell velocity, the solout sample and the
 // predictor -- deterministic: the value never depends on which wave finishes first.
 //   a_i = ((p_0 + p_1) + ... + p_{S-1}),  p_s = ((0 + c(i, j0)) + c(i, j0 + 1)) + ...   (j over slice s, j != i)
+// for S and slice_len of dispatch.cpp (fast_slices, fast_slice_len) -- held to it bit for bit, in every form, against a CPU restatement
+// of exactly this formula (tests/test_gpu_fast_reference.py; the other two paths to bounds counted from their operations).
 // ------------------------------------------------------------------------------------------------------
 constexpr int kFastWaves = 4;                          // waves (= slices) per workgroup
 constexpr int kFastMaxSlices = 64;
@@ -189,10 +191,6 @@ __global__ void __launch_bounds__(64 * kFastWaves) k_fast_partial(int n, int npa
 // instructions arrive in consecutive scalar registers straight from s_load_dwordx16 (the AoS form needed 13 s_mov per 4 sources).
 // ------------------------------------------------------------------------------------------------------
 typedef float v2f __attribute__((ext_vector_type(2)));
-#ifndef EPH_F32_GROUP
-#define EPH_F32_GROUP 32
-#endif
-constexpr int kF32Group = EPH_F32_GROUP;               // sources per conversion to f64 (slices are multiples of it)
 // rows [lo, lo + cnt) of the binary32 copy (a sharded handle converts the rows it owns: they are what it sends)
 __global__ void __launch_bounds__(256) k_pos_to_f32(int n, int lo, int cnt, const Body4 *__restrict__ pos, float *__restrict__ out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -403,9 +401,7 @@ __global__ void __launch_bounds__(64 * kFastWaves) k_fast_step_f32(const LmArgs 
 // handle: its own rows, which it then all-gathers); 2 = the step on a copy that is already complete
 int lm_step_fast(hipStream_t s, const LmArgs &a, double *partial, int S, int unroll, bool approx, float *posf, int f32_stage,
                  int conv_lo, int conv_cnt, unsigned *tickets) {
-    int slice_len = (a.npad + S - 1) / S;
-    const int un = posf ? kF32Group : approx ? 4 : unroll;   // (8 sources per trip spill 149 SGPRs: the prefetched group is 64 of the 102)
-    slice_len = (slice_len + un - 1) / un * un;
+    const int slice_len = fast_slice_len(a.npad, S, unroll, approx, posf != nullptr);
     const int block0 = a.lo / 64, nblocks = (a.hi - a.lo + 63) / 64;    // (a.lo is a multiple of 64 on a sharded handle, else 0)
     if (!posf && (a.lo != 0 || a.hi != a.n)) return EPH_ERR_UNSUPPORTED;
     if (a.L != 12 && a.L != 13) return EPH_ERR_UNSUPPORTED;

@@ -226,8 +226,44 @@ static void gravity_eval_rows(int n, const v3 *y, const double *mu, v3 *ddy) {
         ddy[i] = acc;
     }
 }
+/* The device's OPT-IN fast path (csrc/fast.hip, EPH_PATH_FAST) restated: the same directed pair terms, summed in S slices of
+ * slice_len consecutive SOURCES each instead of the reference's order. For every target i
+ *     p_s = ((0 + c(i, j0)) + c(i, j0 + 1)) + ...   over the real sources j0 = s * slice_len <= j < min(j0 + slice_len, n), j != i
+ *     sum = ((p_0 + p_1) + ...) + p_{S-1}           an empty slice contributes +0.0
+ *     ddy[i] += sum
+ * with c(i, j) = point_mass_term(p_j - p_i, n2, mu_j) in the selected order. Off (0, 0) unless orc_set_gravity_slices is called; read at
+ * evaluation time, so a run can start up in the reference's order and continue sliced (what eph_nbody_set_path does: the path applies
+ * to the steady steps). Tests only. */
+static int g_gravity_slices = 0, g_gravity_slice_len = 0;
+void orc_set_gravity_slices(int S, int slice_len) {
+    const int on = S > 0 && slice_len > 0;
+    g_gravity_slices = on ? S : 0;
+    g_gravity_slice_len = on ? slice_len : 0;
+}
+static void gravity_eval_sliced(int n, const v3 *y, const double *mu, v3 *ddy) {
+    const int S = g_gravity_slices, len = g_gravity_slice_len;
+    for (int i = 0; i < n; ++i) {
+        v3 sum = {0.0, 0.0, 0.0};
+        for (int s = 0; s < S; ++s) {
+            const int64_t j0 = (int64_t)s * len;
+            const int64_t j1 = j0 + len < n ? j0 + len : n;
+            v3 part = {0.0, 0.0, 0.0};
+            for (int64_t j = j0; j < j1; ++j) {
+                if (j == i) continue;
+                const v3 d = {y[j].x - y[i].x, y[j].y - y[i].y, y[j].z - y[i].z};
+                const double n2 = d.x * d.x + d.y * d.y + d.z * d.z;
+                const v3 c = point_mass_term(d, n2, mu[j]);
+                part.x += c.x; part.y += c.y; part.z += c.z;
+            }
+            sum.x += part.x; sum.y += part.y; sum.z += part.z;
+        }
+        ddy[i].x += sum.x; ddy[i].y += sum.y; ddy[i].z += sum.z;
+    }
+    g_pair_counter += (uint64_t)n * (uint64_t)(n - 1);  /* DIRECTED terms here, two per pair: the counter feeds bench.py's ns/pair, which never runs sliced */
+}
 void orc_newtonian_gravity_eval(int n, const double *y, const double *mu, double *ddy) {
-    if (g_gravity_threads > 1) gravity_eval_rows(n, (const v3 *)y, mu, (v3 *)ddy);
+    if (g_gravity_slices > 0) gravity_eval_sliced(n, (const v3 *)y, mu, (v3 *)ddy);
+    else if (g_gravity_threads > 1) gravity_eval_rows(n, (const v3 *)y, mu, (v3 *)ddy);
     else gravity_eval(n, (const v3 *)y, mu, (v3 *)ddy);
 }
 
@@ -247,7 +283,8 @@ static v3 *v3_dup(const v3 *s, int n) { v3 *d = v3_alloc(n); memcpy(d, s, sizeof
 static void v3_zero(v3 *v, int n) { for (int i = 0; i < n; ++i) v[i].x = v[i].y = v[i].z = 0.0; }
 
 static void ode_eval(problem_t *p, const v3 *y, v3 *ddy_zeroed) {
-    if (g_gravity_threads > 1) gravity_eval_rows(p->n, y, p->mu, ddy_zeroed);
+    if (g_gravity_slices > 0) gravity_eval_sliced(p->n, y, p->mu, ddy_zeroed);
+    else if (g_gravity_threads > 1) gravity_eval_rows(p->n, y, p->mu, ddy_zeroed);
     else gravity_eval(p->n, y, p->mu, ddy_zeroed);
     p->evals++;
 }

@@ -59,6 +59,10 @@ int orc_erk_coeffs(const char *name, int *stages, int *order, int *order_embedde
 void orc_set_gravity_threads(int threads);
 /* tests only: 0 = the pinned pair formula, 1..3 = other plausible evaluation orders of 1/r^3 (sensitivity study) */
 void orc_set_pair_variant(int variant);
+/* tests only: the device's opt-in EPH_PATH_FAST summation restated -- every target's directed terms c(i, j) chained in source order
+ * within S slices of slice_len consecutive sources, the S partial sums then added in slice order (eph_oracle.c gravity_eval_sliced).
+ * (0, 0) = off, the default. Process-wide, read at every evaluation: orc_newtonian_gravity_eval and every integrator follow it. */
+void orc_set_gravity_slices(int S, int slice_len);
 void orc_newtonian_gravity_eval(int n, const double *y, const double *mu, double *ddy);
 /* number of (paired) interactions evaluated since process start -- used by bench.py for ns/pair */
 uint64_t orc_pair_counter(void);

@@ -3,6 +3,7 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module; the product
 package `ephemeris_explorer_amd` never does.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -55,6 +56,8 @@ def lib(native=False):
     L.orc_newtonian_gravity_eval.argtypes = [C.c_int, _dp, _dp, _dp]
     L.orc_newtonian_gravity_eval.restype = None
     L.orc_pair_counter.restype = C.c_uint64
+    L.orc_set_gravity_slices.argtypes = [C.c_int, C.c_int]
+    L.orc_set_gravity_slices.restype = None
     L.orc_double_solve.argtypes = [C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_char_p, C.c_int64,
                                    _dp, _dp, _dp]
     L.orc_convergence.restype = C.c_double
@@ -384,6 +387,22 @@ def convergence(pos, vel, mu, t0, bound, method, h0=75.0, native=False):
 def set_pair_variant(variant, native=False):
     """tests only: evaluation order of 1/r^3 in the pair interaction (0 = pinned restatement, 1..3 = alternatives)."""
     lib(native).orc_set_pair_variant(int(variant))
+
+
+def set_gravity_slices(S, slice_len, native=False):
+    """tests only: every gravity evaluation from now sums each target's terms in S slices of slice_len consecutive sources, the
+    partial sums in slice order (the device's EPH_PATH_FAST); (0, 0) = the reference's order again."""
+    lib(native).orc_set_gravity_slices(int(S), int(slice_len))
+
+
+@contextlib.contextmanager
+def gravity_slices(S, slice_len, native=False):
+    """`with orc.gravity_slices(S, slice_len): ...` -- the sliced sums inside, the reference's order restored on exit"""
+    set_gravity_slices(S, slice_len, native)
+    try:
+        yield
+    finally:
+        set_gravity_slices(0, 0, native)
 
 
 def set_gravity_threads(threads, native=False):

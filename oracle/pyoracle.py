@@ -104,6 +104,25 @@ def gravity(y, mu, zero, sqrt=math.sqrt):
     return ddy
 
 
+def gravity_sliced(y, mu, zero, S, slice_len, sqrt=math.sqrt):
+    """The device's opt-in EPH_PATH_FAST summation (csrc/fast.hip), not the reference's: per target, the directed terms of the
+    sources of slice s = [s * slice_len, (s + 1) * slice_len) chained in source order from 0, the S slice sums then chained in slice
+    order from the first (an empty slice is +0.0), and that added to the zeroed output."""
+    n = len(y)
+    ddy = []
+    for i in range(n):
+        total = None
+        for s in range(S):
+            part = Vec(zero, zero, zero)
+            for j in range(s * slice_len, min((s + 1) * slice_len, n)):
+                if j != i:
+                    d = y[j] - y[i]
+                    part = part + point_mass_term(d, d[0] * d[0] + d[1] * d[1] + d[2] * d[2], mu[j], sqrt)
+            total = part if total is None else total + part
+        ddy.append(Vec(zero, zero, zero) + total)
+    return ddy
+
+
 class Srkn:
     """SRKN<C, V> (integration/src/runge_kutta/nystrom/symplectic.rs:36-102)."""
 
@@ -142,9 +161,15 @@ class Problem:
         self.time = num(t0)
         self.evals = 0
         self.bound = math.inf                 # NBodyProblem::bound (f64::INFINITY until set_bound)
+        self.slices = None                    # tests: (S, slice_len) -> gravity_sliced from the next evaluation on
+
+    def set_gravity_slices(self, S, slice_len):
+        self.slices = (int(S), int(slice_len)) if S > 0 and slice_len > 0 else None
 
     def eval(self, y):
         self.evals += 1
+        if self.slices:
+            return gravity_sliced(y, self.mu, self.num(0), *self.slices, sqrt=self.sqrt)
         return gravity(y, self.mu, self.num(0), self.sqrt)
 
 

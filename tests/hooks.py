@@ -34,6 +34,7 @@ class Hooks:
         L.eph_debug_rsq.argtypes = [i64, _dp, _dp, _dp]
         L.eph_debug_wg_cycles.argtypes = [C.POINTER(C.c_int64)]
         L.eph_debug_fail_alloc.argtypes = [C.c_int32]
+        L.eph_debug_fast_partition.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.eph_status_string.restype = C.c_char_p
         L.eph_status_string.argtypes = [C.c_int32]
         self.L = L
@@ -99,6 +100,13 @@ class Hooks:
         """arm: the nth device allocation this library makes on this thread from now fails with ERR_OUT_OF_MEMORY (one shot);
         0 disarms. -> what was left of the previous countdown (0: it was disarmed)"""
         return int(self.L.eph_debug_fail_alloc(int(nth)))
+
+    def fast_partition(self, npad, path):
+        """(S, slice_len): the slices a steady step of `path` (4, 5 or 6) cuts npad padded sources into in this process
+        (EPH_FAST_SLICES / EPH_FAST_UNROLL honoured). Host only."""
+        S, sl = C.c_int32(), C.c_int32()
+        self._check(self.L.eph_debug_fast_partition(int(npad), int(path), C.byref(S), C.byref(sl)), "eph_debug_fast_partition")
+        return S.value, sl.value
 
 
 _cache = {}

@@ -171,14 +171,14 @@ def test_cpp_operator_surface_compiles_and_links(product_lib, tmp_path):
 
 
 def test_debug_hooks_are_not_in_the_product(product_lib):
-    """csrc/eph_debug.h: the eight eph_debug_* hooks are exported by the test-hooks library (the product's objects + debug_api.o + debug_kernels.o)
+    """csrc/eph_debug.h: the nine eph_debug_* hooks are exported by the test-hooks library (the product's objects + debug_api.o + debug_kernels.o)
     and by tuning builds, never by libephemeris_amd.so; the product exports the header's functions and no other eph_* name."""
     hooks_lib = product_lib.LIB_PATH.with_name("libephemeris_amd_testhooks.so")
     assert hooks_lib.exists(), "ephemeris_explorer_amd.build builds it beside the product"
     text = (ROOT / "ephemeris_explorer_amd" / "csrc" / "eph_debug.h").read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     debug = sorted(set(re.findall(r"\b(eph_debug_[a-z0-9_]+)\s*\(", text)))
-    assert len(debug) == 8
+    assert len(debug) == 9
     assert not any(n.startswith("eph_debug") for n in header_functions())
 
     def exported(path):
