@@ -749,6 +749,33 @@ void orc_solution_clear(orc_solution *so, int body, double at, int after) {
     }
 }
 orc_solution *orc_solution_clone(const orc_solution *src) { return solution_clone(src); }
+/* Vec<UniformSpline> from its parts (tests: tables that no propagator fitted). The layout orc_solution_coeffs writes: polynomial p
+ * of the concatenated list (body 0's first) has its coefficient k at coeffs[(p*8+k)*3 + c]; ncoef[p] rows are copied and nothing
+ * at or beyond them is read. NULL for a negative count or a coefficient count outside 0..8. */
+orc_solution *orc_solution_create(int n, const double *start, const double *interval, const int64_t *npoly, const double *coeffs,
+                                  const int32_t *ncoef) {
+    if (n < 0) return NULL;
+    int64_t total = 0;
+    for (int b = 0; b < n; ++b) {
+        if (npoly[b] < 0) return NULL;
+        for (int64_t p = 0; p < npoly[b]; ++p, ++total)
+            if (ncoef[total] < 0 || ncoef[total] > DIV) return NULL;
+    }
+    orc_solution *so = solution_alloc(n);
+    int64_t q = 0;
+    for (int b = 0; b < n; ++b) {
+        spline_t *s = &so->s[b];
+        spline_init(s, start[b], interval[b]);
+        if (!npoly[b]) continue;
+        s->buf = calloc((size_t)npoly[b], sizeof(poly_t));
+        s->cap = s->len = npoly[b];
+        for (int64_t p = 0; p < npoly[b]; ++p, ++q) {
+            s->buf[p].ncoef = ncoef[q];
+            if (ncoef[q]) memcpy(s->buf[p].c, coeffs + q * DIV * 3, sizeof(v3) * (size_t)ncoef[q]);
+        }
+    }
+    return so;
+}
 
 /* ------------------------------------------------------------------------------------------------ */
 /* LeastSquaresFit::interpolate  ephemeris_explorer/src/dynamics/celestial.rs:24-135                */

@@ -112,6 +112,11 @@ int orc_solution_eval(const orc_solution *, int body, double at, double *pos, do
 int orc_solution_append(orc_solution *a, const orc_solution *b, int direction);
 void orc_solution_clear(orc_solution *so, int body, double at, int after);
 orc_solution *orc_solution_clone(const orc_solution *src);
+/* Vec<UniformSpline> from its parts, in the layout orc_solution_coeffs returns (polynomials of body 0 first, coefficient k of
+ * polynomial p at [(p*8+k)*3 + c]); copies ncoef[p] rows per polynomial and never reads a row at or beyond ncoef[p]. NULL for a
+ * negative count or ncoef outside 0..8. */
+orc_solution *orc_solution_create(int n, const double *start, const double *interval, const int64_t *npoly, const double *coeffs,
+                                  const int32_t *ncoef);
 
 /* LeastSquaresFit::interpolate (ephemeris_explorer/src/dynamics/celestial.rs:24-135):
  * ts[m], xs[m*3] -> coeffs[8*3] (zero padded), returns ncoef after trim, or -1 on Err(()) */

@@ -109,6 +109,8 @@ def lib(native=False):
     L.orc_solution_clear.restype = None
     L.orc_solution_clone.argtypes = [vp]
     L.orc_solution_clone.restype = vp
+    L.orc_solution_create.restype = vp
+    L.orc_solution_create.argtypes = [C.c_int, _dp, _dp, C.POINTER(C.c_int64), _dp, _i32p]
     L.orc_least_squares_fit.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
     L.orc_poly_eval_and_deriv.argtypes = [C.c_int, _dp, C.c_double, _dp, _dp]
     L.orc_poly_eval_and_deriv.restype = None
@@ -250,6 +252,28 @@ class Solution:
     def __init__(self, L, handle):
         self.L, self.h = L, handle
         self.n = L.orc_solution_bodies(handle)
+
+    @classmethod
+    def from_parts(cls, start, interval, polys, native=False):
+        """Vec<UniformSpline> from per-body (start, interval) and a list per body of (coeffs[k][3]) polynomials of 0 to 8 rows: the
+        signature of ephemeris_explorer_amd.Solution.from_parts. Coefficients are copied bit for bit (signed zeros included).
+        NaN epochs are out of scope for whatever is built here: spline_get_polynomial casts ceil(q) to uint64_t, which C leaves
+        undefined for NaN; no test evaluates such a solution at a NaN epoch."""
+        L = lib(native)
+        npoly = np.array([len(p) for p in polys], dtype=np.int64)
+        tot = max(int(npoly.sum()), 1)
+        co, nc, q = np.zeros((tot, 8, 3)), np.zeros(tot, dtype=np.int32), 0
+        for body in polys:
+            for poly in body:
+                poly = np.asarray(poly, dtype=np.float64).reshape(-1, 3)
+                co[q, :len(poly)] = poly
+                nc[q] = len(poly)
+                q += 1
+        h = L.orc_solution_create(len(npoly), _ptr(_f64(start)), _ptr(_f64(interval)), _ptr(npoly, C.POINTER(C.c_int64)), _ptr(co),
+                                  _ptr(nc, _i32p))
+        if not h:
+            raise ValueError("orc_solution_create: a negative count, or a polynomial of more than 8 rows")
+        return cls(L, h)
 
     def info(self, body):
         s, i, n = C.c_double(), C.c_double(), C.c_int64()

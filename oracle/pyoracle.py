@@ -611,8 +611,10 @@ class Craft:
 
     EMIN, EMAX = -1.7976931348623157e308, 1.7976931348623157e308
 
-    def __init__(self, eph, mu, t0, pos, vel, method, tol, burns, h_init=60.0, n_max=1_000_000, soi=None):
+    def __init__(self, eph, mu, t0, pos, vel, method, tol, burns, h_init=60.0, n_max=1_000_000, soi=None, body_order=None):
         self.eph, self.mu, self.method, self.tol = eph, list(mu), method, tol
+        # the order Bodies::acceleration visits the bodies in (a burn's reference body stays an index into `eph`)
+        self.order = list(range(len(eph))) if body_order is None else [int(b) for b in body_order]
         self.soi = soi                      # SpacecraftSolout: sphere-of-influence radii, or None
         self.h_init, self.n_max = h_init, n_max
         self.fac_min, self.fac_max, self.fac, self.h_max = 1.0 / 5.0, 5.0 / 1.0, 9.0 / 10.0, self.EMAX
@@ -770,7 +772,8 @@ class Craft:
     def rhs(self, t, y):
         pos, vel = Vec(*y[:3]), Vec(*y[3:])
         acc = Vec(0.0, 0.0, 0.0)
-        for b, e in enumerate(self.eph):
+        for b in self.order:
+            e = self.eph[b]
             bp = spline_position(e["start"], e["interval"], e["polys"], t)
             if bp is None:
                 return None
