@@ -1,11 +1,13 @@
-// craft_attempt.inc -- one attempt of the embedded pair, included TEXTUALLY by the sweep kernels of craft_sweep.hip (the static
-// k_craft_propagate and the queue form k_craft_queue). Textual on purpose: routed through a function the same code gets a
-// measurably worse register allocation (444 SGPR-spill reloads against 8 in the static kernel, 4 % in the queue kernel).
+// craft_attempt.inc -- one attempt of the embedded pair, included TEXTUALLY by the sweep kernels of craft_sweep.hip (parts 1 and 2: the
+// static k_craft_propagate and the queue form k_craft_queue; part 3: those two and k_craft_wave). Textual on purpose: routed through
+// a function the same code gets a measurably worse register allocation (444 SGPR-spill reloads against 8 in the static kernel, 4 % in
+// the queue kernel; the ten controller lines of part 3 alone, as a function: 80 -> 96 B of scratch in the 13-stage static kernel).
 // In scope at the include site: a (CraftArgs), EPH_RK (the method table: a.rk or *rkp), sg, time, h, rk_i, y[6], template parameters
 // S / FSAL / NYS, and the stage derivatives k_s = (velocity half, acceleration half) behind KV_GET / KV_PUT and ka[S][3] (see
 // craft_sweep.hip "stage storage": the velocity halves live in LDS). Every component's chain of additions is the reference's, in the
 // reference's order -- the loops over d are merely split in two. EPH_ATTEMPT_PART 1: the stages (ERK::advance, explicit.rs:72-106, or
-// the ERKNG form) -> `bool ok`; part 2: the solution update and the error estimate (RKEmbedded::error) -> `double e[6]`.
+// the ERKNG form) -> `bool ok`; part 2: the solution update and the error estimate (RKEmbedded::error) -> `double e[6]`; part 3: the
+// error norm and the step-size controller, from e[6], `lower` and next_h -> `double err`, next_h updated.
 #if EPH_ATTEMPT_PART == 1
             // ERK::advance  explicit.rs:72-106
             bool ok = true;
@@ -65,7 +67,7 @@
                     ka[s][d] = zeroed ? 0.0 : out[3 + d];
                 }
             }
-#else
+#elif EPH_ATTEMPT_PART == 2
             double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             if (NYS) {
 #pragma unroll
@@ -105,4 +107,14 @@
                     }
                 }
             }
+#else
+            // AbsTol::err_over_tol
+            const double pm = fmax(fabs(e[0] / a.tol_pos), fmax(fabs(e[1] / a.tol_pos), fabs(e[2] / a.tol_pos)));
+            const double vm = fmax(fabs(e[3] / a.tol_vel), fmax(fabs(e[4] / a.tol_vel), fabs(e[5] / a.tol_vel)));
+            const double err = fmax(pm, vm);
+            // IController::step  mod.rs:225-243
+            const double m = a.fac * cr_pow(err, -(1.0 / (double)lower));
+            const double c = m < a.fac_min ? a.fac_min : (m > a.fac_max ? a.fac_max : m);
+            const double nh = next_h * c;
+            next_h = nh > a.h_max ? a.h_max : nh;
 #endif

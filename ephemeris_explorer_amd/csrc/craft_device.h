@@ -146,7 +146,13 @@ __device__ __noinline__ double cr_pow(double x, double y) {
     for (int n = EPH_POW_TERMS - 2; n >= 0; --n) ex = dd_add(dd_mul(ex, r), DD{eph_pow_invfact[n].hi, eph_pow_invfact[n].lo});
     return ldexp(ex.hi + ex.lo, (int)kf);
 }
-// UniformSpline::get_polynomial: false = None
+// ---- UniformSpline::get_polynomial: three statements, each with a role ---------------------------------------------------------
+//   spline_locate       the reference's form with the compiler's divisions: the evaluators (trajectory_eval.h), the burn frame,
+//                       k_craft_tau and the sweep's out-of-line path (body_position_generic)
+//   spline_locate_fast  guarded, always the reference's bits: k_craft_wave's terms (body_term, body_term_cached)
+//   locate_spec         (craft_sweep.hip) speculative and straight-line, with one verdict for the wave, which falls back to one of
+//                       the other two: the thread-per-craft kernels' body loop and body_term_wave
+// false = None
 __device__ __forceinline__ bool spline_locate(const BodyEntry &b, double at, long long &idx, double &tau) {
     const double local = at - b.start;
     const double span = b.interval * (double)b.npoly;
@@ -160,9 +166,8 @@ __device__ __forceinline__ bool spline_locate(const BodyEntry &b, double at, lon
     return true;
 }
 
-// UniformSpline::get_polynomial for the sweep kernels: the span product comes precomputed with the table entry and
-// the f64 <-> u64 conversions take the one-instruction 32-bit forms when every lane's segment count fits (always, in
-// practice); same values as spline_locate.
+// the guarded form: the span product comes precomputed with the table entry and the f64 <-> u64 conversions take the
+// one-instruction 32-bit forms when every lane's segment count fits (always, in practice); same values as spline_locate.
 __device__ __forceinline__ bool locate_quot_ok(double a) {   // numerator usable by div_refined: +-0 or in in_range_div
     return a == 0.0 || in_range_div(a);
 }

@@ -19,134 +19,125 @@
 namespace eph {
 namespace EPH_PV_NS {
 
-#ifndef EPH_CRAFT_SCALAR_ROWS
-#define EPH_CRAFT_SCALAR_ROWS 1
-#endif
+// The body-table lookup (UniformSpline::get_polynomial) is stated three times in all, each with a role of its own (craft_device.h, and
+// locate_spec below); the row load, the Horner pass over all rows and the guarded point-mass term once each, here.
+__device__ __forceinline__ long long uniform64(long long v) {
+    return (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)v) | ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32);
+}
+__device__ __forceinline__ long long lane64(long long v, int l) {
+    return (long long)(unsigned)__builtin_amdgcn_readlane((int)v, l) | ((long long)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32);
+}
+// one polynomial's 24 coefficients into the lane's registers: twelve 16-byte loads in flight at once
+__device__ __forceinline__ void load_row(const double *row, double (&c)[kDiv * 3]) {
+    const double2 *co = reinterpret_cast<const double2 *>(row);
+#pragma unroll
+    for (int q = 0; q < kDiv * 3 / 2; ++q) { const double2 v = co[q]; c[2 * q] = v.x; c[2 * q + 1] = v.y; }
+}
+// eval_slice_horner over all kDiv rows: rows >= ncoef are +0.0 in the device table (eph_ephemeris_create), so the leading steps give
+// 0*tau + 0 = +0, the state the reference's Horner starts from -- same bits, no ncoef load, no loop. `c`: a register array, a pointer
+// to per-lane memory, or the constant-address-space pointer of the scalar path.
+template <typename Row>
+__device__ __forceinline__ V3 horner_all(const Row &c, double tau) {
+    V3 bp = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = kDiv - 1; k >= 0; --k) {
+        bp.x = bp.x * tau + c[k * 3 + 0];
+        bp.y = bp.y * tau + c[k * 3 + 1];
+        bp.z = bp.z * tau + c[k * 3 + 2];
+    }
+    return bp;
+}
+// the point-mass term in the build's evaluation order, IEEE sqrt and divide (pair_term.h): the wrapper-free sequences when every
+// lane's squared distance is in their range, the compiler's expansions otherwise
+__device__ __forceinline__ void point_mass(double n2, const V3 &d, double mu, V3 &term) {
+    if (__builtin_amdgcn_ballot_w64(!in_range(n2)) == 0) pair_apply<true>(pair_den<true>(n2), d.x, d.y, d.z, mu, term.x, term.y, term.z);
+    else pair_apply<false>(pair_den<false>(n2), d.x, d.y, d.z, mu, term.x, term.y, term.z);
+}
 // One body's term of Bodies::acceleration (dynamics/spacecraft.rs:70-74,222-228): segment lookup, Horner, point mass.
+// (k_craft_wave above 64 bodies: the lanes differ in be)
 __device__ __forceinline__ bool body_term(const CraftArgs &a, const BodyEntry &be, double t, const V3 &pos, V3 &term) {
     long long idx;
     double tau;
     if (!spline_locate_fast(be, t, idx, tau)) return false;
-    // eval_slice_horner over all kDiv rows: rows >= ncoef are +0.0 in the device table (eph_ephemeris_create), so
-    // the leading steps give 0*tau + 0 = +0, the state the reference's Horner starts from -- same bits, no
-    // ncoef load, no loop, and twelve 16-byte loads in flight at once
-    V3 bp = {0.0, 0.0, 0.0};
-    const long long row = be.coeff_off + idx;         // (in the wave-per-craft form of > 64 bodies the lanes differ in be too)
-    const long long row0 = (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)row) |
-                           ((long long)__builtin_amdgcn_readfirstlane((int)(row >> 32)) << 32);
-    if (EPH_CRAFT_SCALAR_ROWS && __builtin_amdgcn_ballot_w64(row != row0) == 0) {
-        // every lane of the wave is inside the SAME polynomial (craft of one sweep started together: the usual case): its 24
-        // coefficients come through the scalar cache into SGPRs instead of 64 lanes x 192 B through the vector L1
-        const auto *cs = (const __attribute__((address_space(4))) double *)(unsigned long long)(a.coeffs + row0 * kDiv * 3);
-#pragma unroll
-        for (int k = kDiv - 1; k >= 0; --k) {
-            bp.x = bp.x * tau + cs[k * 3 + 0];
-            bp.y = bp.y * tau + cs[k * 3 + 1];
-            bp.z = bp.z * tau + cs[k * 3 + 2];
-        }
+    V3 bp;
+    const long long row = be.coeff_off + idx, row0 = uniform64(row);
+    if (__builtin_amdgcn_ballot_w64(row != row0) == 0) {
+        // every lane of the wave is inside the SAME polynomial: its 24 coefficients come through the scalar cache into SGPRs instead
+        // of 64 lanes x 192 B through the vector L1
+        bp = horner_all((const __attribute__((address_space(4))) double *)(unsigned long long)(a.coeffs + row0 * kDiv * 3), tau);
     } else {
-        const double2 *co = reinterpret_cast<const double2 *>(a.coeffs + row * kDiv * 3);
         double c[kDiv * 3];
-#pragma unroll
-        for (int q = 0; q < kDiv * 3 / 2; ++q) { const double2 v = co[q]; c[2 * q] = v.x; c[2 * q + 1] = v.y; }
-#pragma unroll
-        for (int k = kDiv - 1; k >= 0; --k) {
-            bp.x = bp.x * tau + c[k * 3 + 0];
-            bp.y = bp.y * tau + c[k * 3 + 1];
-            bp.z = bp.z * tau + c[k * 3 + 2];
-        }
+        load_row(a.coeffs + row * kDiv * 3, c);
+        bp = horner_all(c, tau);
     }
     const V3 d = sub(bp, pos);                        // acceleration_at::<false>: dir = body - at
-    const double n2 = dot(d, d);
-    // the point-mass term in the build's evaluation order, IEEE sqrt and divide (pair_term.h)
-    if (__builtin_amdgcn_ballot_w64(!in_range(n2)) == 0) pair_apply<true>(pair_den<true>(n2), d.x, d.y, d.z, be.mu, term.x, term.y, term.z);
-    else pair_apply<false>(pair_den<false>(n2), d.x, d.y, d.z, be.mu, term.x, term.y, term.z);
+    point_mass(dot(d, d), d, be.mu, term);
     return true;
 }
-// k_craft_wave: lane b always evaluates body b, so the body's table entry, the refined reciprocal of its spline
-// interval and the coefficients of the polynomial it is currently in stay in the lane's registers; the polynomial is
-// reloaded only when the segment index changes (every few hundred steps). Used when n_bodies <= 64.
+// ---- UniformSpline::get_polynomial, SPECULATIVELY: spline_locate_fast with every guarded choice assumed (the entry's shared reciprocal
+// for both quotients, 32-bit segment count). Straight-line. When every lane's assumptions hold and it is inside the spline (and the entry
+// passes entry_fast), tau and idx are spline_locate_fast's. The tests are folded: both
+// numerators in the guarded range of the shared-reciprocal division (one max over their range keys; a negative, zero or NaN `local`
+// has a key outside it, so the sign test is implied -- t == start exactly, where local = rem = +0 is a legal numerator, takes the
+// out-of-line path), not beyond the span, and the segment inside the table (which also catches a count that was clamped at 2^31:
+// entry_fast requires npoly < 2^31).
+// Returns the wave's ballot of lanes for which an assumption does NOT hold (0 = every lane fine), as the OR of one ballot per test: a
+// ballot of a single compare is the compare's own result mask, a ballot of a combined per-lane flag costs a select and a second compare.
+__device__ __forceinline__ unsigned div_key(double x) { return (unsigned)(__double2hiint(x) - 0x33700000); }    // in_range_div: key < 0x19000000
+__device__ __forceinline__ unsigned long long locate_spec(const BodyEntry &b, double at, double &tau, unsigned &idx) {
+    const double local = at - b.start;
+    const double c = ceil(div_refined(local, b.interval, b.rinv));
+    const unsigned ci = (unsigned)fmin(fmax(c, 0.0), 2147483648.0);       // c <= 0 (and NaN) -> 0, as `c <= 0.0 ? 0u : (unsigned)c`
+    const unsigned i32 = ci == 0 ? 0u : ci - 1u;
+    const double rem = local - b.interval * (double)i32;
+    tau = div_refined(rem, b.interval, b.rinv);
+    idx = i32;
+    return __builtin_amdgcn_ballot_w64(max(div_key(local), div_key(rem)) >= 0x19000000u) | __builtin_amdgcn_ballot_w64(local > b.span) |
+           __builtin_amdgcn_ballot_w64(i32 >= (unsigned)b.npoly);
+}
+// the entry's refined reciprocal is +0.0 unless the interval is in the guarded range of the shared-reciprocal division AND the segment
+// count fits 31 bits (k_body_reciprocals); a nonzero one is a normal number. (Wave-uniform in the thread kernels: one scalar compare.)
+__device__ __forceinline__ bool entry_fast(const BodyEntry &b) { return __double2hiint(b.rinv) != 0; }
+
+// k_craft_wave: lane b always evaluates body b, so the body's table entry (with the refined reciprocal of its spline interval) and
+// the coefficients of the polynomial it is currently in stay in the lane's registers; the polynomial is reloaded only when the
+// segment index changes (every few hundred steps). Used when n_bodies <= 64.
 struct LaneBody {
     BodyEntry be;
-    double r;                 // rcp_refined(be.interval)
-    bool b_ok;                // interval in range for the wrapper-free division
     long long idx;            // segment whose coefficients are in c (-1: none)
     double c[kDiv * 3];
 };
 __device__ __forceinline__ bool body_term_cached(const CraftArgs &a, LaneBody &lb, double t, const V3 &pos, V3 &term) {
-    // UniformSpline::get_polynomial, the two divisions by the interval through the shared reciprocal (same quotients)
-    const BodyEntry &b = lb.be;
-    const double local = t - b.start;
-    if (__builtin_signbit(local) || local > b.span) return false;
-    const double cq = ceil(div_shared(local, b.interval, lb.r, lb.b_ok));
-    unsigned long long i;
-    double fi;
-    if (__builtin_amdgcn_ballot_w64(!(cq < 2147483648.0)) == 0) {
-        const unsigned ci = cq <= 0.0 ? 0u : (unsigned)cq;
-        const unsigned i32 = ci == 0 ? 0u : ci - 1u;
-        i = i32;
-        fi = (double)i32;
-    } else {
-        const unsigned long long ci = cq <= 0.0 ? 0ull : (cq >= 18446744073709551616.0 ? ~0ull : (unsigned long long)cq);
-        i = ci == 0 ? 0 : ci - 1;
-        fi = (double)i;
-    }
-    if (i >= (unsigned long long)b.npoly) return false;
-    const long long idx = (long long)i;
-    const double tau = div_shared(local - b.interval * fi, b.interval, lb.r, lb.b_ok);
+    long long idx;
+    double tau;
+    if (!spline_locate_fast(lb.be, t, idx, tau)) return false;
     if (idx != lb.idx) {
-        const double2 *co = reinterpret_cast<const double2 *>(a.coeffs + (b.coeff_off + idx) * kDiv * 3);
-#pragma unroll
-        for (int q = 0; q < kDiv * 3 / 2; ++q) { const double2 v = co[q]; lb.c[2 * q] = v.x; lb.c[2 * q + 1] = v.y; }
+        load_row(a.coeffs + (lb.be.coeff_off + idx) * kDiv * 3, lb.c);
         lb.idx = idx;
     }
-    V3 bp = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = kDiv - 1; k >= 0; --k) {
-        bp.x = bp.x * tau + lb.c[k * 3 + 0];
-        bp.y = bp.y * tau + lb.c[k * 3 + 1];
-        bp.z = bp.z * tau + lb.c[k * 3 + 2];
-    }
-    const V3 d = sub(bp, pos);
-    const double n2 = dot(d, d);
-    if (__builtin_amdgcn_ballot_w64(!in_range(n2)) == 0) pair_apply<true>(pair_den<true>(n2), d.x, d.y, d.z, b.mu, term.x, term.y, term.z);
-    else pair_apply<false>(pair_den<false>(n2), d.x, d.y, d.z, b.mu, term.x, term.y, term.z);
+    const V3 d = sub(horner_all(lb.c, tau), pos);
+    point_mass(dot(d, d), d, lb.be.mu, term);
     return true;
 }
-__device__ __forceinline__ unsigned div_key(double x) { return (unsigned)(__double2hiint(x) - 0x33700000); }    // in_range_div: key < 0x19000000
-// The same term with the lookup SPECULATIVE and branch-free, like the thread-per-craft kernels' locate_spec (every guarded choice of
-// body_term_cached assumed -- the lane's own reciprocal for both quotients, 32-bit segment count, in-range squared distance -- and ONE
-// ballot at the end; whatever does not hold sends the wave through body_term_cached itself, which gives the same bits). On the single
-// wave this kernel is, every branch of the guarded form is a bubble: a ship's step 32.0-32.7 -> 30.7-31.1 us (64 craft: 27.5 -> 26.1).
+// The same term on the speculative lookup, branch-free like the thread-per-craft kernels' body loop: the in-range point-mass term
+// assumed too, the lane's entry_fast and the squared distance's range OR-ed into locate_spec's verdict; whatever does not hold anywhere
+// in the wave sends it through body_term_cached itself, which gives the same bits. On the single wave this kernel is, every branch of
+// the guarded form is a bubble: a ship's step 32.0-32.7 -> 30.7-31.1 us (64 craft: 27.5 -> 26.1).
 __device__ __forceinline__ bool body_term_wave(const CraftArgs &a, LaneBody &lb, double t, const V3 &pos, V3 &term) {
     const BodyEntry &b = lb.be;
-    const double local = t - b.start;
-    const double cq = ceil(div_refined(local, b.interval, lb.r));
-    const unsigned ci = (unsigned)fmin(fmax(cq, 0.0), 2147483648.0);
-    const unsigned i32 = ci == 0 ? 0u : ci - 1u;
-    const double rem = local - b.interval * (double)i32;
-    const double tau = div_refined(rem, b.interval, lb.r);
-    bool bad = !lb.b_ok | (max(div_key(local), div_key(rem)) >= 0x19000000u) | (local > b.span) |
-               ((unsigned long long)i32 >= (unsigned long long)b.npoly);
+    double tau;
+    unsigned i32;
+    unsigned long long bad = locate_spec(b, t, tau, i32) | __builtin_amdgcn_ballot_w64(!entry_fast(b));
     const long long idx = (long long)i32;
-    if (!bad && idx != lb.idx) {                      // (the lane's polynomial changed: every few hundred steps)
-        const double2 *co = reinterpret_cast<const double2 *>(a.coeffs + (b.coeff_off + idx) * kDiv * 3);
-#pragma unroll
-        for (int q = 0; q < kDiv * 3 / 2; ++q) { const double2 v = co[q]; lb.c[2 * q] = v.x; lb.c[2 * q + 1] = v.y; }
+    if (bad == 0 && idx != lb.idx) {                  // (the lane's polynomial changed: every few hundred steps; a rejected index is never an address)
+        load_row(a.coeffs + (b.coeff_off + idx) * kDiv * 3, lb.c);
         lb.idx = idx;
     }
-    V3 bp = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = kDiv - 1; k >= 0; --k) {
-        bp.x = bp.x * tau + lb.c[k * 3 + 0];
-        bp.y = bp.y * tau + lb.c[k * 3 + 1];
-        bp.z = bp.z * tau + lb.c[k * 3 + 2];
-    }
-    const V3 d = sub(bp, pos);
+    const V3 d = sub(horner_all(lb.c, tau), pos);
     const double n2 = dot(d, d);
     pair_apply<true>(pair_den<true>(n2), d.x, d.y, d.z, b.mu, term.x, term.y, term.z);
-    bad = bad | !in_range(n2);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) {
+    bad |= __builtin_amdgcn_ballot_w64(!in_range(n2));
+    if (__builtin_expect(bad != 0, 0)) {
         asm volatile("");
         return body_term_cached(a, lb, t, pos, term);
     }
@@ -181,34 +172,16 @@ __device__ __forceinline__ BodyEntry entry_uniform(const BodyEntry *table, int b
     be.coeff_off = bc->coeff_off; be.span = bc->span; be.rinv = bc->rinv; be.rows = bc->rows;
     return be;
 }
-__device__ __forceinline__ long long uniform64(long long v) {
-    return (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)v) | ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32);
-}
-__device__ __forceinline__ long long lane64(long long v, int l) {
-    return (long long)(unsigned)__builtin_amdgcn_readlane((int)v, l) | ((long long)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32);
-}
 struct RowS { double c[kDiv * 3]; };                  // one polynomial's 24 coefficients, wave-uniform: SGPRs
-// EPH_CRAFT_ROW_SPLIT=1 loads it in two parts -- the 16 high coefficients (Horner's first five steps) a body ahead, the 8 low ones at
-// the start of the body's own Horner pass -- so that 32 instead of 48 SGPRs stay occupied across the previous body's term and none of
-// the row is spilled to VGPR lanes. Measured on one box (scripts/ab_craft.sh, 262 144 craft x 0.25 d): 31.1 ms against 29.9-30.0 for
-// the whole row a body ahead (8 v_readlane per term, but no exposed scalar-cache latency in front of Horner): off.
-#ifndef EPH_CRAFT_ROW_SPLIT
-#define EPH_CRAFT_ROW_SPLIT 0
-#endif
-constexpr int kRowLo = EPH_CRAFT_ROW_SPLIT ? 8 : 0;   // coefficients [0, kRowLo) are loaded late
-__device__ __forceinline__ void row_uniform_hi(const double *rows, unsigned i0, RowS &r) {
+// requested whole, a body ahead. (In two parts -- the 16 high coefficients a body ahead, the 8 low ones at the start of the body's own
+// Horner pass, 32 instead of 48 SGPRs occupied across the previous body's term -- measured on one box, 262 144 craft x 0.25 d: 31.1 ms
+// against 29.9-30.0 for the whole row: 8 v_readlane per term, but no exposed scalar-cache latency in front of Horner.)
+__device__ __forceinline__ void row_uniform(const double *rows, unsigned i0, RowS &r) {
     const auto *cs = (const __attribute__((address_space(4))) double *)(unsigned long long)(rows + (size_t)i0 * (kDiv * 3));
 #pragma unroll
-    for (int k = kRowLo; k < kDiv * 3; ++k) r.c[k] = cs[k];
+    for (int k = 0; k < kDiv * 3; ++k) r.c[k] = cs[k];
 }
-__device__ __forceinline__ void row_uniform_lo(const double *rows, unsigned i0, RowS &r) {
-    const auto *cs = (const __attribute__((address_space(4))) double *)(unsigned long long)(rows + (size_t)i0 * (kDiv * 3));
-#pragma unroll
-    for (int k = 0; k < kRowLo; ++k) r.c[k] = cs[k];
-}
-// eval_slice_horner over all kDiv rows: rows >= ncoef are +0.0 in the device table (eph_ephemeris_create), so the leading steps give
-// 0*tau + 0 = +0, the state the reference's Horner starts from -- same bits, no ncoef load, no loop
-// ... and the first step without its product: the reference starts from T::default() = +0 (trajectory.rs:404-407), and (+0) * tau is +0
+// horner_all with the first step without its product: the reference starts from T::default() = +0 (trajectory.rs:404-407), and (+0) * tau is +0
 // for every tau the speculative lookup lets through (tau > 0: the remainder of a positive `local`), so step one is (+0) + c -- kept as
 // an addition, because (+0) + (-0) is +0, not -0. Three multiplications less per term; same bits.
 __device__ __forceinline__ V3 horner_row(const RowS &r, double tau) {
@@ -221,30 +194,7 @@ __device__ __forceinline__ V3 horner_row(const RowS &r, double tau) {
     }
     return bp;
 }
-// UniformSpline::get_polynomial, speculatively: spline_locate_fast with every guarded choice assumed (shared reciprocal for both
-// quotients, 32-bit segment count). Straight-line. When every lane's assumptions hold and it is inside the spline (and the entry
-// passes entry_fast), tau and idx are spline_locate_fast's. The tests are folded: both
-// numerators in the guarded range of the shared-reciprocal division (one max over their range keys; a negative, zero or NaN `local`
-// has a key outside it, so the sign test is implied -- t == start exactly, where local = rem = +0 is a legal numerator, takes the
-// out-of-line path), not beyond the span, and the segment inside the table (which also catches a count that was clamped at 2^31:
-// entry_fast requires npoly < 2^31).
-// Returns the wave's ballot of lanes for which an assumption does NOT hold (0 = every lane fine), as the OR of one ballot per test: a
-// ballot of a single compare is the compare's own result mask, a ballot of a combined per-lane flag costs a select and a second compare.
-__device__ __forceinline__ unsigned long long locate_spec(const BodyEntry &b, double at, double &tau, unsigned &idx) {
-    const double local = at - b.start;
-    const double c = ceil(div_refined(local, b.interval, b.rinv));
-    const unsigned ci = (unsigned)fmin(fmax(c, 0.0), 2147483648.0);       // c <= 0 (and NaN) -> 0, as `c <= 0.0 ? 0u : (unsigned)c`
-    const unsigned i32 = ci == 0 ? 0u : ci - 1u;
-    const double rem = local - b.interval * (double)i32;
-    tau = div_refined(rem, b.interval, b.rinv);
-    idx = i32;
-    return __builtin_amdgcn_ballot_w64(max(div_key(local), div_key(rem)) >= 0x19000000u) | __builtin_amdgcn_ballot_w64(local > b.span) |
-           __builtin_amdgcn_ballot_w64(i32 >= (unsigned)b.npoly);
-}
-// wave-uniform, one scalar compare: the entry's refined reciprocal is +0.0 unless the interval is in the guarded range of the
-// shared-reciprocal division AND the segment count fits 31 bits (k_body_reciprocals); a nonzero one is a normal number
-__device__ __forceinline__ bool entry_fast(const BodyEntry &b) { return __double2hiint(b.rinv) != 0; }
-// the out-of-line IEEE path (cold): UniformSpline::get_polynomial + eval with the compiler's divisions, per-lane coefficient loads
+// the out-of-line IEEE path (cold): the reference's lookup with the compiler's divisions (spline_locate), per-lane coefficient loads
 struct BodyPos { double x, y, z; int located; };
 // (reads the table entry itself: the hot loop then keeps nothing of an entry alive for this call's sake)
 __device__ __noinline__ BodyPos body_position_generic(const double *coeffs, const BodyEntry *table, int b, double t) {
@@ -254,30 +204,15 @@ __device__ __noinline__ BodyPos body_position_generic(const double *coeffs, cons
     long long idx;
     double tau;
     if (!spline_locate(be, t, idx, tau)) return BodyPos{0.0, 0.0, 0.0, 0};
-    const double *co = coeffs + (coeff_off + idx) * kDiv * 3;
-    V3 bp = {0.0, 0.0, 0.0};
-    for (int k = kDiv - 1; k >= 0; --k) {
-        bp.x = bp.x * tau + co[k * 3 + 0];
-        bp.y = bp.y * tau + co[k * 3 + 1];
-        bp.z = bp.z * tau + co[k * 3 + 2];
-    }
+    const V3 bp = horner_all(coeffs + (coeff_off + idx) * kDiv * 3, tau);
     return BodyPos{bp.x, bp.y, bp.z, 1};
 }
 // Horner with PER-LANE coefficient loads (cold): the lanes of a wave that are inside many different polynomials of one body -- craft
 // whose epochs have drifted far apart (an undealt heterogeneous batch in the work-queue kernel: lanes pick up new craft at any time)
 __device__ __noinline__ V3 horner_lane_rows(const double *rows, unsigned idx, double tau) {
-    const double2 *co = reinterpret_cast<const double2 *>(rows + (size_t)idx * (kDiv * 3));
     double c[kDiv * 3];
-#pragma unroll
-    for (int q = 0; q < kDiv * 3 / 2; ++q) { const double2 v = co[q]; c[2 * q] = v.x; c[2 * q + 1] = v.y; }
-    V3 bp = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = kDiv - 1; k >= 0; --k) {
-        bp.x = bp.x * tau + c[k * 3 + 0];
-        bp.y = bp.y * tau + c[k * 3 + 1];
-        bp.z = bp.z * tau + c[k * 3 + 2];
-    }
-    return bp;
+    load_row(rows + (size_t)idx * (kDiv * 3), c);
+    return horner_all(c, tau);
 }
 __device__ __noinline__ V3 pair_generic(double n2, double dx, double dy, double dz, double mu) {
     V3 term;
@@ -293,7 +228,7 @@ __device__ __forceinline__ bool bodies_acceleration(const CraftArgs &a, double t
     // wave takes the out-of-line IEEE path for that body, which gives the other lanes the same bits -- a slow last evaluation for a
     // wave that holds a failing craft, three scalar operations less per term for everybody else.
     bool failed = false;
-    // prologue: body 0's entry, lookup and the high part of its row
+    // prologue: body 0's entry, lookup and its row
     BodyEntry be = entry_uniform(a.bodies, 0);
     double tau;
     unsigned idx;
@@ -302,10 +237,9 @@ __device__ __forceinline__ bool bodies_acceleration(const CraftArgs &a, double t
     unsigned i0 = (unsigned)__builtin_amdgcn_readfirstlane((int)idx) & -(unsigned)all_good;            // (branch-free: row 0 of a body is always a valid address)
     const double *rows = be.rows;                     // (a row address from the entry alone: no table base in the loop)
     RowS cs;
-    row_uniform_hi(rows, i0, cs);
+    row_uniform(rows, i0, cs);
     for (int b = 0; b < nb; ++b) {
         // ---- P(b): the body's position at t
-        row_uniform_lo(rows, i0, cs);
         V3 bp;
         if (__builtin_expect(all_good, 1)) {
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(idx != i0) == 0, 1)) {
@@ -341,7 +275,7 @@ __device__ __forceinline__ bool bodies_acceleration(const CraftArgs &a, double t
         all_good = more & entry_fast(be) & (bad == 0);
         i0 = (unsigned)__builtin_amdgcn_readfirstlane((int)idx) & -(unsigned)all_good;
         rows = be.rows;
-        row_uniform_hi(rows, i0, cs);
+        row_uniform(rows, i0, cs);
         V3 term;
         pair_apply<true>(den, d.x, d.y, d.z, mu, term.x, term.y, term.z);
         // (the empty asm keeps the straight-line term IN this block, beside the lookup of the next body: two independent chains; without
@@ -601,15 +535,9 @@ k_craft_propagate(const CraftArgs a) {
             time = time + h;
             rk_i += 1;
             n_att += 1;
-            // AbsTol::err_over_tol
-            const double pm = fmax(fabs(e[0] / a.tol_pos), fmax(fabs(e[1] / a.tol_pos), fabs(e[2] / a.tol_pos)));
-            const double vm = fmax(fabs(e[3] / a.tol_vel), fmax(fabs(e[4] / a.tol_vel), fabs(e[5] / a.tol_vel)));
-            const double err = fmax(pm, vm);
-            // IController::step  mod.rs:225-243
-            const double m = a.fac * cr_pow(err, -(1.0 / (double)lower));
-            const double c = m < a.fac_min ? a.fac_min : (m > a.fac_max ? a.fac_max : m);
-            const double nh = next_h * c;
-            next_h = nh > a.h_max ? a.h_max : nh;
+#define EPH_ATTEMPT_PART 3
+#include "craft_attempt.inc"
+#undef EPH_ATTEMPT_PART
             if (err <= 1.0) break;
             time = prev_t;                            // PreviousStep::restore
 #pragma unroll
@@ -772,15 +700,9 @@ k_craft_queue(const CraftArgs a) {
             time = time + h;
             rk_i += 1;
             n_att += 1;
-            // AbsTol::err_over_tol
-            const double pm = fmax(fabs(e[0] / a.tol_pos), fmax(fabs(e[1] / a.tol_pos), fabs(e[2] / a.tol_pos)));
-            const double vm = fmax(fabs(e[3] / a.tol_vel), fmax(fabs(e[4] / a.tol_vel), fabs(e[5] / a.tol_vel)));
-            const double err = fmax(pm, vm);
-            // IController::step  mod.rs:225-243
-            const double m = a.fac * cr_pow(err, -(1.0 / (double)lower));
-            const double c = m < a.fac_min ? a.fac_min : (m > a.fac_max ? a.fac_max : m);
-            const double nh = next_h * c;
-            next_h = nh > a.h_max ? a.h_max : nh;
+#define EPH_ATTEMPT_PART 3
+#include "craft_attempt.inc"
+#undef EPH_ATTEMPT_PART
             if (err <= 1.0) {
                 // accepted. CubicHermiteSplineSolout::solout: push (t, r, v)
                 steps += 1;
@@ -873,8 +795,6 @@ __global__ void __launch_bounds__(64) k_craft_wave(const CraftArgs a) {
     const int lower = a.rk.order < a.rk.order_embedded ? a.rk.order : a.rk.order_embedded;
     LaneBody lb;
     lb.be = a.bodies[lane < a.n_bodies ? lane : 0];
-    lb.r = rcp_refined(lb.be.interval);
-    lb.b_ok = in_range_div(lb.be.interval);
     lb.idx = -1;
 #pragma unroll
     for (int q = 0; q < kDiv * 3; ++q) lb.c[q] = 0.0;
@@ -956,9 +876,6 @@ __global__ void __launch_bounds__(64) k_craft_wave(const CraftArgs a) {
 #pragma unroll
                     for (int d = 0; d < 6; ++d) yi[d] = lane_bcast(sum, d);
                 }
-#if defined(EPH_EXPERIMENTS) && defined(EPH_WAVE_RHS2)
-                { double o2[6]; (void)craft_rhs<true>(a, sg, ti + 1e-3, yi, o2, red, &lb); asm volatile("" ::"v"(o2[3]), "v"(o2[4]), "v"(o2[5])); }   // TIMING: one evaluation more per stage
-#endif
                 ok = craft_rhs<true>(a, sg, ti, yi, out, red, &lb);
                 if (!ok) {                            // an Err leaves k[s] as `self.k[s].zero()` made it  explicit.rs:92
 #pragma unroll
@@ -1020,18 +937,9 @@ __global__ void __launch_bounds__(64) k_craft_wave(const CraftArgs a) {
             time = time + h;
             rk_i += 1;
             n_att += 1;
-            // AbsTol::err_over_tol
-            const double pm = fmax(fabs(e[0] / a.tol_pos), fmax(fabs(e[1] / a.tol_pos), fabs(e[2] / a.tol_pos)));
-            const double vm = fmax(fabs(e[3] / a.tol_vel), fmax(fabs(e[4] / a.tol_vel), fabs(e[5] / a.tol_vel)));
-            const double err = fmax(pm, vm);
-            // IController::step  mod.rs:225-243
-#if defined(EPH_EXPERIMENTS) && defined(EPH_WAVE_POW2)
-            { const double m2 = cr_pow(err * 1.0000001, -(1.0 / (double)lower)); asm volatile("" ::"v"(m2)); }   // TIMING: one pow more per attempt
-#endif
-            const double m = a.fac * cr_pow(err, -(1.0 / (double)lower));
-            const double c = m < a.fac_min ? a.fac_min : (m > a.fac_max ? a.fac_max : m);
-            const double nh = next_h * c;
-            next_h = nh > a.h_max ? a.h_max : nh;
+#define EPH_ATTEMPT_PART 3
+#include "craft_attempt.inc"
+#undef EPH_ATTEMPT_PART
             if (err <= 1.0) break;
             time = prev_t;                            // PreviousStep::restore
 #pragma unroll
@@ -1086,38 +994,35 @@ int craft_launch(hipStream_t s, const CraftArgs &a, const CraftLaunch &how) {
     const long long waves = (a.n_craft + 63) / 64;
     const int S = a.rk.stages;
     const bool F = a.rk.fsal != 0;
+    // the supported (stages, FSAL) pairs of the ERK form; the one Nystroem pair is (7, FSAL)
+#define EPH_CRAFT_PAIRS(X) X(6, false) X(7, true) X(7, false) X(9, false) X(13, false) X(16, false)
     if (how.queue) {
         const dim3 grid((unsigned)how.resident_waves), block(64);
+#define EPH_CRAFT_CASE(S_, F_) else if (S == S_ && F == F_) hipLaunchKernelGGL((k_craft_queue<S_, F_>), grid, block, 0, s, a);
         if (a.rk.nystrom) {
             if (S == 7 && F) hipLaunchKernelGGL((k_craft_queue<7, true, true>), grid, block, 0, s, a);
             else return EPH_ERR_UNSUPPORTED;
-        } else if (S == 6 && !F) hipLaunchKernelGGL((k_craft_queue<6, false>), grid, block, 0, s, a);
-        else if (S == 7 && F) hipLaunchKernelGGL((k_craft_queue<7, true>), grid, block, 0, s, a);
-        else if (S == 7 && !F) hipLaunchKernelGGL((k_craft_queue<7, false>), grid, block, 0, s, a);
-        else if (S == 9 && !F) hipLaunchKernelGGL((k_craft_queue<9, false>), grid, block, 0, s, a);
-        else if (S == 13 && !F) hipLaunchKernelGGL((k_craft_queue<13, false>), grid, block, 0, s, a);
-        else if (S == 16 && !F) hipLaunchKernelGGL((k_craft_queue<16, false>), grid, block, 0, s, a);
+        }
+        EPH_CRAFT_PAIRS(EPH_CRAFT_CASE)
         else return EPH_ERR_UNSUPPORTED;
+#undef EPH_CRAFT_CASE
         return launched("k_craft_queue");
     }
     const dim3 grid((unsigned)waves), block(64);
     const bool occ2 = how.occ2;
 #define EPH_CRAFT_CASE(S_, F_)                                                                     \
-    do {                                                                                           \
+    else if (S == S_ && F == F_) {                                                                 \
         if (occ2) hipLaunchKernelGGL((k_craft_propagate<S_, F_, false, 2>), grid, block, 0, s, a); \
         else hipLaunchKernelGGL((k_craft_propagate<S_, F_, false, 1>), grid, block, 0, s, a);      \
-    } while (0)
+    }
     if (a.rk.nystrom) {
         if (S == 7 && F) hipLaunchKernelGGL((k_craft_propagate<7, true, true, 2>), grid, block, 0, s, a);
         else return EPH_ERR_UNSUPPORTED;
-    } else if (S == 6 && !F) EPH_CRAFT_CASE(6, false);
-    else if (S == 7 && F) EPH_CRAFT_CASE(7, true);
-    else if (S == 7 && !F) EPH_CRAFT_CASE(7, false);
-    else if (S == 9 && !F) EPH_CRAFT_CASE(9, false);
-    else if (S == 13 && !F) EPH_CRAFT_CASE(13, false);
-    else if (S == 16 && !F) EPH_CRAFT_CASE(16, false);
+    }
+    EPH_CRAFT_PAIRS(EPH_CRAFT_CASE)
     else return EPH_ERR_UNSUPPORTED;
 #undef EPH_CRAFT_CASE
+#undef EPH_CRAFT_PAIRS
     return launched("k_craft_propagate");
 }
 

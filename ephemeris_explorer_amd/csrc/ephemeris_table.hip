@@ -15,8 +15,8 @@
 
 namespace eph {
 
-// the reciprocal of every body's spline interval, formed once where the sweep kernels would form it (same instructions as
-// LaneBody::r): the table entry carries it to spline_locate_fast
+// the reciprocal of every body's spline interval, formed once, on the device the sweep kernels run on: the table entry carries it
+// to spline_locate_fast and locate_spec, in every form of the sweep
 __global__ void k_body_reciprocals(int n, BodyEntry *bodies) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n) return;

@@ -4,9 +4,10 @@
 // the reference's operation order bit for bit (-ffp-contract=off; the association of every expression is the reference's): a
 // correction is made here and nowhere else.
 // Device code only (but separation_request_ok, the host's check of what both searches refuse), every function inlined into its
-// kernel. Not here, on purpose: the sweep's own body loop (craft_sweep.hip: Horner over all kDiv rows, spline_locate_fast),
-// k_craft_tau (approximate by design) and the event search's struct Hermite (craft_events.hip: coefficients built once per step,
-// evaluated many times).
+// kernel. Not here, on purpose: the sweep's own body loop, whose parts are stated once each where they are used (craft_device.h:
+// spline_locate_fast, the guarded lookup; craft_sweep.hip: locate_spec, the speculative one, and horner_all / horner_row over all
+// kDiv rows), k_craft_tau (approximate by design) and the event search's struct Hermite (craft_events.hip: coefficients built once
+// per step, evaluated many times).
 //
 // Mirrors (paths relative to the reference repository root):
 //   UniformSpline::{position, state_vector, get_polynomial}, Polynomial::{eval, eval_and_deriv}, eval_slice_horner

@@ -2,9 +2,10 @@
 (CPU: the C oracle against the Python restatement) and tests/test_gpu_craft_lookup.py (device against the C oracle). A plain module, no
 fixtures.
 
-Why: the lookup of a massive body's polynomial (UniformSpline::get_polynomial + Horner, trajectory.rs:398-410,551-617) exists in five forms
-in the sweep kernels (csrc/craft_sweep.hip, craft_device.h) plus spline_locate / spline_state_vector (trajectory_eval.h), all promised to
-give the reference's bits. Tables fitted by the N-body propagator never put a stage epoch on a polynomial boundary except by accident, never
+Why: the lookup of a massive body's polynomial (UniformSpline::get_polynomial + Horner, trajectory.rs:398-410,551-617) is stated three
+times for the device -- spline_locate, spline_locate_fast (csrc/craft_device.h) and the speculative locate_spec (csrc/craft_sweep.hip) --
+and reaches the sweep kernels through four terms (bodies_acceleration, body_term, body_term_cached, body_term_wave) plus
+spline_state_vector (trajectory_eval.h), all promised to give the reference's bits. Tables fitted by the N-body propagator never put a stage epoch on a polynomial boundary except by accident, never
 fail entry_fast, agree at their boundaries to round-off and start every body at one epoch. These tables do the opposite on purpose.
 
 The tables (make_body): every body moves on a circle; polynomial p holds the Taylor rows of that motion about its own start, truncated to
@@ -19,7 +20,8 @@ NaN epochs are out of scope (the C oracle's ceil -> uint64_t cast is undefined t
 Scenario -> the kernel arm it is there for
   A  boundary walk: 70 craft (a full wave and a partial one in the thread-per-craft forms) take 16 steps of exactly 64 s from t0 == start
      of bodies 0 and 1 to start + span of bodies 0 and 2, a knot on every boundary of the 64 s body, then EvalFailed. local == +0 (the
-     folded sign test of locate_spec sends `t == start` to body_position_generic; body_term_wave's ballot to body_term_cached),
+     folded sign test of locate_spec sends `t == start` to body_position_generic in bodies_acceleration, and through body_term_wave's
+     mask to body_term_cached, i.e. spline_locate_fast),
      local == k * interval exactly (ceil - 1, not floor: tau == 1 of polynomial k - 1), local == span (idx == npoly - 1, not npoly).
   B  one ulp around: craft started at nextafter(boundary, +-inf), nextafter(start, -inf) (fails before any attempt), start, start + span,
      nextafter(start + span, +inf) of a dyadic table; then t0 = start + interval * k on a table whose intervals are the committed systems'
@@ -29,9 +31,10 @@ Scenario -> the kernel arm it is there for
      numerators nearest an integer quotient.
   C  drifted lanes: 136 craft from a low orbit out to 50 radii against 32 s polynomials, advanced with step_n: the lanes of one wave end up
      hundreds of polynomials apart. horner_lane_rows in the undealt static form (the prefetched row belongs to the first lane only), the
-     per-lane reload of body_term_cached / body_term_wave (idx != lb.idx) in the wave form, the queue form's refill.
+     per-lane reload (load_row) of body_term_wave / body_term_cached (idx != lb.idx) in the wave form, the queue form's refill.
   D  mixed entries and body counts: one body whose interval is 2^210 s (one polynomial; k_body_reciprocals leaves rinv == +0.0, entry_fast
-     fails: the `all_good == false` arm, i0 masked to row 0, body_position_generic) placed first, in the middle and last, which toggles
+     fails: the `all_good == false` arm, i0 masked to row 0, body_position_generic; in the wave form the lane's entry_fast ballot sends
+     the wave to body_term_cached, whose spline_locate_fast divides with the compiler's division) placed first, in the middle and last, which toggles
      all_good from body to body; tables of 1, 2, 64 and 65 bodies (the pipeline's prologue and discarded last lookup; k_craft_wave through
      body_term in two chunks above 64); one case under set_body_order with a TNB burn whose reference body is not at its own index in the
      visiting order (bodies_by_index != bodies).
