@@ -15,8 +15,8 @@ import ctypes as C
 import numpy as np
 
 from . import systems  # noqa: F401  (state.json / ephemeris.json / ships readers)
-from ._abi import (ABI_SYMBOLS, EXCHANGE_FN, LIB_PATH, AdaptiveParams, OrbitPlotConfig, PlotRequest,  # noqa: F401  (the package's names)
-                   PlotSegment, PlotView, SeparationRequest, _dp, _fp, _i32p, _i64p, _lib, _u8p, _u32p, hip_runtime)
+from ._abi import (ABI_SYMBOLS, EXCHANGE_FN, LIB_PATH, AdaptiveParams, MarkerRequest, OrbitPlotConfig, PlotMarker,  # noqa: F401  (the package's names)
+                   PlotRequest, PlotSegment, PlotView, SeparationRequest, _dp, _fp, _i32p, _i64p, _lib, _u8p, _u32p, hip_runtime)
 
 FORWARD, BACKWARD = 1, -1
 PATH_FAST = 4
@@ -692,6 +692,33 @@ class SpacecraftBatch(_Handle):
         _call("eph_craft_batch_plot_segments", *head, total, records, _p(first, _i64p), C.byref(_plot_view(view)), *out.args())
         return segments, out.rows(total)
 
+    MARKER = np.dtype([("request", "i8"), ("kind", "i4"), ("index", "i4"), ("body", "i4"), ("status", "i4"), ("time", "f8"),
+                       ("position", "f8", 3), ("distance", "f8"), ("apsis_distance", "f8"), ("frame", "f8", 9)], align=True)  # eph_plot_marker
+
+    def plot_markers(self, requests, craft=None):
+        """The event markers of the batch's plots (eph_craft_batch_plot_markers; the app's plot_*_markers and *_marker_picking,
+        ephemeris_explorer/src/ui/world/tooltip.rs:84-245, picking.rs:256-447): request r asks, for one plot of craft craft[r]
+        (None: request r is craft r), for every burn start, SOI transition, apsis and trajectory bound of that craft inside the
+        plot's points. requests: list of dict(reference_body=-1, kinds, first, last), or one dict for all -- marker_requests()
+        builds them from the output of plot_segments(). -> (markers, first): markers a record array (MARKER: request, kind,
+        index, body, status, time, position, distance, apsis_distance, frame) request by request, manoeuvres, transitions,
+        apsides, Start, End; first[r] .. first[r + 1] the records of request r. Sizes with the records-free call, then fills."""
+        requests, (crafts,) = _per_request("SpacecraftBatch.plot_markers: one craft per request", self.n, requests, craft)
+        n = len(requests)
+        arr = (MarkerRequest * max(n, 1))()
+        for i, q in enumerate(requests):
+            arr[i] = MarkerRequest(int(q.get("reference_body", -1)), int(q["kinds"]), float(q["first"]), float(q["last"]))
+        first = np.zeros(n + 1, dtype=np.int64)
+        head = (self._h, n, arr, _p_or_null(crafts, _i64p))
+        st = _lib().eph_craft_batch_plot_markers(*head, 0, None, _p(first, _i64p))
+        total = int(first[n])
+        if st != ERR_BAD_ARGUMENT or total == 0:        # (a sizing call that is refused has written the total it needs)
+            _check(st, "eph_craft_batch_plot_markers")
+        markers = np.zeros(total, dtype=self.MARKER)
+        if total:
+            _call("eph_craft_batch_plot_markers", *head, total, markers.ctypes.data_as(C.POINTER(PlotMarker)), _p(first, _i64p))
+        return markers, first
+
     def closest_separation(self, requests, craft=None, target_craft=None):
         """The closest-separation search of target plotting on the batch's own knots (eph_craft_batch_closest_separation):
         request p searches craft craft[p] (None: request p is craft p) against body requests[p]["target_body"] of the live
@@ -895,6 +922,35 @@ def segment_name(names, segment):
     """The Name setup_segment_plotting gives a plot (analysis.rs:212,245-290), e.g. "Mars Flyby Burn": names in table order,
     segment one record of SpacecraftBatch.plot_segments."""
     return f"{names[int(segment['soi_body'])]} {SEGMENT_KINDS[int(segment['kind'])]}" + (" Burn" if int(segment["is_burn"]) else "")
+
+
+MARKER_KINDS = ("Manoeuvre", "Transition", "Periapsis", "Apoapsis", "Start", "End")
+MARK_MANOEUVRES, MARK_TRANSITIONS, MARK_APSIDES, MARK_BOUNDS = 1, 2, 4, 8
+
+
+def marker_requests(segments, plots):
+    """The requests of SpacecraftBatch.plot_markers for the output of SpacecraftBatch.plot_segments(view, ...): one per record,
+    relative to the record's reference body, between the epochs of the plot's first and last point; manoeuvres only on burn
+    pieces (BurnPlotSegment), transitions only on plots that are not an overlapping copy, apsides and bounds on every plot;
+    kinds = 0 for a plot without points. The craft of request s is the craft of entry segments["plot"][s]."""
+    out = []
+    for r, p in zip(segments, plots):
+        t = p[2]
+        if len(t) == 0:
+            out.append({"reference_body": int(r["reference_body"]), "kinds": 0, "first": 0.0, "last": 0.0})
+            continue
+        kinds = MARK_APSIDES | MARK_BOUNDS | (MARK_MANOEUVRES if r["is_burn"] else 0) | (0 if r["overlapping"] else MARK_TRANSITIONS)
+        out.append({"reference_body": int(r["reference_body"]), "kinds": kinds, "first": float(t[0]), "last": float(t[-1])})
+    return out
+
+
+def marker_name(names, marker):
+    """What the app's tooltip calls a marker ("Mars Periapsis", "Sun Transition", "Start"): names the bodies' names in table
+    order, marker one record of SpacecraftBatch.plot_markers. A manoeuvre is named after its frame's body ("Inertial" without)."""
+    kind, body = MARKER_KINDS[int(marker["kind"])], int(marker["body"])
+    if kind in ("Start", "End"):
+        return kind
+    return f"{names[body] if body >= 0 else 'Inertial'} {kind}"
 
 
 def _separation_requests(requests, craft_source=False):

@@ -49,6 +49,18 @@ class PlotSegment(C.Structure):
                 ("start", C.c_double), ("end", C.c_double)]
 
 
+class MarkerRequest(C.Structure):
+    """eph_marker_request: one plot whose event markers are asked for (PlotSource.reference + PlotPoints::contains)."""
+    _fields_ = [("reference_body", C.c_int32), ("kinds", C.c_int32), ("first", C.c_double), ("last", C.c_double)]
+
+
+class PlotMarker(C.Structure):
+    """eph_plot_marker: one marker of a plot (ephemeris_explorer/src/ui/world/tooltip.rs:84-245)."""
+    _fields_ = [("request", C.c_int64), ("kind", C.c_int32), ("index", C.c_int32), ("body", C.c_int32), ("status", C.c_int32),
+                ("time", C.c_double), ("position", C.c_double * 3), ("distance", C.c_double), ("apsis_distance", C.c_double),
+                ("frame", C.c_double * 9)]
+
+
 class SeparationRequest(C.Structure):
     """eph_separation_request: one closest-separation search of target plotting (ephemeris_explorer/src/analysis.rs:344-348)."""
     _fields_ = [("source_body", C.c_int32), ("target_body", C.c_int32), ("source_knot_first", C.c_int64),
@@ -73,6 +85,7 @@ def _signatures():
     vp, i32, i64, u32, u64, f64, text = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double, C.c_char_p
     view, plots, searches, params = C.POINTER(PlotView), C.POINTER(PlotRequest), C.POINTER(SeparationRequest), C.POINTER(AdaptiveParams)
     configs, segments = C.POINTER(OrbitPlotConfig), C.POINTER(PlotSegment)
+    marker_requests, markers = C.POINTER(MarkerRequest), C.POINTER(PlotMarker)
     knots = [i64, _dp, _dp, _dp]                                  # a (count, t, pos, vel) knot triple
     separation_out = [_u8p, _dp, _dp, _i32p, _i32p, _dp]          # found, time, distance, iterations, status, failed_at
     plot_out = [i64, _dp, _fp, _i64p, _i32p, _dp]                 # capacity, t, xyz, count, status, failed_at
@@ -171,6 +184,7 @@ def _signatures():
         "eph_craft_batch_eval": (i32, [vp, i64, _dp, i32, i32, _dp, _u8p]),
         "eph_craft_batch_plot_points": (i32, [vp, view, i64, plots, _i64p, *plot_out]),
         "eph_craft_batch_plot_segments": (i32, [vp, i64, configs, _i64p, _i32p, i64, segments, _i64p, view, *plot_out]),
+        "eph_craft_batch_plot_markers": (i32, [vp, i64, marker_requests, _i64p, i64, markers, _i64p]),
         "eph_craft_batch_closest_separation": (i32, [vp, i64, searches, _i64p, _i64p, *separation_out]),
         "eph_craft_batch_restart": (i32, [vp, _u8p, _i64p, *burns, _dp, params, _dp, _i32p]),
         "eph_craft_batch_reset_knots": (i32, [vp]),

@@ -610,6 +610,66 @@ int32_t eph_craft_batch_plot_segments(eph_craft_batch *b, int64_t n_plots, const
                                       int64_t segment_capacity, eph_plot_segment *out_segments, int64_t *out_first,
                                       const eph_plot_view *view, int64_t capacity, double *out_t, float *out_xyz,
                                       int64_t *out_count, int32_t *out_status, double *out_failed_at);
+/* ---- plot markers: the events drawn on, and picked from, a ship's plots -------------------------------------------
+ * plot_manoeuvre_markers, plot_transition_markers, plot_apsis_markers, plot_bounds_markers (ephemeris_explorer/src/ui/
+ * world/tooltip.rs:84-245) and manoeuvre_marker_picking, transition_marker_picking, apsis_marker_picking,
+ * bound_marker_picking (ui/world/picking.rs:256-447) for ships that live in an eph_craft_batch. For every plot of a ship
+ * and every burn start, SOI transition, apsis and trajectory bound of that ship they ask whether the plot's points
+ * contain the epoch (PlotPoints::contains, ui/world/plot.rs:170-173), compute relative.position(t).length() against the
+ * plot's reference body and, for a burn, the TNB frame of ReferenceFrame::transform (dynamics/spacecraft.rs:240-293) at
+ * the burn's start: the f64 trajectory work, done here one device thread per marker. PlotPoints::evaluate's f32 lerp,
+ * the camera-dependent sizes and the ray-sphere test stay with the caller, who holds the points. */
+typedef struct eph_marker_request {   /* one plot: PlotSource.reference + what PlotPoints::contains needs */
+    int32_t reference_body;           /* -1 None, else a body of the bound ephemeris, table order */
+    int32_t kinds;                    /* bit mask: 1 manoeuvres, 2 transitions, 4 apsides, 8 bounds */
+    double first, last;               /* epochs of the plot's first and last point */
+} eph_marker_request;                 /* 24 bytes */
+typedef struct eph_plot_marker {
+    int64_t request;                  /* r */
+    int32_t kind;                     /* 0 Manoeuvre 1 Transition 2 Periapsis 3 Apoapsis 4 Start 5 End */
+    int32_t index;                    /* timeline-segment / transition / apsis index in the craft's list; 0 for bounds */
+    int32_t body;                     /* burn_ref (-1 inertial) / entered body / the apsis's body / -1 */
+    int32_t status;                   /* bit 0: relative.position(time) is Some; bit 1 (manoeuvres): the frame is Some */
+    double time;
+    double position[3];               /* relative.position(time); +0.0 without bit 0 */
+    double distance;                  /* .length(); +0.0 without bit 0 */
+    double apsis_distance;            /* the Apsis's stored distance; +0.0 for other kinds */
+    double frame[9];                  /* manoeuvres with bit 1: TNB.0 column major (x_axis, y_axis, z_axis); +0.0 otherwise */
+} eph_plot_marker;                    /* 144 bytes, padding-free */
+/* Request r reads craft craft[r] of the batch (craft == NULL: request r is craft r, so n_requests <= n_craft; a craft may
+ * appear in many requests). The caller sets kinds from the plot: manoeuvres only for BurnPlotSegment plots
+ * (tooltip.rs:87, picking.rs:259), transitions only for plots that are not OverlappingPlotSegment (tooltip.rs:131,
+ * picking.rs:308), apsides and bounds for every plot, 0 for a plot without points. An epoch t of the craft is a candidate
+ * of request r iff first <= t && last >= t (PlotPoints::contains, inclusive at both ends), and EVERY candidate gets a
+ * record, whose status tells what the reference's `if let` chain would have done with it: the count is free of
+ * evaluations and independent of the table's extent. Records of a request, in this order: the burn segments of the
+ * craft's current Timeline in timeline order with t = seg.start (the flight plan's active burns; Timeline::new keeps each
+ * burn's own start and frame, ephemeris/src/propagators/spacecraft.rs:131-157); the transitions in list order; the
+ * apsides in list order (kind 2 or 3 from the apsis); Start (t = knot 0); End (t = the last knot). The lists are as the
+ * batch holds them now, with the conventions of eph_craft_batch_plot_segments (after eph_craft_batch_reset_events the
+ * newest transition only; for EPH_EVENTS_FULL what was found so far; counts clamped to the slab depth); a batch without
+ * eph_craft_batch_enable_events has empty transition and apsis lists and still gives manoeuvres and bounds.
+ * position is RelativeTrajectory::position (ephemeris/src/trajectory.rs:319-325): the craft's
+ * CubicHermiteSpline::position (:784-789; an epoch equal to a knot returns the knot's position, before the first knot and
+ * after the last it is None) minus the body's UniformSpline::position from the LIVE table, None where either is None;
+ * distance = sqrt(x*x + y*y + z*z), summed left to right. The frame (tooltip.rs:105-108) comes from the craft's inertial
+ * state_vector(seg.start) and the burn's own ref: ref >= 0: TNB::try_new(sv - body.state_vector(t)), None when the body's
+ * spline does not contain t or either try_normalize fails; ref == -1: the identity; None in both cases where the craft's
+ * state vector is. It is evaluated independently of bit 0 (picking needs bit 0 only, drawing needs both). The columns are
+ * DMat3::from_cols(x, z, y): x_axis = prograde, y_axis = radial (z), z_axis = normal (y).
+ * out_first[n_requests + 1] is the exclusive prefix sum of records per request, written whenever the arguments are valid.
+ * If the total exceeds marker_capacity nothing else is written and the status is EPH_ERR_BAD_ARGUMENT; marker_capacity ==
+ * 0 with out_markers == NULL is the sizing call (eph_craft_batch_plot_segments' convention). Results come in passes of
+ * at most 256 MB. One 4-byte count per request comes back between the count and the fill.
+ * Does not change the batch (state, knots, events, a pending retry, the FSAL stages, the deal to the lanes); works on
+ * clones; reads the LIVE table as it is when the call starts, and takes its read lock only if some request names a body
+ * or some candidate burn has ref >= 0. n_requests == 0 or an empty batch: EPH_OK, nothing written.
+ * EPH_ERR_BAD_ARGUMENT (nothing written, no device work): NULL batch; n_requests < 0; NULL requests or out_first with
+ * requests to do; craft[r] outside 0 .. n_craft - 1; craft == NULL with n_requests > n_craft; reference_body < -1 or
+ * >= n_bodies; kinds outside 0..15; NaN first or last; marker_capacity < 0; NULL out_markers with marker_capacity > 0. */
+int32_t eph_craft_batch_plot_markers(eph_craft_batch *b, int64_t n_requests, const eph_marker_request *requests,
+                                     const int64_t *craft, int64_t marker_capacity, eph_plot_marker *out_markers,
+                                     int64_t *out_first);
 
 /* ---- target plotting: the closest-separation search (ephemeris_explorer/src/analysis.rs:308-371) -------------------
  * setup_target_plotting for a batch of (trajectory, OrbitTarget) pairs, one device thread per request:

@@ -562,6 +562,49 @@ public:
         }
         return out;
     }
+    // The event markers of the batch's plots (plot_*_markers, ephemeris_explorer/src/ui/world/tooltip.rs:84-245, and *_marker_picking,
+    // ui/world/picking.rs:256-447), on the device: request r asks, for one plot of craft craft[r] (craft empty: request r is craft r),
+    // for every burn start, SOI transition, apsis and trajectory bound of that craft inside the plot's points (first <= t <= last), each
+    // with relative.position(t), its length and, for a burn, the TNB frame at its start. markers: request by request (first[r] ..
+    // first[r + 1]), manoeuvres, transitions, apsides, Start, End. marker_requests builds the requests from the output of plot_segments.
+    struct PlotMarkers {
+        std::vector<eph_plot_marker> markers;
+        std::vector<int64_t> first;
+    };
+    static const char *marker_kind(int32_t kind) {
+        static const char *const names[] = {"Manoeuvre", "Transition", "Periapsis", "Apoapsis", "Start", "End"};
+        return kind >= 0 && kind < 6 ? names[kind] : "?";
+    }
+    static std::vector<eph_marker_request> marker_requests(const PlotSegments &plots) {
+        std::vector<eph_marker_request> out(plots.segments.size());
+        for (size_t s = 0; s < out.size(); ++s) {
+            const eph_plot_segment &g = plots.segments[s];
+            const std::vector<double> &t = plots.points[s].t;
+            out[s].reference_body = g.reference_body;
+            out[s].kinds = t.empty() ? 0 : (4 | 8 | (g.is_burn ? 1 : 0) | (g.overlapping ? 0 : 2));
+            out[s].first = t.empty() ? 0.0 : t.front();
+            out[s].last = t.empty() ? 0.0 : t.back();
+        }
+        return out;
+    }
+    PlotMarkers plot_markers(const std::vector<eph_marker_request> &requests, const std::vector<int64_t> &craft = {}) const {
+        const size_t nr = requests.size();
+        if (!craft.empty() && craft.size() != nr) throw std::invalid_argument("SpacecraftBatch::plot_markers: one craft per request");
+        if (craft.empty() && nr > static_cast<size_t>(n_)) throw std::invalid_argument("SpacecraftBatch::plot_markers: more requests than craft");
+        const int64_t *cr = craft.empty() ? nullptr : craft.data();
+        PlotMarkers out;
+        out.first.assign(nr + 1, 0);
+        // the sizing call: refused with the needed total in first[nr] unless there is no marker
+        const int32_t st = eph_craft_batch_plot_markers(h_, static_cast<int64_t>(nr), requests.data(), cr, 0, nullptr, out.first.data());
+        const size_t total = static_cast<size_t>(out.first[nr]);
+        if (st != EPH_ERR_BAD_ARGUMENT || total == 0) detail::check(st, "eph_craft_batch_plot_markers");
+        if (total == 0) return out;
+        out.markers.resize(total);
+        detail::check(eph_craft_batch_plot_markers(h_, static_cast<int64_t>(nr), requests.data(), cr, static_cast<int64_t>(total), out.markers.data(),
+                                                   out.first.data()),
+                      "eph_craft_batch_plot_markers");
+        return out;
+    }
     // setup_target_plotting's search (ephemeris_explorer/src/analysis.rs:344-366) for ships that live in the batch, on the device, from
     // the knots the batch holds: RelativeTrajectory::closest_separation_between(left, right, precision, max_iterations, distance) of
     // craft craft[p] (craft empty: request p is craft p) against body requests[p].target_body of the ephemeris or craft
