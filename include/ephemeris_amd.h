@@ -482,7 +482,17 @@ int32_t eph_craft_batch_restart(eph_craft_batch *b, const uint8_t *which,
 int32_t eph_craft_batch_reset_knots(eph_craft_batch *b);
 /* Drain point for the event slabs: after the caller has read them, only the newest transition of every craft (the
  * sphere it is in) is kept, apsides are emptied and EPH_EVENTS_FULL is cleared. A craft whose slab filled up in the
- * middle of a propagate call resumes its event search from the step where it stopped at the next propagate. */
+ * middle of a propagate call resumes its event search from the step where it stopped at the next propagate.
+ * A slab counts as full while fewer than two entries are free at a step boundary; then the search stops ON the boundary and the
+ * next lists continue where the last ones ended (the kept transition is read a second time). Several crossings in one step can
+ * still fill the transition slab from INSIDE the step: the step is then searched again from its start, so the next lists may
+ * repeat entries already read, may bring entries EARLIER than the kept one, and may hold an entry that SoiTransitions::insert's
+ * same-body rule drops once its predecessor is known. Merge rule, for a caller that wants the reference's single history: pass
+ * every transition read, list after list, through SoiTransitions::insert (equal time: replace; same body as the entry before:
+ * drop), and every apsis through Apsides::insert (by time; equal time: replace). The merged lists are the reference's, with one
+ * limit: a step searched again no longer knows the sphere the craft was in at its start if that entry was dropped, so an apsis
+ * about THAT sphere between the step's start and its first transition is not reported. Draining whenever fewer entries are free
+ * than one step can bring (three or more spheres crossed in one step is rare) keeps the stop on step boundaries. */
 int32_t eph_craft_batch_reset_events(eph_craft_batch *b);
 int32_t eph_craft_batch_kernel_time(eph_craft_batch *b, double *total_ms);
 void eph_craft_batch_destroy(eph_craft_batch *b);
