@@ -212,6 +212,10 @@ __device__ __forceinline__ void pair_finish(const PairPre &p, double mu, double 
 // to the other waves of its SIMD. Same operations as pair_finish<true>, same bits. Orders 0 and 4-6 (the seeded reciprocal);
 // orders 1-3 take the compiler's schedule. Measured at N = 4096 (order 0): 36.9 against 37.3 us per step
 // (profiles/r03_step_kernel_evidence.md section 6); the division forms: profiles/r04_pair_variants.md.
+// (Round 8 measured the two scalings by a power of two, h = y * 0.5 and q * 8, as ONE integer add on the high word each -- exact
+// behind the range test, two of the 30 f64 instructions of an interaction at the integer rate. Alone: 32.80-32.92 against
+// 33.25-33.35 us per step at N = 4096. On top of the 14 / 14 / 14 / 6 deal of step_wg.hip: 31.46-31.63 against 31.25-31.48 without
+// it, 0.2 us SLOWER. Not kept: scripts/experiments/pair_expadd.patch, profiles/r08_step_kernel_evidence.md section 3.)
 constexpr int kSchedMask = 0x4 | 0x10 | 0x80;   // SALU, VMEM, DS may cross a sched_barrier; VALU stays pinned
 constexpr bool kPairStaged = kPairVariant == 0 || kDivForm;
 template <int M>

@@ -13,6 +13,13 @@
 //     <= 168 VGPRs each: on SIMDs 1-3 three pair waves that carry the SAME five bodies (1-5, 6-10, 11-15) and take one source
 //     tile each of a three-tile phase (round 7: pair work dealt by source tile); SIMD 0 a one-body pair wave (body 0, all
 //     three tiles), the chain wave (at raised issue priority) and the tail wave;
+//   * round 8: 14 / 14 / 14 / 6 units (body, source tile) per three-tile phase instead of 15 / 15 / 15 / 3. The pair SIMDs are
+//     issue-bound (about 195 issue cycles per interaction); the wave of each pair SIMD that takes the phase's third tile carries
+//     four bodies, and the three shed units (bodies 5, 10, 15 against that tile) are one block of the tail wave, which only met
+//     barriers in the tile loop. 31.18-31.36 against 33.25-33.37 us per step at N = 4096, same box, alternating, 3 x 5 blocks of
+//     500 steps; pair side alone 28.4 (was 31.1), chain side alone 25.1, SIMD 0 alone (its six units and the chain,
+//     -DEPH_WG_SIDE=3) 28.6: SIMD 0 is now as long as the pair SIMDs, so there is nothing left to move that way
+//     (profiles/r08_step_kernel_evidence.md);
 //   * ONE s_barrier per 192 sources (three 64-source tiles; the first two tiles go singly so the chain wave starts early): 23
 //     barriers for the 64 tiles of N = 4096. Six 25 KB LDS tile buffers as two sets of three: the pair waves write one phase
 //     while the chain wave sums the one before. Rounds 2-6 had one barrier per 128 sources (three sets of two buffers, pair
@@ -38,8 +45,9 @@
 #define EPH_EXPERIMENTS 0
 #endif
 // tuning builds only (scripts/build_exp.sh NAME -DEPH_EXPERIMENTS=1 -DEPH_WG_SIDE=k): 1 = the chain wave skips its sums (pair side
-// alone), 2 = the pair waves skip their tiles (chain side alone); results are then meaningless. Compile-time on purpose: the same
-// two tests as run-time flags cost the default path 3.6 us per step.
+// alone), 2 = the pair waves skip their tiles (chain side alone), 3 = the pair waves of SIMDs 1-3 skip theirs (SIMD 0 alone: its six
+// units per phase and the chain); results are then meaningless. Compile-time on purpose: the same two tests as run-time flags cost
+// the default path 3.6 us per step.
 #if !EPH_EXPERIMENTS || !defined(EPH_WG_SIDE)
 #undef EPH_WG_SIDE
 #define EPH_WG_SIDE 0
@@ -277,10 +285,6 @@ __device__ __forceinline__ void wg_idle_wave(int tiles) {
 __device__ __forceinline__ int phase_start(int P) { return P < 2 ? P : 3 * P - 4; }
 __device__ __forceinline__ int phase_count(int tiles) { return tiles <= 2 ? tiles : 2 + (tiles - 2 + 2) / 3; }
 __device__ __forceinline__ int phase_tiles(int P, int tiles) { return P < 2 ? 1 : min(3, tiles - phase_start(P)); }
-__device__ __forceinline__ void wg_idle_wave_phases(int tiles) {
-    __syncthreads();
-    for (int P = 1; P < phase_count(tiles); ++P) WG_LOOP_BARRIER();
-}
 
 // the staged term for M = MA + MB interactions in two runs (the division orders 4 and 6 carry six more doubles per interaction
 // through the stages: five at once do not fit 168 VGPRs)
@@ -302,8 +306,8 @@ __device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA
 
 // NB bodies (local indices b0..) against NT 64-source tiles: NB * NT independent interactions behind ONE range test, the staged
 // arithmetic (pair_finish_staged, pair_term.h), then the write burst. self[s]: EPH_WG_DIAG_PATCH only -- the lane that holds body
-// b0 as a source of tile s (far off: none).
-template <int NB, int NT>
+// b0 as a source of tile s (far off: none). BS: the stride of the bodies (local indices b0, b0 + BS, ...; rows 3 * body + component).
+template <int NB, int NT, int BS = 1>
 __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
                                               const Body4 (&pj)[NT], bool ieee, double *const (&tile)[NT], int b0, int lane,
                                               const int (&self)[NT]) {
@@ -320,7 +324,7 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
             pre[k] = pair_pre(xi[b], yi[b], zi[b], pj[s]);
             mus[k] = pj[s].mu;
             if constexpr (EPH_WG_DIAG_PATCH_ON) {
-                if (lane == self[s] + b) { pre[k].n2 = 1.0; pre[k].lo = 0x3ff00000u; }
+                if (lane == self[s] + BS * b) { pre[k].n2 = 1.0; pre[k].lo = 0x3ff00000u; }
             }
             worst = max(worst, range_key(pre[k].n2));
             low = min(low, pre[k].lo);
@@ -346,21 +350,23 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
 #pragma unroll
         for (int q = 0; q < 3 * NB; ++q) {
             if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(c[3 * NB * s + q]));
-            else tile[s][(3 * b0 + q) * kRow + lane] = c[3 * NB * s + q];
+            else tile[s][(3 * (b0 + BS * (q / 3)) + q % 3) * kRow + lane] = c[3 * NB * s + q];
         }
     }
 }
 
-// A pair wave of SIMDs 1-3: the five bodies b0.. of its SIMD group against ONE tile of every phase, the tile given by the wave's
-// rank among the three waves of its SIMD -- three waves of identical shape and work, one source tile loaded per wave and phase.
-// In the single-tile phases rank 0 has the tile and the other two only meet the barrier.
-template <typename PosPtr>
+// A pair wave of SIMDs 1-3: the bodies b0.. of its SIMD group against ONE tile of every phase, the tile given by the wave's rank
+// among the three waves of its SIMD -- one source tile loaded per wave and phase. In the single-tile phases rank 0 has the tile
+// and the other two only meet the barrier. Round 8: 14 / 14 / 14 / 6 units (body, source tile) per three-tile phase instead of
+// 15 / 15 / 15 / 3 -- ranks 0 and 1 carry the five bodies of the group (NB = 5), rank 2, which only ever has the THIRD tile of a
+// three-tile phase, the first four (NB = 4); the fifth bodies of the three groups (local bodies 5, 10, 15) against that tile are ONE
+// block of wave 8 on SIMD 0 (NB = 3, BS = 5, rank 2: the same loop), written to the rows the rank-2 waves would have written.
+template <int NB, int BS = 1, typename PosPtr>
 __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int b0, int rank, double *C, int lane, int tiles, int tdiag, int wbuf) {
-    constexpr int NB = 5;
     double xi[NB], yi[NB], zi[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        const int ii = min(i0 + b0 + b, n - 1);
+        const int ii = min(i0 + b0 + BS * b, n - 1);
         xi[b] = pos[ii].x;
         yi[b] = pos[ii].y;
         zi[b] = pos[ii].z;
@@ -373,12 +379,12 @@ __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int
     };
     auto tile_of = [&](int P) { return P < 2 ? (rank == 0 ? P : tiles) : phase_start(P) + rank; };   // >= tiles: none
     auto produce = [&](int t, const Body4 &pj) {
-        if (t >= tiles || EPH_WG_SIDE == 2) return;
+        if (t >= tiles || EPH_WG_SIDE == 2 || (EPH_WG_SIDE == 3 && BS == 1)) return;
         const Body4 src[1] = {pj};
         double *const dst[1] = {C + (t % kWgTileBufs) * wbuf};
         // (bodies beyond n are clamped copies of body n - 1: never diagonal lanes)
         const int self[1] = {EPH_WG_DIAG_PATCH_ON && t == tdiag ? i0 + b0 - t * kTile : -64};
-        wg_pair_block<NB, 1>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self);
+        wg_pair_block<NB, 1, BS>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self);
     };
     const int NP = phase_count(tiles);
     Body4 pj = load_src(tile_of(0)), pjn = load_src(tile_of(1));
@@ -390,6 +396,16 @@ __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int
         produce(tile_of(P), pj);
         WG_LOOP_BARRIER();
     }
+}
+// wave 8 in the tile loop (the tail wave of k_lm_step_wg, between loading its history and the integrator's work; in k_accel_wg its
+// only work): the fifth bodies of the three SIMD groups against the third tile of every three-tile phase, behind one range test and
+// one ballot, through pair_finish_staged<3>. (The same six units per phase on SIMD 0 with the one-body wave carrying all of them and
+// this wave only meeting the barriers -- two waves beside the chain's adds instead of three -- measured 31.41-31.56 against
+// 31.18-31.36 us per step: scripts/experiments/wg_solo6.patch.)
+constexpr int kWgShedFirst = 5, kWgShedStride = 5, kWgShedBodies = 3;
+template <typename PosPtr>
+__device__ __forceinline__ void wg_tail_wave_phases(PosPtr pos, int n, int i0, double *C, int lane, int tiles, int tdiag, int wbuf) {
+    wg_pair_wave_deal<kWgShedBodies, kWgShedStride>(pos, n, i0, kWgShedFirst, 2, C, lane, tiles, tdiag, wbuf);
 }
 // The one-body pair wave of the chain wave's SIMD: body 0 against every tile of the phase (three interactions at once)
 template <typename PosPtr>
@@ -558,13 +574,16 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
     } else {
         // Roles of the twelve waves (wave k runs on SIMD k % 4, so waves k and k + 4 share a SIMD whatever the start of the
         // hardware's cyclic order): wave id = 1, 2, 3 (mod 4) are the pair waves of SIMD group id % 4 -- bodies 1-5, 6-10, 11-15 --
-        // and take the tile of the phase given by their rank id >> 2; wave 0 is the one-body pair wave (body 0) beside the chain
-        // wave (4) and the tail wave (8). ONE copy of the five-body pair loop, the first body and the rank run-time scalars
-        // (inlining the loop once per role measured 0.15 us slower in round 4 and is 40 KB more code per evaluation order).
+        // and take the tile of the phase given by their rank id >> 2 (rank 2: the first four bodies only); wave 0 is the one-body
+        // pair wave (body 0) beside the chain wave (4) and the tail wave (8: bodies 5, 10, 15 against the third tile). TWO copies of
+        // the pair loop of SIMDs 1-3, five bodies and four, the first body and the rank run-time scalars (inlining the loop once
+        // per role measured 0.15 us slower in round 4 and is 40 KB more code per evaluation order).
         const int w = __builtin_amdgcn_readfirstlane(wave);
         if (w == 0) { wg_pair_wave_solo(pos, n, i0, C, lane, tiles, tdiag, kBuf); return 0.0; }
-        if (w & 3) { wg_pair_wave_deal(pos, n, i0, 5 * (w & 3) - 4, w >> 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
-        if (w == kWgTailWave) { wg_idle_wave_phases(tiles); return 0.0; }   // (k_lm_step_wg gives this wave the integrator's work instead)
+        if ((w & 3) && w < 8) { wg_pair_wave_deal<5>(pos, n, i0, 5 * (w & 3) - 4, w >> 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
+        if (w & 3) { wg_pair_wave_deal<4>(pos, n, i0, 5 * (w & 3) - 4, 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
+        // (k_lm_step_wg gives this wave the integrator's work around the same call)
+        if (w == kWgTailWave) { wg_tail_wave_phases(pos, n, i0, C, lane, tiles, tdiag, kBuf); return 0.0; }
     }
     // chain wave. Its dependent adds issue ahead of the one-body pair wave of its SIMD (s_setprio; the same library with and
     // without, alternating on one box: 36.3 against 36.8 us per step at N = 4096 on two boxes of the pool, 36.2 either way on a
@@ -696,7 +715,7 @@ k_lm_step_wg(const LmArgs a) {
         if constexpr (wg_tile_split(WB) && !DUO) {
             for (int t = 0; t <= tiles; ++t) __syncthreads();                             // one barrier per tile there
         } else if constexpr (WB == kWgBodies && !DUO) {
-            wg_idle_wave_phases(tiles);
+            wg_tail_wave_phases(a.pos_cur, a.n, i0, C, lane, tiles, i0 / kTile, 3 * WB * kRow);
         } else {
             wg_idle_wave(tiles);
         }

@@ -20,8 +20,12 @@ for n in (4096, 2048):
     while time.time() - t < 1.0:
         lib.eph_nbody_advance(h, 500); lib.eph_nbody_sync(h)
     lib.eph_nbody_enable_timing(h, 1)
+    ms, l = C.c_double(), C.c_uint64()
+    blocks, m0, l0 = [], 0.0, 0
     for rep in range(5):
         lib.eph_nbody_advance(h, 500); lib.eph_nbody_sync(h)
-    ms, l = C.c_double(), C.c_uint64()
-    lib.eph_nbody_kernel_time(h, C.byref(ms), C.byref(l))
-    print(os.path.basename(sys.argv[1]), n, "%.2f us/step" % (ms.value / l.value * 1e3), flush=True)
+        lib.eph_nbody_kernel_time(h, C.byref(ms), C.byref(l))      # cumulative since enable_timing
+        blocks.append((ms.value - m0) / (l.value - l0) * 1e3)
+        m0, l0 = ms.value, l.value
+    print(os.path.basename(sys.argv[1]), n, "%.2f us/step" % (ms.value / l.value * 1e3),
+          "blocks", " ".join("%.2f" % b for b in blocks), flush=True)
