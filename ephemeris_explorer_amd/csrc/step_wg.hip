@@ -30,6 +30,11 @@
 //     (scripts/experiments/wg_deal128.patch). Keeping a phase's results in registers across the barrier and issuing the ds_writes
 //     at the head of the NEXT phase (nothing drains before the barrier; the chain wave one phase further behind) was built
 //     and measured as well: bit-identical and 1.4 us slower (35.53-35.63 against 34.15-34.25 for the same build without it);
+//   * round 9: the same deferral for the producers of the THIRD tile of a phase only (the rank-2 waves, wave 8's block, the one-body
+//     wave's third interaction: 4 of the 10 write bursts): 29.84-30.10 against 31.22-31.36 us per step at N = 4096, same box,
+//     alternating, 3 x 5 blocks of 500 steps; the schedule and its buffer lifetimes are stated above phase_start. Different
+//     s_setprio levels for the three pair waves of a SIMD (2 / 1 / 0 by rank, and the reverse) on top of it: 33.39-33.57 and
+//     32.98-33.09, three us SLOWER (scripts/experiments/wg_rank_prio.patch; profiles/r09_step_kernel_evidence.md);
 //   * the tail wave (k_lm_step_wg) loads the 2 L history values while the others work, receives the new acceleration through
 //     LDS and does Cowell's velocity, the solout sample and the predictor;
 //   * 8- and 4-body workgroups for target counts that would leave CUs without a 16-body workgroup (<= 2048 / <= 1024 targets): the
@@ -59,6 +64,18 @@
 #define EPH_WG_ABLATE 0
 #endif
 #define WG_LOOP_BARRIER() do { if constexpr (!(EPH_WG_ABLATE & 2)) __syncthreads(); } while (0)
+// Where a wave that holds a phase's third tile over the barrier (phase_start below) issues the late ds_writes inside the next
+// interval's block (wg_pair_block): 0 = at the head, before the pre-stage; 1 = behind the range test, before the staged arithmetic
+// (the compiler merges the two sides of the test and spreads the stores over the pre-stage); 2 = between two runs of the staged
+// arithmetic (half the block's interactions each); 3 = behind the arithmetic. A constant in the product;
+// -DEPH_EXPERIMENTS=1 -DEPH_WG_LATE_AT=k for the tuning builds. Measured at N = 4096, us per step, parent 31.14-31.26:
+// 0: 29.79-29.98, 1: 33.30-33.45, 2: 32.42-32.50, 3: 31.67-31.86 (profiles/r09_step_kernel_evidence.md). The head it is: behind the
+// barrier the LDS store path has nothing else to do (the chain wave opens its interval with reads), and a third of the producers
+// is not the burst of all ten that round 7 put there.
+#if !EPH_EXPERIMENTS || !defined(EPH_WG_LATE_AT)
+#undef EPH_WG_LATE_AT
+#define EPH_WG_LATE_AT 0
+#endif
 // MEASURED, NOT THE DEFAULT (-DEPH_EXPERIMENTS=1 -DEPH_WG_DIAG_PATCH=1): the pair waves that meet the workgroup's own tile take the
 // IEEE form for it (n2 = 0 on the self lanes fails the range test of the whole wave): about 1.8 x the instructions for that wave in
 // one phase. With the switch the self lanes get in-range operands instead (n2 = 1; their contribution is read and discarded by
@@ -280,16 +297,42 @@ __device__ __forceinline__ void wg_idle_wave(int tiles) {
 // The same six tile buffers as two sets of three: phases 0 and 1 are the single tiles 0 and 1 (the chain wave starts as early as
 // before), phase P >= 2 is the tiles 3 P - 4 .. 3 P - 2. Tile t lives in buffer t % 6, so even phases >= 2 own buffers {2, 3, 4}, odd
 // ones {5, 0, 1}; the single tiles (buffers 0 and 1) have been summed two barriers before phase 3 writes there. The chain wave sums
-// phase P while the pair waves write phase P + 1. Every wave executes phase_count(tiles) barriers: B_0 after tile 0 is in LDS, then
-// one behind every phase but the last (which the chain wave sums alone; the buffers are dead after it).
+// phase P while the pair waves work on phase P + 1. Rounds 7 and 8: every tile of a phase written before the phase's barrier,
+// phase_count(tiles) barriers for every wave -- B_0 after tile 0 is in LDS, then one behind every phase but the last.
+//
+// Round 9, the LATE THIRD TILE. Call the tiles of a three-tile phase P a, b, c (c = phase_start(P) + 2; the single-tile phases and a
+// last phase of one or two tiles have none). Every producer of c -- the rank-2 waves of SIMDs 1-3, the three-body block of wave 8,
+// the third interaction of the one-body wave -- computes it in interval P as before (interval P: between barriers B_(P-1) and
+// B_P), keeps the contributions in registers across B_P and issues the ds_writes inside its block of interval P + 1, where its own
+// arithmetic covers their drain; a and b are written before B_P as before. The chain wave therefore sums, behind B_I, the tiles
+// {c(I-1), a(I), b(I)}: still three consecutive tiles in source order with the same prefetch pattern, two tiles (a, b) behind B_2,
+// and, when the LAST phase has a c, that tile alone behind one more barrier: interval_count(tiles) barriers for every wave.
+// Buffer lifetimes, tile t in buffer t % 6 as before: c(P) is written in interval P + 1 and read in interval P + 2; the next user of
+// its buffer is c(P + 2), written in interval P + 3. a(P) and b(P) are written in interval P and read in P + 1; their buffers are
+// next written in P + 2 (a(P + 2), b(P + 2)). Tiles 0 and 1 are read in intervals 1 and 2, their buffers next written in
+// intervals 3 (b(3)) and 4 (c(3)). No buffer is written while it is read -- with SIX buffers, and only because EVERY producer of c
+// is late: the one-body wave writing c(P) early would overwrite c(P - 2) while the chain wave reads it. In the interval of the
+// first c there is nothing held yet; the block then stores zeros to that c's own buffer, idle until the real values follow one
+// interval later (the block stays free of a branch around the stores).
+// Orders 0, 4 and 5 only: with the same schedule orders 1, 2, 3 and 6 LOSE about 2.2 us per step (35.36 / 35.36 / 39.76 / 38.64
+// against 33.12 / 33.49 / 37.56 / 36.07 at N = 4096, the stores at the head in the generated code of all of them) and keep the
+// schedule of round 8, third tiles written before their phase's barrier (profiles/r09_step_kernel_evidence.md section 6).
+constexpr bool kWgLateThird = kPairVariant == 0 || kPairVariant == 4 || kPairVariant == 5;
+static_assert(kWgTileBufs == 6, "the late third tile needs tile t + 6 to be written two intervals after tile t was read");
 __device__ __forceinline__ int phase_start(int P) { return P < 2 ? P : 3 * P - 4; }
 __device__ __forceinline__ int phase_count(int tiles) { return tiles <= 2 ? tiles : 2 + (tiles - 2 + 2) / 3; }
 __device__ __forceinline__ int phase_tiles(int P, int tiles) { return P < 2 ? 1 : min(3, tiles - phase_start(P)); }
+// barriers of the tile loop: one more than phases when the last phase has a third tile
+__device__ __forceinline__ int interval_count(int tiles) { return phase_count(tiles) + (kWgLateThird && tiles >= 5 && (tiles - 2) % 3 == 0); }
+// the tiles the chain wave sums behind barrier B_I: [chain_first(I), chain_first(I + 1)) cut at `tiles`
+__device__ __forceinline__ int chain_first(int I) { return kWgLateThird ? (I <= 2 ? I : 3 * I - 5) : phase_start(I); }
 
 // the staged term for M = MA + MB interactions in two runs (the division orders 4 and 6 carry six more doubles per interaction
 // through the stages: five at once do not fit 168 VGPRs)
-template <int MA, int MB>
-__device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA + MB], const double (&mu)[MA + MB], double (&c)[3 * (MA + MB)]) {
+struct NoHook { __device__ __forceinline__ void operator()() const {} };
+template <int MA, int MB, typename Between = NoHook>
+__device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA + MB], const double (&mu)[MA + MB], double (&c)[3 * (MA + MB)],
+                                                         Between between = Between()) {
     PairPre pa[MA], pb[MB];
     double ma[MA], mb[MB], ca[3 * MA], cb[3 * MB];
 #pragma unroll
@@ -297,6 +340,7 @@ __device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA
 #pragma unroll
     for (int k = 0; k < MB; ++k) { pb[k] = pre[MA + k]; mb[k] = mu[MA + k]; }
     pair_finish_staged<MA>(pa, ma, ca);
+    between();
     pair_finish_staged<MB>(pb, mb, cb);
 #pragma unroll
     for (int k = 0; k < 3 * MA; ++k) c[k] = ca[k];
@@ -307,11 +351,21 @@ __device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA
 // NB bodies (local indices b0..) against NT 64-source tiles: NB * NT independent interactions behind ONE range test, the staged
 // arithmetic (pair_finish_staged, pair_term.h), then the write burst. self[s]: EPH_WG_DIAG_PATCH only -- the lane that holds body
 // b0 as a source of tile s (far off: none). BS: the stride of the bodies (local indices b0, b0 + BS, ...; rows 3 * body + component).
-template <int NB, int NT, int BS = 1>
+// LATE (the late third tile, phase_start above): the contributions of the LAST tile are not written but left in `held`, and what
+// `held` brought in -- the same rows of the third tile of the phase before -- is written to `held_tile` at EPH_WG_LATE_AT.
+template <int NB, int NT, int BS = 1, bool LATE = false>
 __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
                                               const Body4 (&pj)[NT], bool ieee, double *const (&tile)[NT], int b0, int lane,
-                                              const int (&self)[NT]) {
+                                              const int (&self)[NT], double (&held)[3 * NB], double *held_tile) {
     constexpr int M = NB * NT;
+    auto write_held = [&]() {
+#pragma unroll
+        for (int q = 0; q < 3 * NB; ++q) {
+            if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(held[q]));
+            else held_tile[(3 * (b0 + BS * (q / 3)) + q % 3) * kRow + lane] = held[q];
+        }
+    };
+    if constexpr (LATE && EPH_WG_LATE_AT == 0) write_held();
     PairPre pre[M];
     double mus[M];
     unsigned worst = ieee ? kRangeSpan : 0u, low = ~0u;
@@ -332,8 +386,12 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
     }
     worst = max(worst, low_key(low));
     double c[3 * M];
+    constexpr bool kLateMid = LATE && kPairStaged && EPH_WG_LATE_AT == 2 && M >= 2;
     if (__builtin_amdgcn_ballot_w64(worst >= kRangeSpan) == 0) {
-        if constexpr (kPairStaged && M == 5 && (kPairVariant == 4 || kPairVariant == 6)) {
+        if constexpr (LATE && (EPH_WG_LATE_AT == 1 || (EPH_WG_LATE_AT == 2 && !kLateMid))) write_held();
+        if constexpr (kLateMid) {
+            pair_finish_staged_split<M - M / 2, M / 2>(pre, mus, c, write_held);
+        } else if constexpr (kPairStaged && M == 5 && (kPairVariant == 4 || kPairVariant == 6)) {
             pair_finish_staged_split<3, 2>(pre, mus, c);
         } else if constexpr (kPairStaged) {
             pair_finish_staged<M>(pre, mus, c);
@@ -342,17 +400,30 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
             for (int k = 0; k < M; ++k) pair_finish<true>(pre[k], mus[k], c[3 * k], c[3 * k + 1], c[3 * k + 2]);
         }
     } else {   // the tile holding the workgroup's own bodies (n2 = 0 on the self lane) or an operand outside the guarded ranges
+        if constexpr (LATE && (EPH_WG_LATE_AT == 1 || EPH_WG_LATE_AT == 2)) write_held();
 #pragma unroll
         for (int k = 0; k < M; ++k) pair_finish<false>(pre[k], mus[k], c[3 * k], c[3 * k + 1], c[3 * k + 2]);
     }
+    if constexpr (LATE && EPH_WG_LATE_AT == 3) write_held();
 #pragma unroll
-    for (int s = 0; s < NT; ++s) {
+    for (int s = 0; s < NT - LATE; ++s) {
 #pragma unroll
         for (int q = 0; q < 3 * NB; ++q) {
             if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(c[3 * NB * s + q]));
             else tile[s][(3 * (b0 + BS * (q / 3)) + q % 3) * kRow + lane] = c[3 * NB * s + q];
         }
     }
+    if constexpr (LATE) {
+#pragma unroll
+        for (int q = 0; q < 3 * NB; ++q) held[q] = c[3 * NB * (NT - 1) + q];
+    }
+}
+template <int NB, int NT, int BS = 1>
+__device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
+                                              const Body4 (&pj)[NT], bool ieee, double *const (&tile)[NT], int b0, int lane,
+                                              const int (&self)[NT]) {
+    double none[3 * NB];
+    wg_pair_block<NB, NT, BS, false>(xi, yi, zi, pj, ieee, tile, b0, lane, self, none, nullptr);
 }
 
 // A pair wave of SIMDs 1-3: the bodies b0.. of its SIMD group against ONE tile of every phase, the tile given by the wave's rank
@@ -378,23 +449,60 @@ __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int
         return pos[j < n ? j : n - 1];
     };
     auto tile_of = [&](int P) { return P < 2 ? (rank == 0 ? P : tiles) : phase_start(P) + rank; };   // >= tiles: none
-    auto produce = [&](int t, const Body4 &pj) {
-        if (t >= tiles || EPH_WG_SIDE == 2 || (EPH_WG_SIDE == 3 && BS == 1)) return;
-        const Body4 src[1] = {pj};
-        double *const dst[1] = {C + (t % kWgTileBufs) * wbuf};
-        // (bodies beyond n are clamped copies of body n - 1: never diagonal lanes)
-        const int self[1] = {EPH_WG_DIAG_PATCH_ON && t == tdiag ? i0 + b0 - t * kTile : -64};
-        wg_pair_block<NB, 1, BS>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self);
-    };
-    const int NP = phase_count(tiles);
-    Body4 pj = load_src(tile_of(0)), pjn = load_src(tile_of(1));
-    produce(tile_of(0), pj);
-    __syncthreads();
-    for (int P = 1; P < NP; ++P) {
-        pj = pjn;
-        pjn = load_src(tile_of(P + 1));
-        produce(tile_of(P), pj);
-        WG_LOOP_BARRIER();
+    constexpr bool kOff = EPH_WG_SIDE == 2 || (EPH_WG_SIDE == 3 && BS == 1);
+    const int NI = interval_count(tiles);
+    [[maybe_unused]] const int NP = kWgLateThird ? phase_count(tiles) : NI;
+    if constexpr (NB == 5 || !kWgLateThird) {   // ranks 0 and 1: tiles a and b, written before the phase's barrier
+        auto produce = [&](int t, const Body4 &pj) {
+            if (t >= tiles || kOff) return;
+            const Body4 src[1] = {pj};
+            double *const dst[1] = {C + (t % kWgTileBufs) * wbuf};
+            // (bodies beyond n are clamped copies of body n - 1: never diagonal lanes)
+            const int self[1] = {EPH_WG_DIAG_PATCH_ON && t == tdiag ? i0 + b0 - t * kTile : -64};
+            wg_pair_block<NB, 1, BS>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self);
+        };
+        Body4 pj = load_src(tile_of(0)), pjn = load_src(tile_of(1));
+        produce(tile_of(0), pj);
+        __syncthreads();
+        for (int P = 1; P < NP; ++P) {
+            pj = pjn;
+            pjn = load_src(tile_of(P + 1));
+            produce(tile_of(P), pj);
+            WG_LOOP_BARRIER();
+        }
+        if (NI > NP) WG_LOOP_BARRIER();                 // the last phase's third tile is written behind the phase's barrier
+    } else {                   // rank 2: tile c of every three-tile phase, computed in its interval and written in the next
+        static_assert(NB < 5, "the late loop is the rank-2 waves' (four bodies) and wave 8's (three)");
+        double held[3 * NB];
+#pragma unroll
+        for (int q = 0; q < 3 * NB; ++q) held[q] = 0.0;
+        int tprev = tile_of(2);                         // nothing held in the interval of the first c: zeros to its own buffer
+        Body4 pj, pjn = load_src(tile_of(2));
+        __syncthreads();
+        for (int I = 1; I < NI; ++I) {
+            const int t = I < 2 ? tiles : tile_of(I);
+            if (I >= 2) {
+                pj = pjn;
+                pjn = load_src(tile_of(I + 1));
+            }
+            double *const late = C + (tprev % kWgTileBufs) * wbuf;
+            if (kOff) {
+            } else if (t < tiles) {
+                const Body4 src[1] = {pj};
+                double *const dst[1] = {nullptr};       // the block's only tile is held
+                const int self[1] = {EPH_WG_DIAG_PATCH_ON && t == tdiag ? i0 + b0 - t * kTile : -64};
+                wg_pair_block<NB, 1, BS, true>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self, held, late);
+                tprev = t;
+            } else if (tprev < tiles && I > 2) {       // behind the last c: its writes alone
+#pragma unroll
+                for (int q = 0; q < 3 * NB; ++q) {
+                    if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(held[q]));
+                    else late[(3 * (b0 + BS * (q / 3)) + q % 3) * kRow + lane] = held[q];
+                }
+                tprev = tiles;
+            }
+            WG_LOOP_BARRIER();
+        }
     }
 }
 // wave 8 in the tile loop (the tail wave of k_lm_step_wg, between loading its history and the integrator's work; in k_accel_wg its
@@ -421,18 +529,37 @@ __device__ __forceinline__ void wg_pair_wave_solo(PosPtr pos, int n, int i0, dou
         s[0] = load_src(t);
         if (P >= 2) { s[1] = load_src(t + 1); s[2] = load_src(t + 2); }
     };
-    const int NP = phase_count(tiles);
+    const int NI = interval_count(tiles), NP = kWgLateThird ? phase_count(tiles) : NI;
+    // the third interaction of a three-tile phase is held over the barrier like the rank-2 waves' tiles (phase_start above)
+    double held[3] = {0.0, 0.0, 0.0};
+    int tprev = tiles;                                  // the tile in `held` (tiles: none)
+    auto write_held = [&]() {
+        if (tprev >= tiles) return;
+        double *const late = C + (tprev % kWgTileBufs) * wbuf;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(held[q]));
+            else late[q * kRow + lane] = held[q];
+        }
+        tprev = tiles;
+    };
     auto produce = [&](int P, const Body4 (&s)[3]) {
-        if (P >= NP || EPH_WG_SIDE == 2) return;
+        if (EPH_WG_SIDE == 2) return;
+        if (P >= NP) { write_held(); return; }
         const int t = phase_start(P), cnt = phase_tiles(P, tiles);
         if (cnt == 3) {
-            double *const dst[3] = {C + (t % kWgTileBufs) * wbuf, C + ((t + 1) % kWgTileBufs) * wbuf, C + ((t + 2) % kWgTileBufs) * wbuf};
+            double *const dst[3] = {C + (t % kWgTileBufs) * wbuf, C + ((t + 1) % kWgTileBufs) * wbuf,
+                                    kWgLateThird ? nullptr : C + ((t + 2) % kWgTileBufs) * wbuf};
             const bool own = tdiag >= t && tdiag < t + 3;
             int self[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) self[k] = EPH_WG_DIAG_PATCH_ON && tdiag == t + k ? i0 - (t + k) * kTile : -64;
-            wg_pair_block<1, 3>(xi, yi, zi, s, !EPH_WG_DIAG_PATCH_ON && own, dst, 0, lane, self);
+            // (nothing held in the interval of the first c: zeros to its own buffer)
+            double *const late = C + ((tprev < tiles ? tprev : t + 2) % kWgTileBufs) * wbuf;
+            wg_pair_block<1, 3, 1, kWgLateThird>(xi, yi, zi, s, !EPH_WG_DIAG_PATCH_ON && own, dst, 0, lane, self, held, late);
+            if constexpr (kWgLateThird) tprev = t + 2;
         } else {   // the single tiles and a short last phase
+            write_held();
             auto one = [&](int k, const Body4 &pj) {
                 const Body4 src[1] = {pj};
                 double *const dst[1] = {C + ((t + k) % kWgTileBufs) * wbuf};
@@ -448,7 +575,7 @@ __device__ __forceinline__ void wg_pair_wave_solo(PosPtr pos, int n, int i0, dou
     load_phase(1, sn);
     produce(0, s);
     __syncthreads();
-    for (int P = 1; P < NP; ++P) {
+    for (int P = 1; P < NI; ++P) {                      // (P = NP, when the last phase has a third tile: its writes alone)
 #pragma unroll
         for (int k = 0; k < 3; ++k) s[k] = sn[k];
         load_phase(P + 1, sn);
@@ -598,10 +725,11 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
     if constexpr (WB == kWgBodies && !DUO) {
         // phases of up to three tiles. Until the barrier that ends phase P every buffer outside P is being written, so a phase
         // opens with the load of its own first two chunks; inside a phase tile t + 1 is prefetched while tile t is summed.
-        const int NP = phase_count(tiles);
+        // Behind barrier B_P the complete tiles are c of phase P - 1 and a, b of phase P (phase_start above).
+        const int NP = interval_count(tiles);
         __syncthreads();                              // B_0: tile 0 ready
         for (int P = 0; P < NP; ++P) {
-            const int t0 = phase_start(P), nt = phase_tiles(P, tiles);
+            const int t0 = chain_first(P), nt = min(chain_first(P + 1), tiles) - t0;
             // three whole tiles of other workgroups' bodies (all but a handful of phases): written out, the prefetch registers
             // never change hands. (As a loop over the tiles of the phase with the masked form inside, the optimiser left it rolled
             // and rotated the 128 prefetch registers through moves behind an lgkmcnt(0): 40.3 us per step at N = 4096.)
@@ -627,7 +755,7 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
                     chain_masked<WB>(r, cnt, t == tdiag ? gself : -1, lit, acc, accL);
                 }
             }
-            if (P + 1 < NP) WG_LOOP_BARRIER();        // phase P consumed, phase P + 1 ready
+            if (P + 1 < NP) WG_LOOP_BARRIER();        // these tiles consumed, the next ready
         }
         return accL + acc;
     }
