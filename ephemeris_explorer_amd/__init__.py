@@ -565,6 +565,49 @@ class SpacecraftBatch(_Handle):
         """SpacecraftPropagator: Clone -- a deep copy (state, knots, events) that can be resumed independently."""
         return self._clone("eph_craft_batch_clone")
 
+    @classmethod
+    def gather(cls, sources, source_of=None, craft_of=None):
+        """A new batch whose craft i is craft craft_of[i] of sources[source_of[i]], as it is now, bit for bit
+        (eph_craft_batch_gather): removing, adding, splitting, merging, permuting and duplicating ships are all this call. source_of
+        None: every craft from the one source; craft_of None (and source_of None): all sources concatenated in order. The sources
+        must share ephemeris, method, parameters, body order, a pending retry_failed and the event setup (ValueError names the first
+        disagreement); they are not changed and stay independent of the result."""
+        sources = list(sources)
+        if not sources:
+            raise ValueError("SpacecraftBatch.gather: at least one source batch")
+        handles = (C.c_void_p * len(sources))(*[s._h for s in sources])
+        co = None if craft_of is None else np.ascontiguousarray(craft_of, dtype=np.int64).reshape(-1)
+        so = None if source_of is None else np.ascontiguousarray(source_of, dtype=np.int32).reshape(-1)
+        if so is not None and (co is None or len(so) != len(co)):
+            raise ValueError("SpacecraftBatch.gather: source_of needs a craft_of of the same length")
+        n_out = sum(s.n for s in sources) if co is None else len(co)
+        if co is not None and n_out == 0:            # an empty selection is still a selection: craft_of stays a pointer
+            co = np.zeros(1, dtype=np.int64)
+            so = None if so is None else np.zeros(1, dtype=np.int32)
+        h = C.c_void_p()
+        st = _lib().eph_craft_batch_gather(len(sources), handles, n_out, _p_or_null(so, _i32p), _p_or_null(co, _i64p), C.byref(h))
+        if st == ERR_BAD_ARGUMENT:
+            raise ValueError(_lib().eph_last_error().decode() or "SpacecraftBatch.gather: bad argument")
+        _check(st, "eph_craft_batch_gather")
+        first = sources[0]
+        attributes = {k: v for k, v in vars(first).items() if k not in ("_L", "_h", "_owned")}
+        attributes["n"] = int(n_out)
+        return cls._adopt(h, **attributes)
+
+    def select(self, indices):
+        """The craft `indices` of this batch (in that order; an index may repeat), or those a boolean mask keeps, as a new batch."""
+        idx = np.asarray(indices)
+        if idx.dtype == bool:
+            if idx.shape != (self.n,):
+                raise ValueError("SpacecraftBatch.select: a mask has one entry per craft")
+            idx = np.flatnonzero(idx)
+        return type(self).gather([self], None, idx.astype(np.int64).reshape(-1))
+
+    @classmethod
+    def concat(cls, batches):
+        """All craft of `batches`, in order, as one new batch."""
+        return cls.gather(batches)
+
     def retry_failed(self):
         """Re-arm: the NEXT propagate / step_n steps the craft whose last step returned a StepError too -- the reference's next
         step() on a propagator that returned Err (how a stored ship propagator resumes once the ephemeris has grown)."""

@@ -180,6 +180,7 @@ def _signatures():
         "eph_craft_batch_knots": (i32, [vp, i64, _dp, _dp, _dp]),
         "eph_craft_batch_kernel_time": (i32, [vp, _dp]),
         "eph_craft_batch_clone": (i32, [vp, _vpp]),
+        "eph_craft_batch_gather": (i32, [i32, _vpp, i64, _i32p, _i64p, _vpp]),
         "eph_craft_batch_knot_slabs": (i32, [vp, i32, i32, _dp, _dp]),
         "eph_craft_batch_eval": (i32, [vp, i64, _dp, i32, i32, _dp, _u8p]),
         "eph_craft_batch_plot_points": (i32, [vp, view, i64, plots, _i64p, *plot_out]),

@@ -200,22 +200,22 @@ static int craft_sort_mode() {
     static const int mode = [] { const char *e = getenv("EPH_CRAFT_SORT"); return !e || !*e ? 2 : (e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2)); }();
     return mode;
 }
-static int craft_sort(eph_craft_batch *b) {
+int eph::craft_sort(eph_craft_batch *b, bool knot0_to_lanes) {
     const long long n = b->n;
     const int mode = craft_sort_mode();
-    if (mode == 0 || (mode == 1 && !b->heterogeneous) || n < 128 || n > 0x7fffffffLL) return EPH_OK;
+    if (craft_wave_form(n) || mode == 0 || (mode == 1 && !b->heterogeneous) || n < 128 || n > 0x7fffffffLL) return EPH_OK;
     // Transfers through the process's pinned staging buffer (mem.cpp), moved by kernels: no pinning and unpinning of three
     // short-lived host vectors per creation.
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;    // 16-byte granules for k_copy16
     DevBuf<float> tau;
     int st = tau.alloc(n4);
     if (st) return st;
+    StreamIdleOnExit idle(b->stream);                  // (declared after tau: a failed allocation below leaves with k_craft_tau done)
     EPH_LAUNCH("k_craft_tau", k_craft_tau, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, n, b->eph->n_bodies, b->eph->bodies.p,
                b->eph->coeffs.p, b->time.p, b->y.p, tau.p);
     if ((st = b->perm.alloc(n4)) || (st = b->slot_of.alloc(n4))) return st;
     PinnedStage stage(2 * n4 * sizeof(int));
     if (stage.status()) return stage.status();
-    StreamIdleOnExit idle(b->stream);
     const unsigned cgrid = (unsigned)std::min<size_t>((n4 / 4 + 255) / 256, 4096);
     EPH_LAUNCH("k_copy16", k_copy16, dim3(cgrid), dim3(256), b->stream, (long long)(n4 / 4), (const double2 *)tau.p, (double2 *)stage.dev());
     EPH_HIP(hipStreamSynchronize(b->stream));
@@ -251,8 +251,9 @@ static int craft_sort(eph_craft_batch *b) {
     EPH_LAUNCH("k_copy16", k_copy16, dim3(cgrid), dim3(256), b->stream, (long long)(n4 / 4), (const double2 *)(dp + n4), (double2 *)b->slot_of.p);
     b->h_slot = std::move(slot);
     // knot 0 (the initial state, uploaded in craft order) moves to the lanes' columns
-    EPH_LAUNCH("k_knot0_to_lanes", k_knot0_to_lanes, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, n, b->perm.p, b->time.p,
-               b->y.p, b->knot_t.p, b->knot_y.p);
+    if (knot0_to_lanes)
+        EPH_LAUNCH("k_knot0_to_lanes", k_knot0_to_lanes, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, n, b->perm.p, b->time.p,
+                   b->y.p, b->knot_t.p, b->knot_y.p);
     EPH_HIP(hipStreamSynchronize(b->stream));
     return EPH_OK;
 }
@@ -429,7 +430,7 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
             EPH_HIP(hipMemcpy(b->knot_t.p, t0, sizeof(double) * n, hipMemcpyHostToDevice));
             EPH_HIP(hipMemcpy(b->knot_y.p, ysoa.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice));
             b->heterogeneous = craft_time_scales_differ(*e, n, t0, pos);
-            if (!craft_wave_form(n) && (st = craft_sort(b.get()))) return st;
+            if ((st = craft_sort(b.get(), true))) return st;
         }
         b->h_seg_off = std::move(seg_off);
         b->h_segs = std::move(segs);

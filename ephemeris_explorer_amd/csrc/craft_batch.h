@@ -58,6 +58,11 @@ struct eph_craft_batch {
 namespace eph {
 bool craft_wave_form(long long n_craft);                  // craft.hip: one wave per craft (few spacecraft) or one thread
 int craft_events_search(eph_craft_batch *b, hipStream_t s);   // craft_events.hip: the event search on the steps a sweep just took
+// craft.hip: the creation rule's deal of a thread-per-craft batch to the lanes from its current time and state (perm, slot_of, h_slot;
+// nothing when the gate -- EPH_CRAFT_SORT, n >= 128, not the wave form -- says no deal). knot0_to_lanes: creation's tail, knot 0
+// (uploaded in craft order) moves to the lanes' columns; eph_craft_batch_gather moves whole columns itself. The caller holds the
+// table's read lock and has the batch's device current; the batch's stream is idle on return.
+int craft_sort(eph_craft_batch *b, bool knot0_to_lanes);
 // craft.hip: Timeline::new (spacecraft.rs:129-152) of one craft's burns, appended to `segs` (create, restart, divergence time)
 void timeline_new(long long nburns, const double *burn_start, const double *burn_end, const double *burn_acc, const int32_t *burn_ref,
                   std::vector<SegmentDev> &segs);

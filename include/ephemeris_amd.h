@@ -412,6 +412,37 @@ int32_t eph_craft_batch_events(eph_craft_batch *b, int64_t craft, double *tr_tim
  * same (live) eph_ephemeris, which must outlive both: a clone taken before an eph_ephemeris_append resumes against the
  * extended table. */
 int32_t eph_craft_batch_clone(eph_craft_batch *b, eph_craft_batch **out);
+/* Regroup living spacecraft: a NEW batch whose craft i is craft craft_of[i] of sources[source_of[i]], as it is now. Removing,
+ * adding (gather the fleet with a one-ship batch), splitting, merging, permuting and duplicating a ship (the app's snapshot of one
+ * ship) are all this call; eph_craft_batch_clone is its identity case. The app's fleet changes while it flies: ships are spawned
+ * (ephemeris_explorer/src/ui/windows/spawner.rs:136,367,408), loaded and deleted (ui/windows/body.rs:184-207), and each owns its
+ * propagator (prediction.rs).
+ *   source_of == NULL: every craft comes from sources[0] (n_sources must be 1).
+ *   craft_of == NULL:  the concatenation of all sources in order (source_of must be NULL too, n_out = the sum of their sizes).
+ * A (source, craft) pair may occur more than once; n_out == 0 gives an empty batch with the sources' configuration. The sources'
+ * streams are synchronised first (as eph_craft_batch_clone does); the sources are not changed and stay usable and independent of
+ * `out`, which refers to the same (live) eph_ephemeris.
+ * Contract: any sequence of library calls applied to `out` gives for craft i exactly what the same calls give for craft
+ * craft_of[i] in its source batch, bit for bit, in everything this header lets a caller read. Carried per craft: time, state,
+ * next_h, the FSAL registers k[0] / k[S-1] (the stale first stage after an EvalFailed included, see eph_craft_batch_retry_failed),
+ * the last knot's epoch, the attempt counter n, the step counters, the current timeline segment, status, the creation epoch, the
+ * knots 0 .. nknots - 1, the craft's Timeline (eph_craft_batch_restart of `out` diverges from it), and with events on the search
+ * position, the counts, the event status and the used part of the transition and apsis lists. Slab entries at or beyond a craft's
+ * counts stay unspecified. Which lane runs a craft never shows in a result: `out` is dealt to the lanes as a batch created from
+ * these craft would be (the survivors of a sparse selection are packed into full waves of similar craft).
+ * Depths: `out` gets the largest max_knots of the sources and, with events on, the largest max_transitions and max_apsides; a craft
+ * from a shallower source has more room from now on. EPH_KNOTS_FULL is re-derived by every sweep from nknots >= max_knots, so a
+ * craft that was full in a shallower source continues in `out` at the next propagate (its status reads EPH_KNOTS_FULL until then);
+ * EPH_EVENTS_FULL is a sticky flag and stays until eph_craft_batch_reset_events. The contract above therefore holds whenever the
+ * source's own slabs would not have filled earlier.
+ * The sources must agree; refused with EPH_ERR_BAD_ARGUMENT, eph_last_error naming the first disagreement, and *out = NULL unless all
+ * share: the eph_ephemeris handle (and with it the device), the method, eph_adaptive_params bytewise, the evaluation order of the
+ * point-mass term, the body order, a pending eph_craft_batch_retry_failed (batch-wide; carried to `out`), events on or off and,
+ * with events on, bytewise-equal soi radii. Refused the same way: n_sources < 1, a NULL source or NULL `out`, n_out < 0, an index
+ * outside its source, any other NULL combination. EPH_ERR_NO_DEVICE as elsewhere. On any error, a failed allocation included, the
+ * sources are exactly as before and *out is NULL. */
+int32_t eph_craft_batch_gather(int32_t n_sources, eph_craft_batch *const *sources, int64_t n_out,
+                               const int32_t *source_of, const int64_t *craft_of, eph_craft_batch **out);
 /* Bulk read of the knot slabs for sweeps (one copy instead of one strided gather per craft): knots first_knot ..
  * first_knot + n_knots - 1 of EVERY craft in the device layout, knot_t[k][craft] and knot_y[k][d][craft] (d = x, y, z,
  * vx, vy, vz); entries at or beyond a craft's nknots are unspecified. Either pointer may be NULL. (A heterogeneous batch

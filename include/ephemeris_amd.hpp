@@ -707,6 +707,22 @@ public:
         detail::check(eph_craft_batch_clone(h_, &c), "eph_craft_batch_clone");
         return SpacecraftBatch(c, n_);
     }
+    // Regrouping living ships (eph_craft_batch_gather): the new batch's craft i is craft craft_of[i] of sources[source_of[i]], as it is
+    // now, bit for bit -- the app's spawn, delete and per-ship snapshot on a fleet that shares one batch. The sources are unchanged.
+    static SpacecraftBatch gather(const std::vector<const SpacecraftBatch *> &sources, const std::vector<int32_t> &source_of,
+                                  const std::vector<int64_t> &craft_of) {
+        if (source_of.size() != craft_of.size()) throw std::invalid_argument("SpacecraftBatch::gather: one source per craft");
+        return gathered(sources, static_cast<int64_t>(craft_of.size()), index_array(source_of), index_array(craft_of));
+    }
+    static SpacecraftBatch gather(const std::vector<const SpacecraftBatch *> &sources, const std::vector<int64_t> &craft_of) {   // of ONE source
+        return gathered(sources, static_cast<int64_t>(craft_of.size()), nullptr, index_array(craft_of));
+    }
+    SpacecraftBatch select(const std::vector<int64_t> &craft) const { return gather({this}, craft); }         // in that order; an index may repeat
+    static SpacecraftBatch concat(const std::vector<const SpacecraftBatch *> &batches) {                       // all craft, in order
+        int64_t n = 0;
+        for (const SpacecraftBatch *s : batches) n += s ? s->n_ : 0;
+        return gathered(batches, n, nullptr, nullptr);
+    }
     SpacecraftBatch(SpacecraftBatch &&o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_) {}
     SpacecraftBatch &operator=(SpacecraftBatch &&o) noexcept {
         if (this != &o) { if (h_) eph_craft_batch_destroy(h_); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; }
@@ -716,6 +732,21 @@ public:
 
 private:
     SpacecraftBatch(eph_craft_batch *h, int64_t n) : h_(h), n_(n) {}
+    // In the C call a NULL index array means "all of it" (craft_of: the concatenation; source_of: sources[0]), and an empty vector's
+    // data() may be NULL: a selection of no craft passes this one dummy instead, which is never read.
+    template <typename T>
+    static const T *index_array(const std::vector<T> &v) {
+        static const T none{};
+        return v.empty() ? &none : v.data();
+    }
+    static SpacecraftBatch gathered(const std::vector<const SpacecraftBatch *> &sources, int64_t n_out, const int32_t *source_of,
+                                    const int64_t *craft_of) {
+        std::vector<eph_craft_batch *> hs;
+        for (const SpacecraftBatch *s : sources) hs.push_back(s ? s->h_ : nullptr);
+        eph_craft_batch *c = nullptr;
+        detail::check(eph_craft_batch_gather(static_cast<int32_t>(hs.size()), hs.data(), n_out, source_of, craft_of, &c), "eph_craft_batch_gather");
+        return SpacecraftBatch(c, n_out);
+    }
     eph_craft_batch *h_ = nullptr;
     int64_t n_ = 0;
 };
