@@ -2,44 +2,36 @@
 // dominant kernel of the massive-body path (one launch per integrator step for N > 512 targets; dispatch.cpp chooses).
 // Compiled once per evaluation order of the point-mass term (pair_ns.h), -ffp-contract=off (parity is bit for bit).
 //
-// Measured on MI355X (scripts/ubench/lat.hip): a dependent v_add_f64 issues every 8.4 cycles from one wave, v_rsq_f64 /
-// v_rcp_f64 cost ~17 issue cycles each, other f64 ops ~4.1-5. In the one-wave-per-block form (step_wave.hip) every wave pays
-// the 64 ordered adds and 32 ds_read_b128 of a tile's ordered sums for only 3 * BPW useful lanes. Here ONE wave of a workgroup
-// (the chain wave) carries the ordered sums of all the workgroup's bodies -- 3 * WB of its 64 lanes -- while pair waves (lane =
-// source) produce the contribution tiles through LDS. The shipped arrangement ("layout 5", round 2; history and the six retired
-// layouts: profiles/r02_step_kernel_evidence.md, profiles/r03_step_kernel_evidence.md; the retired code: step_wg_retired.inc,
-// compiled only with -DEPH_EXPERIMENTS):
-//   * 16 bodies per workgroup, TWELVE waves, three per SIMD (waves go to the four SIMDs round-robin: wave k -> SIMD k % 4),
-//     <= 168 VGPRs each: on SIMDs 1-3 three pair waves that carry the SAME five bodies (1-5, 6-10, 11-15) and take one source
-//     tile each of a three-tile phase (round 7: pair work dealt by source tile); SIMD 0 a one-body pair wave (body 0, all
-//     three tiles), the chain wave (at raised issue priority) and the tail wave;
-//   * round 8: 14 / 14 / 14 / 6 units (body, source tile) per three-tile phase instead of 15 / 15 / 15 / 3. The pair SIMDs are
-//     issue-bound (about 195 issue cycles per interaction); the wave of each pair SIMD that takes the phase's third tile carries
-//     four bodies, and the three shed units (bodies 5, 10, 15 against that tile) are one block of the tail wave, which only met
-//     barriers in the tile loop. 31.18-31.36 against 33.25-33.37 us per step at N = 4096, same box, alternating, 3 x 5 blocks of
-//     500 steps; pair side alone 28.4 (was 31.1), chain side alone 25.1, SIMD 0 alone (its six units and the chain,
-//     -DEPH_WG_SIDE=3) 28.6: SIMD 0 is now as long as the pair SIMDs, so there is nothing left to move that way
-//     (profiles/r08_step_kernel_evidence.md);
-//   * ONE s_barrier per 192 sources (three 64-source tiles; the first two tiles go singly so the chain wave starts early): 23
-//     barriers for the 64 tiles of N = 4096. Six 25 KB LDS tile buffers as two sets of three: the pair waves write one phase
-//     while the chain wave sums the one before. Rounds 2-6 had one barrier per 128 sources (three sets of two buffers, pair
-//     waves of 2 / 2 / 1 bodies against two tiles, 34 barriers): 36.02-36.09 us per step at N = 4096 against 33.16-33.31 for this
-//     form, same box, alternating, 3 x 5 blocks of 500 steps each (profiles/r07_step_kernel_evidence.md); pair side alone
-//     31.1 (was 34.4), chain side alone 25.35 (was 26.55). The dealing WITHOUT the cadence (128-source schedule, two five-body
-//     waves per SIMD and one idle) was 36.40-36.48 against the parent's 35.98-36.11: the gain is the barriers, not the equal-shaped waves
-//     (scripts/experiments/wg_deal128.patch). Keeping a phase's results in registers across the barrier and issuing the ds_writes
-//     at the head of the NEXT phase (nothing drains before the barrier; the chain wave one phase further behind) was built
-//     and measured as well: bit-identical and 1.4 us slower (35.53-35.63 against 34.15-34.25 for the same build without it);
-//   * round 9: the same deferral for the producers of the THIRD tile of a phase only (the rank-2 waves, wave 8's block, the one-body
-//     wave's third interaction: 4 of the 10 write bursts): 29.84-30.10 against 31.22-31.36 us per step at N = 4096, same box,
-//     alternating, 3 x 5 blocks of 500 steps; the schedule and its buffer lifetimes are stated above phase_start. Different
-//     s_setprio levels for the three pair waves of a SIMD (2 / 1 / 0 by rank, and the reverse) on top of it: 33.39-33.57 and
-//     32.98-33.09, three us SLOWER (scripts/experiments/wg_rank_prio.patch; profiles/r09_step_kernel_evidence.md);
-//   * the tail wave (k_lm_step_wg) loads the 2 L history values while the others work, receives the new acceleration through
-//     LDS and does Cowell's velocity, the solout sample and the predictor;
-//   * 8- and 4-body workgroups for target counts that would leave CUs without a 16-body workgroup (<= 2048 / <= 1024 targets): the
-//     8-body one with SIX waves (four pair waves of two bodies, chain, tail; round 5 -- the twelve-wave form with one body per pair
-//     wave stays selectable, EPH_WG_BODIES=8), the 4-body form with one body per pair wave and TWO chain waves on alternate tiles.
+// WHAT IT DOES. The acceleration of a body is the sum over all sources in the reference's order, so the adds of one body are one
+// dependent chain (a dependent v_add_f64 issues every 8.4 cycles from one wave, v_rsq_f64 / v_rcp_f64 cost ~17 issue cycles, other
+// f64 ops ~4.1-5: scripts/ubench/lat.hip). ONE wave of a workgroup, the chain wave, carries those chains for all the workgroup's
+// bodies -- 3 * WB of its 64 lanes -- and reads the contributions from LDS; the pair waves (lane = source) compute them, 64 sources
+// (a tile) at a time, and write them there as rows [3 * body + component][source].
+//
+// THE 16-BODY WORKGROUP (N > 2048 targets), twelve waves, wave k on SIMD k % 4, three per SIMD, <= 168 VGPRs each:
+//   * SIMD 0: wave 0 the one-body pair wave (body 0), wave 4 the chain wave at raised issue priority, wave 8 the tail wave;
+//     SIMDs 1-3: three pair waves each for the bodies 1-5, 6-10, 11-15 (wg_force, 16-body overload).
+//   * Tiles go in PHASES: tiles 0 and 1 singly (the chain wave starts early), then three tiles per phase, one s_barrier per phase:
+//     23 barriers for the 64 tiles of N = 4096. Of the three pair waves of a SIMD each takes ONE tile of the phase (its rank).
+//   * The deal is 14 / 14 / 14 / 6 units (body, source tile) per phase: ranks 0 and 1 carry the five bodies of their SIMD, rank 2
+//     (the third tile) four; the fifth bodies (5, 10, 15) against the third tile are one block of the tail wave on SIMD 0, beside
+//     the one-body wave's three units (wg_pair_wave_deal, wg_tail_wave_phases, wg_pair_wave_solo).
+//   * Six 25 KB LDS tile buffers, tile t in buffer t % 6: the pair waves write one phase while the chain wave sums the one before.
+//     The THIRD tile of a phase is written one interval late by every one of its producers, out of registers, at the head of their
+//     next block (orders 0, 4 and 5); the schedule and the buffer lifetimes are stated above phase_start.
+//   * k_lm_step_wg: the tail wave loads the 2 L history values while the others work, receives the new acceleration through LDS
+//     and does Cowell's velocity, the solout sample and the predictor.
+// THE SMALL FORMS, for target counts that would leave CUs without a 16-body workgroup (wg_force, the other overload):
+//   * 8 bodies, SIX waves (`DUO`; 1024 < targets <= 2048): four pair waves of two bodies, chain, tail; big tiles of two tiles per
+//     barrier (big_start). The twelve-wave 8-body form, one body per pair wave, stays selectable (EPH_WG_BODIES=8).
+//   * 4 bodies (<= 1024 targets): one body per pair wave, one barrier per tile, TWO chain waves on alternate tiles (wg_force_split).
+//
+// HISTORY AND EVIDENCE, by round, under profiles/: r02 / r03_step_kernel_evidence.md (the layout and its six retired rivals, the
+// split form), r04 (what the barriers cost, LDS counters instead), r05 (the six-wave form), r07 (one barrier per 192 sources and the
+// deal by source tile: 33.2 against 36.0 us per step at N = 4096), r08 (14 / 14 / 14 / 6: 31.3 against 33.3), r09 (the late third
+// tile: 29.9 against 31.3), step_wg_refactor.md (this file's present shape, same device code). Variants that were measured and
+// rejected are patches under scripts/experiments/ (README.md there); a measured negative result that guards one line stands beside
+// that line.
 #include <algorithm>
 #include <type_traits>
 #include <utility>
@@ -64,30 +56,6 @@
 #define EPH_WG_ABLATE 0
 #endif
 #define WG_LOOP_BARRIER() do { if constexpr (!(EPH_WG_ABLATE & 2)) __syncthreads(); } while (0)
-// Where a wave that holds a phase's third tile over the barrier (phase_start below) issues the late ds_writes inside the next
-// interval's block (wg_pair_block): 0 = at the head, before the pre-stage; 1 = behind the range test, before the staged arithmetic
-// (the compiler merges the two sides of the test and spreads the stores over the pre-stage); 2 = between two runs of the staged
-// arithmetic (half the block's interactions each); 3 = behind the arithmetic. A constant in the product;
-// -DEPH_EXPERIMENTS=1 -DEPH_WG_LATE_AT=k for the tuning builds. Measured at N = 4096, us per step, parent 31.14-31.26:
-// 0: 29.79-29.98, 1: 33.30-33.45, 2: 32.42-32.50, 3: 31.67-31.86 (profiles/r09_step_kernel_evidence.md). The head it is: behind the
-// barrier the LDS store path has nothing else to do (the chain wave opens its interval with reads), and a third of the producers
-// is not the burst of all ten that round 7 put there.
-#if !EPH_EXPERIMENTS || !defined(EPH_WG_LATE_AT)
-#undef EPH_WG_LATE_AT
-#define EPH_WG_LATE_AT 0
-#endif
-// MEASURED, NOT THE DEFAULT (-DEPH_EXPERIMENTS=1 -DEPH_WG_DIAG_PATCH=1): the pair waves that meet the workgroup's own tile take the
-// IEEE form for it (n2 = 0 on the self lanes fails the range test of the whole wave): about 1.8 x the instructions for that wave in
-// one phase. With the switch the self lanes get in-range operands instead (n2 = 1; their contribution is read and discarded by
-// chain_masked) and the wave stays on the seeded sequences. Round 2 measured the idea on the barrier-per-tile kernel (40.1 vs
-// 40.0 us, no gain); round 7 on the 192-source schedule, five bodies on the wave that meets the own tile: bit-identical
-// (tests/test_gpu_step_phases.py) and SLOWER, 35.19-35.30 against 33.53-33.64 us per step at N = 4096 -- the lane compares and
-// selects sit in front of every tile of every wave, the IEEE form in one phase of 23 (profiles/r07_step_kernel_evidence.md).
-#if EPH_EXPERIMENTS && defined(EPH_WG_DIAG_PATCH)
-#define EPH_WG_DIAG_PATCH_ON 1
-#else
-#define EPH_WG_DIAG_PATCH_ON 0
-#endif
 
 // The SIX-WAVE 8-body workgroup (round 5; `DUO` in the templates below, wb code 9 in the launcher): four pair waves x two bodies, a
 // chain wave, a tail wave, 76 KB of LDS. Built to put TWO workgroups on a CU at N = 4096 so that one's barrier drain is covered by
@@ -106,15 +74,38 @@ constexpr int kDuoTailWave = 5;
 constexpr int kWgChainWave = 4;                      // the chain wave (wave 4: lands on SIMD 0)
 constexpr int kWgTailWave = 8;                       // the step kernel's tail wave (SIMD 0 too)
 constexpr int kWgThreads = 64 * 12;
-constexpr int kWgTileBufs = 6;                       // LDS tile buffers of the barrier-per-128-sources schedule
+constexpr int kWgTileBufs = 6;                       // LDS tile buffers of the phase and big-tile schedules (tile t in buffer t % 6)
 constexpr int kWgSplitBufs = 3;                      // ... of the barrier-per-64 schedule (4-body workgroups, two chain waves)
+
+// a pair wave's own bodies: NB of them from body `first` on, BS apart (bodies beyond n are clamped copies of body n - 1). Wave-uniform,
+// and the compiler keeps them in scalar registers; pinned into vector registers instead: 34.20-34.34 against 33.16-33.31 us per step
+// at N = 4096, alternating on one box
+template <int NB, int BS = 1, typename PosPtr>
+__device__ __forceinline__ void wg_load_own(PosPtr pos, int n, int first, double (&xi)[NB], double (&yi)[NB], double (&zi)[NB]) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int ii = min(first + BS * b, n - 1);
+        xi[b] = pos[ii].x;
+        yi[b] = pos[ii].y;
+        zi[b] = pos[ii].z;
+    }
+}
+// lane = source: the lane's body of source tile t (past the last tile: the last tile again; past body n - 1: that body)
+template <typename PosPtr>
+__device__ __forceinline__ Body4 load_src(PosPtr pos, int n, int tiles, int lane, int t) {
+    const int j = min(t, tiles - 1) * kTile + lane;
+    return pos[j < n ? j : n - 1];
+}
 
 // pair wave: NB bodies (local indices b0..) against the 64 sources in pj -> rows of `tile`
 template <int NB>
 __device__ __forceinline__ void wg_pair_tile(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
                                              const Body4 &pj, bool ieee, double *tile, int b0, int lane) {
-    // (the workgroup's own tile goes to the IEEE form as a whole -- n2 = 0 on the self lanes; giving those lanes a
-    // harmless in-range operand instead, since the chain wave never reads them, was measured: no gain, 40.1 vs 40.0 us)
+    // (the workgroup's own tile goes to the IEEE form as a whole -- n2 = 0 on the self lanes fails the range test of the wave.
+    // Giving those lanes a harmless in-range operand instead, since the chain wave discards what they produce, was measured twice:
+    // no gain in round 2, 40.1 vs 40.0 us; SLOWER on the phase schedule, 35.19-35.30 against 33.53-33.64 us per step at N = 4096 --
+    // the lane compares sit in front of every tile of every wave, the IEEE form in one phase of 23:
+    // scripts/experiments/wg_diag_patch.patch)
     PairPre pre[NB];
     unsigned worst = ieee ? kRangeSpan : mu_key(pj.mu), low = ~0u;   // max of the range keys: one add + one max per body
 #pragma unroll
@@ -144,28 +135,18 @@ __device__ __forceinline__ void wg_pair_tile(const double (&xi)[NB], const doubl
 template <int NB, typename PosPtr>
 __device__ __forceinline__ void wg_pair_wave(PosPtr pos, int n, int i0, int b0, double *C, int lane, int tiles, int tdiag, int wbuf) {
     double xi[NB], yi[NB], zi[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int ii = min(i0 + b0 + b, n - 1);
-        xi[b] = pos[ii].x;
-        yi[b] = pos[ii].y;
-        zi[b] = pos[ii].z;
-    }
-    auto load_src = [&](int t) -> Body4 {
-        const int j = min(t, tiles - 1) * kTile + lane;
-        return pos[j < n ? j : n - 1];
-    };
-    Body4 pj = load_src(0);
-    Body4 pjn = load_src(1);
+    wg_load_own<NB>(pos, n, i0 + b0, xi, yi, zi);
+    Body4 pj = load_src(pos, n, tiles, lane, 0);
+    Body4 pjn = load_src(pos, n, tiles, lane, 1);
     wg_pair_tile<NB>(xi, yi, zi, pj, tdiag == 0, C, b0, lane);
     pj = pjn;
-    pjn = load_src(2);
+    pjn = load_src(pos, n, tiles, lane, 2);
     if (tiles > 1) wg_pair_tile<NB>(xi, yi, zi, pj, tdiag == 1, C + wbuf, b0, lane);
     __syncthreads();
     for (int t = 0; t < tiles; ++t) {
         if (t + 2 < tiles) {
             pj = pjn;
-            pjn = load_src(t + 3);
+            pjn = load_src(pos, n, tiles, lane, t + 3);
             wg_pair_tile<NB>(xi, yi, zi, pj, tdiag == t + 2, C + ((t + 2) % kWgSplitBufs) * wbuf, b0, lane);
         }
         __syncthreads();
@@ -176,17 +157,13 @@ __device__ __forceinline__ void wg_pair_wave(PosPtr pos, int n, int i0, int b0, 
 template <int NB>
 __device__ __forceinline__ void wg_pair_tile2(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
                                               const Body4 &pa, const Body4 &pb, bool ieee, double *tile_a, double *tile_b,
-                                              int b0, int lane, int self_a = -64, int self_b = -64) {
+                                              int b0, int lane) {
     PairPre pre[2 * NB];
     unsigned worst = ieee ? kRangeSpan : max(mu_key(pa.mu), mu_key(pb.mu)), low = ~0u;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         pre[b] = pair_pre(xi[b], yi[b], zi[b], pa);
         pre[NB + b] = pair_pre(xi[b], yi[b], zi[b], pb);
-        if constexpr (EPH_WG_DIAG_PATCH_ON) {          // self_x: the lane that holds body b0 as a source of tile x (far off: none)
-            if (lane == self_a + b) { pre[b].n2 = 1.0; pre[b].lo = 0x3ff00000u; }
-            if (lane == self_b + b) { pre[NB + b].n2 = 1.0; pre[NB + b].lo = 0x3ff00000u; }
-        }
         worst = max(worst, max(range_key(pre[b].n2), range_key(pre[NB + b].n2)));
         low = min(low, min(pre[b].lo, pre[NB + b].lo));
     }
@@ -245,6 +222,7 @@ __device__ __forceinline__ int big_count(int tiles) { return tiles <= 2 ? tiles 
 template <int NB, typename PosPtr>
 __device__ __forceinline__ void wg_pair_wave_big(PosPtr pos, int n, int i0, int b0, double *C, int lane, int tiles, int tdiag, int wbuf) {
     double xi[NB], yi[NB], zi[NB];
+    // (wg_load_own written out: through the helper the six-wave step kernels of order 4 come out with other registers)
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const int ii = min(i0 + b0 + b, n - 1);
@@ -256,33 +234,23 @@ __device__ __forceinline__ void wg_pair_wave_big(PosPtr pos, int n, int i0, int 
     // offset -- ten VALU fewer per interval -- 36.7 against 36.2 us; two intervals per trip with the prefetched register sets
     // trading places instead of being copied 38.7; own bodies' positions through scalar loads 36.4; the first source tiles requested
     // before the own positions 36.3; nontemporal stores of the tail wave 36.1 (nothing): profiles/r04_step_kernel_evidence.md.)
-    auto load_src = [&](int t) -> Body4 {
-        const int j = min(t, tiles - 1) * kTile + lane;
-        return pos[j < n ? j : n - 1];
-    };
     auto produce = [&](int K, const Body4 &pa, const Body4 &pb) {          // big tile K
         const int t = big_start(K);
         if (t >= tiles || EPH_WG_SIDE == 2) return;
         double *ta = C + (t % kWgTileBufs) * wbuf, *tb = C + ((t + 1) % kWgTileBufs) * wbuf;
-        if constexpr (EPH_WG_DIAG_PATCH_ON) {
-            if (K >= 2 && t + 1 < tiles) {
-                const int own = i0 + b0;                // (bodies beyond n are clamped copies of body n - 1: never diagonal lanes)
-                wg_pair_tile2<NB>(xi, yi, zi, pa, pb, false, ta, tb, b0, lane, tdiag == t ? own - t * kTile : -64,
-                                  tdiag == t + 1 ? own - (t + 1) * kTile : -64);
-                return;
-            }
-        }
         if (K >= 2 && t + 1 < tiles) wg_pair_tile2<NB>(xi, yi, zi, pa, pb, tdiag == t || tdiag == t + 1, ta, tb, b0, lane);
         else wg_pair_tile<NB>(xi, yi, zi, pa, tdiag == t, ta, b0, lane);
     };
     const int TB = big_count(tiles);
-    Body4 pa = load_src(0), pb = load_src(1), na = load_src(2), nb = load_src(3);
+    Body4 pa = load_src(pos, n, tiles, lane, 0), pb = load_src(pos, n, tiles, lane, 1);
+    Body4 na = load_src(pos, n, tiles, lane, 2), nb = load_src(pos, n, tiles, lane, 3);
     produce(0, pa, pa);
     produce(1, pb, pb);
     __syncthreads();
     for (int K = 0; K < TB; ++K) {
         pa = na; pb = nb;
-        na = load_src(big_start(K + 3)); nb = load_src(big_start(K + 3) + 1);
+        na = load_src(pos, n, tiles, lane, big_start(K + 3));
+        nb = load_src(pos, n, tiles, lane, big_start(K + 3) + 1);
         produce(K + 2, pa, pb);
         WG_LOOP_BARRIER();
     }
@@ -314,6 +282,9 @@ __device__ __forceinline__ void wg_idle_wave(int tiles) {
 // is late: the one-body wave writing c(P) early would overwrite c(P - 2) while the chain wave reads it. In the interval of the
 // first c there is nothing held yet; the block then stores zeros to that c's own buffer, idle until the real values follow one
 // interval later (the block stays free of a branch around the stores).
+// (The same deferral for EVERY tile of a phase, all ten write bursts at the head of the next phase and the chain wave one phase
+// further behind, was round 7: bit-identical and 1.4 us slower, 35.53-35.63 against 34.15-34.25. Different s_setprio levels for the
+// three pair waves of a SIMD on top of the late third tile: three us slower, scripts/experiments/wg_rank_prio.patch.)
 // Orders 0, 4 and 5 only: with the same schedule orders 1, 2, 3 and 6 LOSE about 2.2 us per step (35.36 / 35.36 / 39.76 / 38.64
 // against 33.12 / 33.49 / 37.56 / 36.07 at N = 4096, the stores at the head in the generated code of all of them) and keep the
 // schedule of round 8, third tiles written before their phase's barrier (profiles/r09_step_kernel_evidence.md section 6).
@@ -329,10 +300,8 @@ __device__ __forceinline__ int chain_first(int I) { return kWgLateThird ? (I <= 
 
 // the staged term for M = MA + MB interactions in two runs (the division orders 4 and 6 carry six more doubles per interaction
 // through the stages: five at once do not fit 168 VGPRs)
-struct NoHook { __device__ __forceinline__ void operator()() const {} };
-template <int MA, int MB, typename Between = NoHook>
-__device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA + MB], const double (&mu)[MA + MB], double (&c)[3 * (MA + MB)],
-                                                         Between between = Between()) {
+template <int MA, int MB>
+__device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA + MB], const double (&mu)[MA + MB], double (&c)[3 * (MA + MB)]) {
     PairPre pa[MA], pb[MB];
     double ma[MA], mb[MB], ca[3 * MA], cb[3 * MB];
 #pragma unroll
@@ -340,7 +309,6 @@ __device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA
 #pragma unroll
     for (int k = 0; k < MB; ++k) { pb[k] = pre[MA + k]; mb[k] = mu[MA + k]; }
     pair_finish_staged<MA>(pa, ma, ca);
-    between();
     pair_finish_staged<MB>(pb, mb, cb);
 #pragma unroll
     for (int k = 0; k < 3 * MA; ++k) c[k] = ca[k];
@@ -348,24 +316,32 @@ __device__ __forceinline__ void pair_finish_staged_split(const PairPre (&pre)[MA
     for (int k = 0; k < 3 * MB; ++k) c[3 * MA + k] = cb[k];
 }
 
+// the held rows of a third tile (wg_pair_block, LATE) -> their tile buffer: bodies b0, b0 + BS, ..., rows 3 * body + component
+template <int NB, int BS>
+__device__ __forceinline__ void wg_store_held(double *tile, int b0, int lane, const double (&held)[3 * NB]) {
+#pragma unroll
+    for (int q = 0; q < 3 * NB; ++q) {
+        if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(held[q]));
+        else tile[(3 * (b0 + BS * (q / 3)) + q % 3) * kRow + lane] = held[q];
+    }
+}
+
 // NB bodies (local indices b0..) against NT 64-source tiles: NB * NT independent interactions behind ONE range test, the staged
-// arithmetic (pair_finish_staged, pair_term.h), then the write burst. self[s]: EPH_WG_DIAG_PATCH only -- the lane that holds body
-// b0 as a source of tile s (far off: none). BS: the stride of the bodies (local indices b0, b0 + BS, ...; rows 3 * body + component).
+// arithmetic (pair_finish_staged, pair_term.h), then the write burst. BS: the stride of the bodies (local indices b0, b0 + BS, ...;
+// rows 3 * body + component).
 // LATE (the late third tile, phase_start above): the contributions of the LAST tile are not written but left in `held`, and what
-// `held` brought in -- the same rows of the third tile of the phase before -- is written to `held_tile` at EPH_WG_LATE_AT.
+// `held` brought in -- the same rows of the third tile of the phase before -- is written to `held_tile` at the HEAD of the block,
+// before the pre-stage: behind the barrier the LDS store path has nothing else to do (the chain wave opens its interval with reads),
+// and a third of the producers is not the burst of all ten that round 7 put there. Measured at N = 4096, us per step, parent
+// 31.14-31.26: at the head 29.79-29.98; behind the range test 33.30-33.45 (the compiler spreads the stores over the pre-stage);
+// between two runs of the staged arithmetic 32.42-32.50; behind the arithmetic 31.67-31.86 (profiles/r09_step_kernel_evidence.md;
+// the switch: scripts/experiments/wg_late_at.patch).
 template <int NB, int NT, int BS = 1, bool LATE = false>
 __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
                                               const Body4 (&pj)[NT], bool ieee, double *const (&tile)[NT], int b0, int lane,
-                                              const int (&self)[NT], double (&held)[3 * NB], double *held_tile) {
+                                              double (&held)[3 * NB], double *held_tile) {
     constexpr int M = NB * NT;
-    auto write_held = [&]() {
-#pragma unroll
-        for (int q = 0; q < 3 * NB; ++q) {
-            if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(held[q]));
-            else held_tile[(3 * (b0 + BS * (q / 3)) + q % 3) * kRow + lane] = held[q];
-        }
-    };
-    if constexpr (LATE && EPH_WG_LATE_AT == 0) write_held();
+    if constexpr (LATE) wg_store_held<NB, BS>(held_tile, b0, lane, held);
     PairPre pre[M];
     double mus[M];
     unsigned worst = ieee ? kRangeSpan : 0u, low = ~0u;
@@ -377,21 +353,14 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
             const int k = s * NB + b;
             pre[k] = pair_pre(xi[b], yi[b], zi[b], pj[s]);
             mus[k] = pj[s].mu;
-            if constexpr (EPH_WG_DIAG_PATCH_ON) {
-                if (lane == self[s] + BS * b) { pre[k].n2 = 1.0; pre[k].lo = 0x3ff00000u; }
-            }
             worst = max(worst, range_key(pre[k].n2));
             low = min(low, pre[k].lo);
         }
     }
     worst = max(worst, low_key(low));
     double c[3 * M];
-    constexpr bool kLateMid = LATE && kPairStaged && EPH_WG_LATE_AT == 2 && M >= 2;
     if (__builtin_amdgcn_ballot_w64(worst >= kRangeSpan) == 0) {
-        if constexpr (LATE && (EPH_WG_LATE_AT == 1 || (EPH_WG_LATE_AT == 2 && !kLateMid))) write_held();
-        if constexpr (kLateMid) {
-            pair_finish_staged_split<M - M / 2, M / 2>(pre, mus, c, write_held);
-        } else if constexpr (kPairStaged && M == 5 && (kPairVariant == 4 || kPairVariant == 6)) {
+        if constexpr (kPairStaged && M == 5 && (kPairVariant == 4 || kPairVariant == 6)) {
             pair_finish_staged_split<3, 2>(pre, mus, c);
         } else if constexpr (kPairStaged) {
             pair_finish_staged<M>(pre, mus, c);
@@ -400,11 +369,9 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
             for (int k = 0; k < M; ++k) pair_finish<true>(pre[k], mus[k], c[3 * k], c[3 * k + 1], c[3 * k + 2]);
         }
     } else {   // the tile holding the workgroup's own bodies (n2 = 0 on the self lane) or an operand outside the guarded ranges
-        if constexpr (LATE && (EPH_WG_LATE_AT == 1 || EPH_WG_LATE_AT == 2)) write_held();
 #pragma unroll
         for (int k = 0; k < M; ++k) pair_finish<false>(pre[k], mus[k], c[3 * k], c[3 * k + 1], c[3 * k + 2]);
     }
-    if constexpr (LATE && EPH_WG_LATE_AT == 3) write_held();
 #pragma unroll
     for (int s = 0; s < NT - LATE; ++s) {
 #pragma unroll
@@ -420,10 +387,9 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
 }
 template <int NB, int NT, int BS = 1>
 __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const double (&yi)[NB], const double (&zi)[NB],
-                                              const Body4 (&pj)[NT], bool ieee, double *const (&tile)[NT], int b0, int lane,
-                                              const int (&self)[NT]) {
+                                              const Body4 (&pj)[NT], bool ieee, double *const (&tile)[NT], int b0, int lane) {
     double none[3 * NB];
-    wg_pair_block<NB, NT, BS, false>(xi, yi, zi, pj, ieee, tile, b0, lane, self, none, nullptr);
+    wg_pair_block<NB, NT, BS, false>(xi, yi, zi, pj, ieee, tile, b0, lane, none, nullptr);
 }
 
 // A pair wave of SIMDs 1-3: the bodies b0.. of its SIMD group against ONE tile of every phase, the tile given by the wave's rank
@@ -435,19 +401,7 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
 template <int NB, int BS = 1, typename PosPtr>
 __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int b0, int rank, double *C, int lane, int tiles, int tdiag, int wbuf) {
     double xi[NB], yi[NB], zi[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int ii = min(i0 + b0 + BS * b, n - 1);
-        xi[b] = pos[ii].x;
-        yi[b] = pos[ii].y;
-        zi[b] = pos[ii].z;
-    }
-    // (the wave's own positions are wave-uniform and the compiler keeps them in scalar registers; pinned into vector registers
-    // instead: 34.20-34.34 against 33.16-33.31 us per step at N = 4096, alternating on one box)
-    auto load_src = [&](int t) -> Body4 {
-        const int j = min(t, tiles - 1) * kTile + lane;
-        return pos[j < n ? j : n - 1];
-    };
+    wg_load_own<NB, BS>(pos, n, i0 + b0, xi, yi, zi);
     auto tile_of = [&](int P) { return P < 2 ? (rank == 0 ? P : tiles) : phase_start(P) + rank; };   // >= tiles: none
     constexpr bool kOff = EPH_WG_SIDE == 2 || (EPH_WG_SIDE == 3 && BS == 1);
     const int NI = interval_count(tiles);
@@ -457,16 +411,14 @@ __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int
             if (t >= tiles || kOff) return;
             const Body4 src[1] = {pj};
             double *const dst[1] = {C + (t % kWgTileBufs) * wbuf};
-            // (bodies beyond n are clamped copies of body n - 1: never diagonal lanes)
-            const int self[1] = {EPH_WG_DIAG_PATCH_ON && t == tdiag ? i0 + b0 - t * kTile : -64};
-            wg_pair_block<NB, 1, BS>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self);
+            wg_pair_block<NB, 1, BS>(xi, yi, zi, src, t == tdiag, dst, b0, lane);
         };
-        Body4 pj = load_src(tile_of(0)), pjn = load_src(tile_of(1));
+        Body4 pj = load_src(pos, n, tiles, lane, tile_of(0)), pjn = load_src(pos, n, tiles, lane, tile_of(1));
         produce(tile_of(0), pj);
         __syncthreads();
         for (int P = 1; P < NP; ++P) {
             pj = pjn;
-            pjn = load_src(tile_of(P + 1));
+            pjn = load_src(pos, n, tiles, lane, tile_of(P + 1));
             produce(tile_of(P), pj);
             WG_LOOP_BARRIER();
         }
@@ -477,57 +429,38 @@ __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int
 #pragma unroll
         for (int q = 0; q < 3 * NB; ++q) held[q] = 0.0;
         int tprev = tile_of(2);                         // nothing held in the interval of the first c: zeros to its own buffer
-        Body4 pj, pjn = load_src(tile_of(2));
+        Body4 pj, pjn = load_src(pos, n, tiles, lane, tile_of(2));
         __syncthreads();
         for (int I = 1; I < NI; ++I) {
             const int t = I < 2 ? tiles : tile_of(I);
             if (I >= 2) {
                 pj = pjn;
-                pjn = load_src(tile_of(I + 1));
+                pjn = load_src(pos, n, tiles, lane, tile_of(I + 1));
             }
             double *const late = C + (tprev % kWgTileBufs) * wbuf;
             if (kOff) {
             } else if (t < tiles) {
                 const Body4 src[1] = {pj};
                 double *const dst[1] = {nullptr};       // the block's only tile is held
-                const int self[1] = {EPH_WG_DIAG_PATCH_ON && t == tdiag ? i0 + b0 - t * kTile : -64};
-                wg_pair_block<NB, 1, BS, true>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && t == tdiag, dst, b0, lane, self, held, late);
+                wg_pair_block<NB, 1, BS, true>(xi, yi, zi, src, t == tdiag, dst, b0, lane, held, late);
                 tprev = t;
             } else if (tprev < tiles && I > 2) {       // behind the last c: its writes alone
-#pragma unroll
-                for (int q = 0; q < 3 * NB; ++q) {
-                    if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(held[q]));
-                    else late[(3 * (b0 + BS * (q / 3)) + q % 3) * kRow + lane] = held[q];
-                }
+                wg_store_held<NB, BS>(late, b0, lane, held);
                 tprev = tiles;
             }
             WG_LOOP_BARRIER();
         }
     }
 }
-// wave 8 in the tile loop (the tail wave of k_lm_step_wg, between loading its history and the integrator's work; in k_accel_wg its
-// only work): the fifth bodies of the three SIMD groups against the third tile of every three-tile phase, behind one range test and
-// one ballot, through pair_finish_staged<3>. (The same six units per phase on SIMD 0 with the one-body wave carrying all of them and
-// this wave only meeting the barriers -- two waves beside the chain's adds instead of three -- measured 31.41-31.56 against
-// 31.18-31.36 us per step: scripts/experiments/wg_solo6.patch.)
-constexpr int kWgShedFirst = 5, kWgShedStride = 5, kWgShedBodies = 3;
-template <typename PosPtr>
-__device__ __forceinline__ void wg_tail_wave_phases(PosPtr pos, int n, int i0, double *C, int lane, int tiles, int tdiag, int wbuf) {
-    wg_pair_wave_deal<kWgShedBodies, kWgShedStride>(pos, n, i0, kWgShedFirst, 2, C, lane, tiles, tdiag, wbuf);
-}
 // The one-body pair wave of the chain wave's SIMD: body 0 against every tile of the phase (three interactions at once)
 template <typename PosPtr>
 __device__ __forceinline__ void wg_pair_wave_solo(PosPtr pos, int n, int i0, double *C, int lane, int tiles, int tdiag, int wbuf) {
-    const int ii = min(i0, n - 1);
-    const double xi[1] = {pos[ii].x}, yi[1] = {pos[ii].y}, zi[1] = {pos[ii].z};
-    auto load_src = [&](int t) -> Body4 {
-        const int j = min(t, tiles - 1) * kTile + lane;
-        return pos[j < n ? j : n - 1];
-    };
+    double xi[1], yi[1], zi[1];
+    wg_load_own<1>(pos, n, i0, xi, yi, zi);
     auto load_phase = [&](int P, Body4 (&s)[3]) {
         const int t = phase_start(P);
-        s[0] = load_src(t);
-        if (P >= 2) { s[1] = load_src(t + 1); s[2] = load_src(t + 2); }
+        s[0] = load_src(pos, n, tiles, lane, t);
+        if (P >= 2) { s[1] = load_src(pos, n, tiles, lane, t + 1); s[2] = load_src(pos, n, tiles, lane, t + 2); }
     };
     const int NI = interval_count(tiles), NP = kWgLateThird ? phase_count(tiles) : NI;
     // the third interaction of a three-tile phase is held over the barrier like the rank-2 waves' tiles (phase_start above)
@@ -536,11 +469,7 @@ __device__ __forceinline__ void wg_pair_wave_solo(PosPtr pos, int n, int i0, dou
     auto write_held = [&]() {
         if (tprev >= tiles) return;
         double *const late = C + (tprev % kWgTileBufs) * wbuf;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if constexpr (EPH_WG_ABLATE & 1) asm volatile("" ::"v"(held[q]));
-            else late[q * kRow + lane] = held[q];
-        }
+        wg_store_held<1, 1>(late, 0, lane, held);
         tprev = tiles;
     };
     auto produce = [&](int P, const Body4 (&s)[3]) {
@@ -550,21 +479,19 @@ __device__ __forceinline__ void wg_pair_wave_solo(PosPtr pos, int n, int i0, dou
         if (cnt == 3) {
             double *const dst[3] = {C + (t % kWgTileBufs) * wbuf, C + ((t + 1) % kWgTileBufs) * wbuf,
                                     kWgLateThird ? nullptr : C + ((t + 2) % kWgTileBufs) * wbuf};
-            const bool own = tdiag >= t && tdiag < t + 3;
-            int self[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) self[k] = EPH_WG_DIAG_PATCH_ON && tdiag == t + k ? i0 - (t + k) * kTile : -64;
+            // (the upper bound first: stated as one expression the two scalar compares and their s_and come out in another order
+            // than in the code that was measured -- harmless, and no longer `same` for scripts/compare_kernels.py)
+            const bool below = tdiag < t + 3, own = tdiag >= t && below;
             // (nothing held in the interval of the first c: zeros to its own buffer)
             double *const late = C + ((tprev < tiles ? tprev : t + 2) % kWgTileBufs) * wbuf;
-            wg_pair_block<1, 3, 1, kWgLateThird>(xi, yi, zi, s, !EPH_WG_DIAG_PATCH_ON && own, dst, 0, lane, self, held, late);
+            wg_pair_block<1, 3, 1, kWgLateThird>(xi, yi, zi, s, own, dst, 0, lane, held, late);
             if constexpr (kWgLateThird) tprev = t + 2;
         } else {   // the single tiles and a short last phase
             write_held();
             auto one = [&](int k, const Body4 &pj) {
                 const Body4 src[1] = {pj};
                 double *const dst[1] = {C + ((t + k) % kWgTileBufs) * wbuf};
-                const int self[1] = {EPH_WG_DIAG_PATCH_ON && tdiag == t + k ? i0 - (t + k) * kTile : -64};
-                wg_pair_block<1, 1>(xi, yi, zi, src, !EPH_WG_DIAG_PATCH_ON && tdiag == t + k, dst, 0, lane, self);
+                wg_pair_block<1, 1>(xi, yi, zi, src, tdiag == t + k, dst, 0, lane);
             };
             one(0, s[0]);
             if (cnt > 1) one(1, s[1]);
@@ -618,11 +545,9 @@ __device__ __forceinline__ double chain_full_pf(const double *row, const double 
 // pair waves a barrier per tile makes the pair side (one interaction per wave and tile: a bare dependent chain) the
 // slower one. Producing the tiles in pairs in every other interval to get two interleaved interactions back: 10.4 / 13.0 /
 // 18.7 / 23.0, worse still (the reader waits out the double intervals). Default: the 4-body workgroups only.
-// (profiles/r03_step_kernel_evidence.md section 1b; -DEPH_WG_TILE_SPLIT=1 applies it to the 8-body workgroups too, 0 switches it off)
-#ifndef EPH_WG_TILE_SPLIT
-#define EPH_WG_TILE_SPLIT 2
-#endif
-constexpr bool wg_tile_split(int wb) { return EPH_WG_TILE_SPLIT == 1 ? wb < 16 : (EPH_WG_TILE_SPLIT == 2 && wb == 4); }
+// (profiles/r03_step_kernel_evidence.md section 1b; the switch that applied it to the 8-body workgroups or to none:
+// scripts/experiments/wg_tile_split_knob.patch)
+constexpr bool wg_tile_split(int wb) { return wb == 4; }
 constexpr int wg_split_wave_b(int wb) { return wb == 8 ? 11 : 6; }   // an idle wave of another SIMD than the chain wave's
 // body of the one-body pair wave `wave` in the 8- / 4-body workgroups (-1: not a pair wave)
 template <int WB>
@@ -677,11 +602,97 @@ __device__ __forceinline__ double wg_force_split(PosPtr pos, int n, int i0, doub
     return isA ? H[64 + lane] + H[lane] : 0.0;
 }
 
+// wave 8 of the 16-body workgroup in the tile loop (the tail wave of k_lm_step_wg, between loading its history and the integrator's
+// work; in k_accel_wg its only work): the fifth bodies of the three SIMD groups against the third tile of every three-tile phase,
+// behind one range test and one ballot, through pair_finish_staged<3>. (The same six units per phase on SIMD 0 with the one-body
+// wave carrying all of them and this wave only meeting the barriers -- two waves beside the chain's adds instead of three -- measured
+// 31.41-31.56 against 31.18-31.36 us per step: scripts/experiments/wg_solo6.patch.)
+constexpr int kWgShedFirst = 5, kWgShedStride = 5, kWgShedBodies = 3;
+template <typename PosPtr>
+__device__ __forceinline__ void wg_tail_wave_phases(PosPtr pos, int n, int i0, double *C, int lane, int tiles, int tdiag, int wbuf) {
+    wg_pair_wave_deal<kWgShedBodies, kWgShedStride>(pos, n, i0, kWgShedFirst, 2, C, lane, tiles, tdiag, wbuf);
+}
+
+// ---- wg_force<WB, DUO>: the force of a workgroup ------------------------------------------------------------------------------------
 // Returns on chain-wave lane ch < 3 * WB: component ch % 3 of body i0 + ch / 3 (init + the reference-order sum over the other
-// bodies). Every thread of the workgroup must call it.
-template <int WB = kWgBodies, bool DUO = false, typename PosPtr>
+// bodies). Every thread of the workgroup must call it. TWO functions of that name, one per design: the 16-body phase schedule and
+// the big-tile / split schedules of the 8- and 4-body workgroups; they share the opening lines and nothing else. (Two overloads and
+// not two functions behind a forwarding wg_force: through one more level of inlining the optimiser makes other code of the 8-body
+// kernels -- 3168 instead of 3376 lines for k_accel_wg<8>, order 0 -- and nobody has measured that code:
+// profiles/step_wg_refactor.md.) The chain wave's dependent adds issue ahead of the pair wave of its SIMD (s_setprio; the same
+// library with and without, alternating on one box: 36.3 against 36.8 us per step at N = 4096 on two boxes of the pool, 36.2 either
+// way on a third; nothing at the chain-bound sizes).
+
+// The 16-body workgroup. Roles of the twelve waves (wave k runs on SIMD k % 4, so waves k and k + 4 share a SIMD whatever the start
+// of the hardware's cyclic order): wave id = 1, 2, 3 (mod 4) are the pair waves of SIMD group id % 4 -- bodies 1-5, 6-10, 11-15 -- and
+// take the tile of the phase given by their rank id >> 2 (rank 2: the first four bodies only); wave 0 is the one-body pair wave
+// (body 0) beside the chain wave (4) and the tail wave (8: bodies 5, 10, 15 against the third tile). TWO copies of the pair loop of
+// SIMDs 1-3, five bodies and four, the first body and the rank run-time scalars (inlining the loop once per role measured 0.15 us
+// slower in round 4 and is 40 KB more code per evaluation order).
+template <int WB = kWgBodies, bool DUO = false, typename PosPtr, std::enable_if_t<WB == kWgBodies && !DUO, int> = 0>
 __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double init, double *C, int tid) {
     constexpr int kRows = 3 * WB, kBuf = kRows * kRow;   // chains of the chain wave, doubles per LDS tile buffer
+    const int lane = tid & 63, wave = tid >> 6;
+    const int tiles = (n + kTile - 1) / kTile;
+    const int tdiag = i0 / kTile;
+    const int w = __builtin_amdgcn_readfirstlane(wave);
+    if (w == 0) { wg_pair_wave_solo(pos, n, i0, C, lane, tiles, tdiag, kBuf); return 0.0; }
+    if ((w & 3) && w < 8) { wg_pair_wave_deal<5>(pos, n, i0, 5 * (w & 3) - 4, w >> 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
+    if (w & 3) { wg_pair_wave_deal<4>(pos, n, i0, 5 * (w & 3) - 4, 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
+    // (k_lm_step_wg gives this wave the integrator's work around the same call)
+    if (w == kWgTailWave) { wg_tail_wave_phases(pos, n, i0, C, lane, tiles, tdiag, kBuf); return 0.0; }
+    // the chain wave
+    const int ch = lane < kRows ? lane : kRows - 1;
+    const double *row = C + ch * kRow;
+    const int gself = (i0 % kTile) / WB;
+    const int li = (i0 % kTile) + ch / 3;
+    double acc = init, accL = 0.0;
+    double2 q[4][8];
+    __builtin_amdgcn_s_setprio(3);
+    // phases of up to three tiles. Until the barrier that ends phase P every buffer outside P is being written, so a phase
+    // opens with the load of its own first two chunks; inside a phase tile t + 1 is prefetched while tile t is summed.
+    // Behind barrier B_P the complete tiles are c of phase P - 1 and a, b of phase P (phase_start above).
+    const int NP = interval_count(tiles);
+    __syncthreads();                              // B_0: tile 0 ready
+    for (int P = 0; P < NP; ++P) {
+        const int t0 = chain_first(P), nt = min(chain_first(P + 1), tiles) - t0;
+        // three whole tiles of other workgroups' bodies (all but a handful of phases): written out, the prefetch registers
+        // never change hands. (As a loop over the tiles of the phase with the masked form inside, the optimiser left it rolled
+        // and rotated the 128 prefetch registers through moves behind an lgkmcnt(0): 40.3 us per step at N = 4096.)
+        const bool whole = nt == 3 && (tdiag < t0 || tdiag > t0 + 2) && n - (t0 + 2) * kTile >= kTile;
+        if constexpr (EPH_WG_SIDE == 1) {
+        } else if (whole) {
+            const double *r0 = row + (t0 % kWgTileBufs) * kBuf, *r1 = row + ((t0 + 1) % kWgTileBufs) * kBuf;
+            const double *r2 = row + ((t0 + 2) % kWgTileBufs) * kBuf;
+            load_chunk(r0, 0, q[0]);
+            load_chunk(r0, 1, q[1]);
+            acc = chain_full_pf(r0, r1, q, acc);
+            acc = chain_full_pf(r1, r2, q, acc);
+            acc = chain_full_q(r2, q, acc);
+        } else {   // the single tiles, the phase with the workgroup's own tile, a short or ragged last phase
+            for (int t = t0; t < t0 + nt; ++t) {
+                const double *r = row + (t % kWgTileBufs) * kBuf;
+                const int cnt = min(kTile, n - t * kTile);
+                if (t != tdiag && cnt == kTile) { acc = chain_full(r, acc); continue; }
+                // (li made opaque per tile: hoisted out of this loop, the 64 "is this source my own body" lane masks of
+                // chain_masked are 128 scalar registers held across the whole kernel)
+                int lit = li;
+                asm volatile("" : "+v"(lit));
+                chain_masked<WB>(r, cnt, t == tdiag ? gself : -1, lit, acc, accL);
+            }
+        }
+        if (P + 1 < NP) WG_LOOP_BARRIER();        // these tiles consumed, the next ready
+    }
+    return accL + acc;
+}
+
+// The 8- and 4-body workgroups: the 4-body one on the barrier-per-tile schedule with two chain waves (wg_force_split); the 8-body
+// ones on the big-tile schedule (big_start above), with SIX waves (DUO: waves 0-3 two bodies each, 4 the chain, 5 the tail) or
+// TWELVE (one body per pair wave, SIMD 0 left to the chain wave: its cost per tile does not depend on how many of its lanes carry a
+// chain, so with one workgroup per CU the step takes the chain wave's time).
+template <int WB, bool DUO = false, typename PosPtr, std::enable_if_t<WB != kWgBodies || DUO, int> = 0>
+__device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double init, double *C, int tid) {
+    constexpr int kRows = 3 * WB, kBuf = kRows * kRow;
     const int lane = tid & 63, wave = tid >> 6;
     const int tiles = (n + kTile - 1) / kTile;
     const int tdiag = i0 / kTile;
@@ -690,75 +701,21 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
         const int w = __builtin_amdgcn_readfirstlane(wave);
         if (w < 4) { wg_pair_wave_big<2>(pos, n, i0, 2 * w, C, lane, tiles, tdiag, kBuf); return 0.0; }
         if (w == kDuoTailWave) { wg_idle_wave(tiles); return 0.0; }
-    } else
-    if constexpr (wg_tile_split(WB)) return wg_force_split<WB>(pos, n, i0, init, C, tid);
-    else if constexpr (WB != kWgBodies) {
-        // 8 / 4 bodies: one body per pair wave, SIMD 0 left to the chain wave (its cost per tile does not depend on how many of its
-        // lanes carry a chain, so with one workgroup per CU the step takes the chain wave's time)
+    } else if constexpr (wg_tile_split(WB)) {
+        return wg_force_split<WB>(pos, n, i0, init, C, tid);
+    } else {
         const int body = wg_small_body<WB>(wave);
         if (body >= 0) { wg_pair_wave_big<1>(pos, n, i0, body, C, lane, tiles, tdiag, kBuf); return 0.0; }
         if (wave != kWgChainWave) { wg_idle_wave(tiles); return 0.0; }
-    } else {
-        // Roles of the twelve waves (wave k runs on SIMD k % 4, so waves k and k + 4 share a SIMD whatever the start of the
-        // hardware's cyclic order): wave id = 1, 2, 3 (mod 4) are the pair waves of SIMD group id % 4 -- bodies 1-5, 6-10, 11-15 --
-        // and take the tile of the phase given by their rank id >> 2 (rank 2: the first four bodies only); wave 0 is the one-body
-        // pair wave (body 0) beside the chain wave (4) and the tail wave (8: bodies 5, 10, 15 against the third tile). TWO copies of
-        // the pair loop of SIMDs 1-3, five bodies and four, the first body and the rank run-time scalars (inlining the loop once
-        // per role measured 0.15 us slower in round 4 and is 40 KB more code per evaluation order).
-        const int w = __builtin_amdgcn_readfirstlane(wave);
-        if (w == 0) { wg_pair_wave_solo(pos, n, i0, C, lane, tiles, tdiag, kBuf); return 0.0; }
-        if ((w & 3) && w < 8) { wg_pair_wave_deal<5>(pos, n, i0, 5 * (w & 3) - 4, w >> 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
-        if (w & 3) { wg_pair_wave_deal<4>(pos, n, i0, 5 * (w & 3) - 4, 2, C, lane, tiles, tdiag, kBuf); return 0.0; }
-        // (k_lm_step_wg gives this wave the integrator's work around the same call)
-        if (w == kWgTailWave) { wg_tail_wave_phases(pos, n, i0, C, lane, tiles, tdiag, kBuf); return 0.0; }
     }
-    // chain wave. Its dependent adds issue ahead of the one-body pair wave of its SIMD (s_setprio; the same library with and
-    // without, alternating on one box: 36.3 against 36.8 us per step at N = 4096 on two boxes of the pool, 36.2 either way on a
-    // third; nothing at the chain-bound sizes)
+    // the chain wave
     const int ch = lane < kRows ? lane : kRows - 1;
     const double *row = C + ch * kRow;
     const int gself = (i0 % kTile) / WB;
     const int li = (i0 % kTile) + ch / 3;
     double acc = init, accL = 0.0;
     double2 q[4][8];
-    if constexpr (WB == kWgBodies || DUO) __builtin_amdgcn_s_setprio(3);
-    if constexpr (WB == kWgBodies && !DUO) {
-        // phases of up to three tiles. Until the barrier that ends phase P every buffer outside P is being written, so a phase
-        // opens with the load of its own first two chunks; inside a phase tile t + 1 is prefetched while tile t is summed.
-        // Behind barrier B_P the complete tiles are c of phase P - 1 and a, b of phase P (phase_start above).
-        const int NP = interval_count(tiles);
-        __syncthreads();                              // B_0: tile 0 ready
-        for (int P = 0; P < NP; ++P) {
-            const int t0 = chain_first(P), nt = min(chain_first(P + 1), tiles) - t0;
-            // three whole tiles of other workgroups' bodies (all but a handful of phases): written out, the prefetch registers
-            // never change hands. (As a loop over the tiles of the phase with the masked form inside, the optimiser left it rolled
-            // and rotated the 128 prefetch registers through moves behind an lgkmcnt(0): 40.3 us per step at N = 4096.)
-            const bool whole = nt == 3 && (tdiag < t0 || tdiag > t0 + 2) && n - (t0 + 2) * kTile >= kTile;
-            if constexpr (EPH_WG_SIDE == 1) {
-            } else if (whole) {
-                const double *r0 = row + (t0 % kWgTileBufs) * kBuf, *r1 = row + ((t0 + 1) % kWgTileBufs) * kBuf;
-                const double *r2 = row + ((t0 + 2) % kWgTileBufs) * kBuf;
-                load_chunk(r0, 0, q[0]);
-                load_chunk(r0, 1, q[1]);
-                acc = chain_full_pf(r0, r1, q, acc);
-                acc = chain_full_pf(r1, r2, q, acc);
-                acc = chain_full_q(r2, q, acc);
-            } else {   // the single tiles, the phase with the workgroup's own tile, a short or ragged last phase
-                for (int t = t0; t < t0 + nt; ++t) {
-                    const double *r = row + (t % kWgTileBufs) * kBuf;
-                    const int cnt = min(kTile, n - t * kTile);
-                    if (t != tdiag && cnt == kTile) { acc = chain_full(r, acc); continue; }
-                    // (li made opaque per tile: hoisted out of this loop, the 64 "is this source my own body" lane masks of
-                    // chain_masked are 128 scalar registers held across the whole kernel)
-                    int lit = li;
-                    asm volatile("" : "+v"(lit));
-                    chain_masked<WB>(r, cnt, t == tdiag ? gself : -1, lit, acc, accL);
-                }
-            }
-            if (P + 1 < NP) WG_LOOP_BARRIER();        // these tiles consumed, the next ready
-        }
-        return accL + acc;
-    }
+    if constexpr (DUO) __builtin_amdgcn_s_setprio(3);
     const int TB = big_count(tiles);
     __syncthreads();                                  // B_0: tiles 0 and 1 ready
     load_chunk(row, 0, q[0]);
@@ -784,6 +741,7 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
     }
     return accL + acc;
 }
+
 constexpr int wg_lds_doubles(int wb, bool duo = false) { return (wg_tile_split(wb) && !duo ? kWgSplitBufs * 3 * wb * kRow + 128 : kWgTileBufs * 3 * wb * kRow); }
 
 template <int WB = kWgBodies>

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Is the device code of two builds the same code? For every kernel (`.amdhsa_kernel` symbol) of two gfx950 assembly files, or of
-every compiled-once .hip unit of two source trees, compares the kernel descriptor block and the instruction text between the
+every compiled-once .hip unit (or chosen per-order units) of two source trees, compares the kernel descriptor block and the instruction text between the
 symbol's label and its `.Lfunc_end`, with `;` comments dropped and the function index in `.LBB<n>_` labels normalised (it changes
 when a kernel changes file; nothing else should). For a refactor that moves kernels between units or code between functions.
 
     compare_kernels.py [-v] A.s B.s
     compare_kernels.py [-v] TREE_A TREE_B   # compiles SOURCES + HOOKS_SOURCES (*.hip) of each tree's build.py with its FLAGS
+    compare_kernels.py [-v] --pair step_wg.hip [--pair ...] TREE_A TREE_B
+                                            # instead: these units of PAIR_SOURCES, once per evaluation order
+                                            # (-DEPH_PAIR_VARIANT=k, k < N_PAIR_VARIANTS); `--pair all`: every unit of PAIR_SOURCES
 
 Three verdicts per kernel:
     same       descriptor block and instruction text identical
@@ -89,19 +92,28 @@ def explain(a, b):
             print(f"        {'*' if pinned(op) else ' '} {op:<28} {ca[op]:>5} -> {cb[op]:<5}")
 
 
-def tree_kernels(tree, tmp):
-    """{kernel symbol: (unit, descriptor, text)} of the compiled-once .hip units of a source tree"""
+def tree_kernels(tree, tmp, pair=()):
+    """{kernel symbol: (unit, descriptor, text)} of the compiled-once .hip units of a source tree, or, with `pair`, of those
+    per-order units in every evaluation order (their kernels live in one namespace per order, so the symbols stay apart)"""
     b = runpy.run_path(str(Path(tree) / "ephemeris_explorer_amd" / "build.py"), run_name="build")
-    srcs = [s for s in b["SOURCES"] + b["HOOKS_SOURCES"] if s.endswith(".hip")]
+    if pair:
+        srcs = b["PAIR_SOURCES"] if "all" in pair else list(pair)
+        assert set(srcs) <= set(b["PAIR_SOURCES"]), f"--pair takes units of PAIR_SOURCES: {b['PAIR_SOURCES']}"
+        jobs = [(s, k) for s in srcs for k in range(b["N_PAIR_VARIANTS"])]
+    else:
+        jobs = [(s, None) for s in b["SOURCES"] + b["HOOKS_SOURCES"] if s.endswith(".hip")]
 
-    def one(src):
-        out = Path(tmp) / (src[:-4] + ".s")
-        subprocess.run([b["hipcc"](), *b["FLAGS"], "--offload-device-only", "-S", "-x", "hip", str(b["CSRC"] / src), "-o", str(out)],
+    def one(job):
+        src, k = job
+        unit = src if k is None else f"{src} pv{k}"
+        out = Path(tmp) / (unit.replace(".hip", "").replace(" ", ".") + ".s")
+        order = [] if k is None else [f"-DEPH_PAIR_VARIANT={k}"]
+        subprocess.run([b["hipcc"](), *b["FLAGS"], *order, "--offload-device-only", "-S", "-x", "hip", str(b["CSRC"] / src), "-o", str(out)],
                        check=True, stderr=subprocess.DEVNULL)
-        return {k: (src, *v) for k, v in kernels(out).items()}
+        return {name: (unit, *v) for name, v in kernels(out).items()}
     found = {}
     with ThreadPoolExecutor(8) as ex:
-        for part in ex.map(one, srcs):
+        for part in ex.map(one, jobs):
             assert not (set(part) & set(found)), "a kernel defined in two units"
             found.update(part)
     return found
@@ -112,10 +124,10 @@ def demangle(names):
     return {n: re.sub(r"\(.*", "", d).replace("void ", "") for n, d in zip(names, out)}
 
 
-def main(a, b, verbose=False):
+def main(a, b, verbose=False, pair=()):
     if Path(a).is_dir():
         with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-            ka, kb = tree_kernels(a, ta), tree_kernels(b, tb)
+            ka, kb = tree_kernels(a, ta, pair), tree_kernels(b, tb, pair)
     else:
         ka, kb = ({k: (Path(p).name, *v) for k, v in kernels(p).items()} for p in (a, b))
     short = demangle(sorted(set(ka) | set(kb)))
@@ -137,7 +149,11 @@ def main(a, b, verbose=False):
 
 
 if __name__ == "__main__":
-    args = [x for x in sys.argv[1:] if x != "-v"]
+    args, pair = [x for x in sys.argv[1:] if x != "-v"], []
+    while "--pair" in args[:-1]:
+        i = args.index("--pair")
+        pair.append(args[i + 1])
+        del args[i:i + 2]
     if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(main(args[0], args[1], verbose="-v" in sys.argv[1:]))
+    sys.exit(main(args[0], args[1], verbose="-v" in sys.argv[1:], pair=pair))

@@ -5,7 +5,9 @@ tallies a 128-byte request as 64, MI355X_MICROARCH.md; Infinity-Cache hits are c
 What "tile" means here: sources per workgroup barrier (64 or 128), bodies per workgroup (chains per chain wave) in the ordered
 path; sources per slice in the opt-in fast path.
 usage (GPU box, from the repository root): python scripts/tile_sweep3.py [LIB] > gpurun_out/<tag>/tile_sweep.jsonl
-LIB: a library built with -DEPH_EXPERIMENTS (the retired layouts live there); default: the product library (layout 5 only)."""
+LIB: another build of the library to sweep (scripts/build_exp.sh); default: the product library. The source holds the shipped
+layout only; the six retired layouts of rounds 2 and 3 are described in profiles/r02_step_kernel_evidence.md and
+profiles/r03_step_kernel_evidence.md, and measured variants since are patches under scripts/experiments/."""
 import csv, json, os, subprocess, sys, tempfile
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
