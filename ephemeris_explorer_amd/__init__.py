@@ -258,13 +258,21 @@ def rccl_unique_id():
 
 
 class NBodyIntegration(_Handle):
-    """Integration<NBodyProblem<DVec3>, M> (no solout). method: "QuinlanTremaine12", "Stormer13" or an SRKN name."""
+    """Integration<NBodyProblem<DVec3>, M> (no solout). method: "QuinlanTremaine12", "Stormer13" or an SRKN name.
+    compensated=True: the state is the reference's Double<DVec3> (every position and velocity component carries a running
+    error term, ephemeris/tests/solar_system_convergence.rs:12-110) -- the method name goes out as "<method><Double>".
+    state() returns the value parts; `.compensated` says which kind the handle is."""
 
     _DESTROY = "eph_nbody_destroy"
+    DOUBLE_TAG = "<Double>"
+    compensated = False                                    # (a handle adopted from a propagator is a plain one)
 
-    def __init__(self, pos, vel, mu, t0, h, method="QuinlanTremaine12"):
+    def __init__(self, pos, vel, mu, t0, h, method="QuinlanTremaine12", compensated=False):
         pos, vel, mu = _f64(pos), _f64(vel), _f64(mu)
         self.n = len(mu)
+        if compensated and not method.endswith(self.DOUBLE_TAG):
+            method += self.DOUBLE_TAG
+        self.compensated = method.endswith(self.DOUBLE_TAG)
         self._bind(_new_handle("eph_nbody_create", self.n, _p(pos), _p(vel), _p(mu), float(t0), float(h), method.encode()))
 
     def advance(self, n_steps=1):
@@ -1080,3 +1088,6 @@ def apsides_join(lhs, rhs, at):
     _call("eph_apsides_join", len(lt), _p(lt), _p(ld), _p(lk, _i32p), _p(lb, _i32p), len(rt), _p(rt), _p(rd), _p(rk, _i32p),
           _p(rb, _i32p), float(at), cap, _p(t), _p(d), _p(k, _i32p), _p(b, _i32p), C.byref(n))
     return t[:n.value].copy(), d[:n.value].copy(), k[:n.value].copy(), b[:n.value].copy()
+
+
+from .convergence import ConvergenceError, convergence  # noqa: E402,F401  (needs NBodyIntegration above)

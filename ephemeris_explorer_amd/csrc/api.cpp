@@ -5,6 +5,7 @@
 #include <new>
 
 #include "host.h"
+#include "method_name.h"
 
 namespace eph {
 namespace {
@@ -206,6 +207,10 @@ int32_t eph_nbody_set_path(eph_nbody *h, int32_t path) {
     EPH_GUARD_BEGIN
     if (!h || !h->p || path < 0 || path > EPH_PATH_F32_PAIRS) return EPH_ERR_BAD_ARGUMENT;
     if (const int st = h->settle()) return st;         // steps queued through a propagator view ran on the path they were queued for
+    if (h->p->compensated() && path > 2) {
+        set_last_error_text("a <Double> handle runs paths 0, 1 and 2: the workgroup-specialised and the fast kernels carry no error parts");
+        return EPH_ERR_UNSUPPORTED;
+    }
     h->p->set_path(path);
     return EPH_OK;
     EPH_GUARD_END
@@ -243,6 +248,10 @@ int32_t eph_nbody_shard(eph_nbody *h, int32_t rank, int32_t world, const void *r
                         void *ctx) {
     EPH_GUARD_BEGIN
     if (!h || !h->p) return EPH_ERR_BAD_ARGUMENT;
+    if (h->p->compensated()) {                          // before any communicator is made
+        set_last_error_text("a <Double> handle is not sharded: the error parts of the state have no exchange");
+        return EPH_ERR_UNSUPPORTED;
+    }
     if (hipSetDevice(h->p->device()) != hipSuccess) return EPH_ERR_HIP;
     std::shared_ptr<Exchange> x;
     int st = Exchange::create(rank, world, rccl_unique_id, fn, ctx, &x);
@@ -306,6 +315,10 @@ int32_t eph_peer_destroy(eph_peer *p) {
 int32_t eph_nbody_shard_peer(eph_nbody *h, eph_peer *p) {
     EPH_GUARD_BEGIN
     if (!h || !h->p || !p || !p->t) return EPH_ERR_BAD_ARGUMENT;
+    if (h->p->compensated()) {
+        set_last_error_text("a <Double> handle is not sharded: the error parts of the state have no exchange");
+        return EPH_ERR_UNSUPPORTED;
+    }
     if (hipSetDevice(h->p->device()) != hipSuccess) return EPH_ERR_HIP;
     std::shared_ptr<Exchange> x;
     int st = Exchange::create_peer(p->t, &x);
@@ -338,6 +351,14 @@ int32_t eph_prop_create(int32_t n, const double *pos, const double *vel, const d
     EPH_GUARD_BEGIN
     if (!out) return EPH_ERR_BAD_ARGUMENT;
     *out = nullptr;
+    if (method && std::strchr(method, '<')) {
+        // the reference has no solout on Double (solar_system_convergence.rs runs EveryStepSolout on the state alone)
+        bool tagged = false;
+        char base[64];
+        if (!parse_method_name(method, base, sizeof(base), &tagged)) return EPH_ERR_BAD_ARGUMENT;
+        set_last_error_text("eph_prop_create takes no <Double> method: the propagator's solout samples a plain DVec3 state");
+        return EPH_ERR_UNSUPPORTED;
+    }
     std::unique_ptr<eph_prop> hnd(new eph_prop());
     int st = NBodyPropagator::create(n, pos, vel, mu, t0, dt, direction, method, count, degree, &hnd->p);
     if (st) return st;

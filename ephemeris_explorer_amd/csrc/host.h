@@ -192,6 +192,8 @@ public:
     hipStream_t stream() const { return stream_; }
     int device() const { return device_; }
     int pair_variant() const { return pv_; }
+    // a `<Double>` handle (double_state.h): Integration<ODEProblem<f64, SecondOrderState<Vec<Double<DVec3>>>, NewtonianGravity>, M>
+    bool compensated() const { return compensated_; }
     void set_path(int p) { path_ = p; }
     int path() const { return path_; }
     // path 1 -> per-step launches with the one-wave-per-block force, 3 -> with the workgroup-specialised force
@@ -233,6 +235,9 @@ private:
     int startup_macro_step();                 // one LinearMultistepIntegrator::advance in the start-up regime
     int srkn_step(double h, double *y_slot);  // FixedRungeKuttaIntegrator::advance (SRKN)
     int lm_batch(int64_t k);                  // k steady-state ELM2::advance
+    int lm_batch_double(int64_t k);           // the same on a `<Double>` handle
+    int srkn_stage_double(double hb, double ha, double *y_slot, double *ye_slot, bool eval);
+    double *YEslot(int s) { return YE_.p + (size_t)s * 3 * npad_; }
     double *Yslot(int s) { return Y_.p + (size_t)s * 3 * npad_; }
     double *Aslot(int s) { return A_.p + (size_t)s * 3 * npad_; }
 
@@ -268,6 +273,11 @@ private:
     SampleArgs samp_{};
     DevBuf<Body4> P_[2];
     DevBuf<double> Y_, A_, V_, ASR_, mu_, stage_;
+    // `<Double>` handles only (allocated, zeroed and cloned on them alone): the error parts of the y ring (same slots as Y_) and of
+    // the current velocity. The accelerations have none. The SRKN working position is the ring slot under construction (slot 0 of an
+    // SRKN method), so its error part is that slot of YE_.
+    bool compensated_ = false;
+    DevBuf<double> YE_, VE_;
     DevBuf<double> fast_partial_;             // EPH_PATH_FAST scratch: [S][3][npad] partial sums
     DevBuf<float> posf_;                      // EPH_PATH_F32_PAIRS scratch: the level's positions and mu as 4 floats per body
     int64_t deferred_time_steps_ = 0;         // advance_many: `time = time + h` replays still owed (run after the gang's launch)

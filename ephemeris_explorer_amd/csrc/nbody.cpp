@@ -14,6 +14,8 @@
 #include <mutex>
 
 #include "host.h"
+#include "double_state.h"
+#include "method_name.h"
 
 namespace eph {
 
@@ -51,16 +53,26 @@ int NBodyIntegration::alloc_buffers() {
     EPH_HIP(hipMemsetAsync(V_.p, 0, sizeof(double) * V_.count, stream_));
     EPH_HIP(hipMemsetAsync(ASR_.p, 0, sizeof(double) * ASR_.count, stream_));
     EPH_HIP(hipMemsetAsync(mu_.p, 0, sizeof(double) * mu_.count, stream_));
+    if (compensated_) {                                   // Double::new(x): error +0.0
+        if ((st = YE_.alloc((size_t)L_ * 3 * npad_))) return st;
+        if ((st = VE_.alloc((size_t)3 * npad_))) return st;
+        EPH_HIP(hipMemsetAsync(YE_.p, 0, sizeof(double) * YE_.count, stream_));
+        EPH_HIP(hipMemsetAsync(VE_.p, 0, sizeof(double) * VE_.count, stream_));
+    }
     return EPH_OK;
 }
 
 int NBodyIntegration::create(int n, const double *pos, const double *vel, const double *mu, double t0, double h,
-                             const char *method, std::unique_ptr<NBodyIntegration> *out) {
-    if (n < 0 || !method || !out || (n > 0 && (!pos || !vel || !mu))) return EPH_ERR_BAD_ARGUMENT;
+                             const char *method_in, std::unique_ptr<NBodyIntegration> *out) {
+    if (n < 0 || !method_in || !out || (n > 0 && (!pos || !vel || !mu))) return EPH_ERR_BAD_ARGUMENT;
     int st = check_device();
     if (st) return st;
     std::unique_ptr<NBodyIntegration> o(new NBodyIntegration());
     o->n_ = n;
+    // "Name" or "Name<Double>" (method_name.h); the coefficient tables know base names only
+    char base[64];
+    if (!parse_method_name(method_in, base, sizeof(base), &o->compensated_)) return EPH_ERR_BAD_ARGUMENT;
+    const char *method = base;
     if (find_elm2(method, &o->lm_)) {
         // LinearMultistep::new + Substepper::<4, BlanesMoan6B>::new   multistep/mod.rs:54-57,120-128; methods.rs:37-40
         o->is_multistep_ = true;
@@ -113,6 +125,7 @@ int NBodyIntegration::clone(std::unique_ptr<NBodyIntegration> *out) {
     o->h_ = h_; o->h_sub_ = h_sub_; o->time_ = time_; o->bound_ = bound_; o->pv_ = pv_;
     o->starter_i_ = starter_i_; o->lm_i_ = lm_i_; o->evals_ = evals_;
     o->cur_ = cur_; o->pp_ = pp_; o->path_ = path_; o->predicted_ = predicted_;
+    o->compensated_ = compensated_;
     o->failed_ = failed_;                                  // (a handle a gang launch left behind its bookkeeping stays marked in its copies)
     o->lo_ = lo_; o->hi_ = hi_; o->slice_ = slice_; o->xch_ = xch_;   // a clone of a sharded handle shares the ranks
     EPH_HIP(hipStreamCreateWithFlags(&o->stream_, hipStreamNonBlocking));
@@ -128,6 +141,10 @@ int NBodyIntegration::clone(std::unique_ptr<NBodyIntegration> *out) {
     EPH_HIP(hipMemcpyAsync(o->V_.p, V_.p, sizeof(double) * V_.count, hipMemcpyDeviceToDevice, s));
     EPH_HIP(hipMemcpyAsync(o->ASR_.p, ASR_.p, sizeof(double) * ASR_.count, hipMemcpyDeviceToDevice, s));
     EPH_HIP(hipMemcpyAsync(o->mu_.p, mu_.p, sizeof(double) * mu_.count, hipMemcpyDeviceToDevice, s));
+    if (compensated_) {                                    // the error parts travel with the clone: it continues bit-identically
+        EPH_HIP(hipMemcpyAsync(o->YE_.p, YE_.p, sizeof(double) * YE_.count, hipMemcpyDeviceToDevice, s));
+        EPH_HIP(hipMemcpyAsync(o->VE_.p, VE_.p, sizeof(double) * VE_.count, hipMemcpyDeviceToDevice, s));
+    }
     EPH_HIP(hipStreamSynchronize(s));
     *out = std::move(o);
     return EPH_OK;
@@ -138,6 +155,10 @@ int NBodyIntegration::clone(std::unique_ptr<NBodyIntegration> *out) {
 // positions of ALL bodies are, through one all-gather after every kernel that publishes positions.
 int NBodyIntegration::set_shard(std::shared_ptr<Exchange> x) {
     if (!x || xch_) return EPH_ERR_BAD_ARGUMENT;          // a handle is sharded once, while every body is current
+    if (compensated_) {
+        set_last_error_text("a <Double> handle is not sharded: the error parts of the state have no exchange");
+        return EPH_ERR_UNSUPPORTED;
+    }
     if (n_ <= kSmallN) return EPH_ERR_UNSUPPORTED;        // one-workgroup systems: replicas only
     if (npad_ % (x->world() * kTile) != 0) {
         set_last_error_text("sharding needs the padded body count to be a multiple of 64 * world");
@@ -168,7 +189,9 @@ int NBodyIntegration::srkn_step(double h, double *y_slot) {
     if (time_ >= bound_) return EPH_BOUND_REACHED;
     if (time_ + h == time_) return EPH_STEP_SIZE_UNDERFLOW;
     int st;
-    for (int s = 0; s < rk_.stages; ++s) {
+    for (int s = 0; s < rk_.stages && compensated_; ++s)
+        if ((st = srkn_stage_double(h * rk_.B[s], h * rk_.A[s], y_slot, YE_.p + (y_slot - Y_.p), !rk_.fsal || s > 0 || starter_i_ == 0))) return st;
+    for (int s = 0; s < rk_.stages && !compensated_; ++s) {
         // *dy = *dy + *ddy * (h * C::B[s]);  *y = *y + *dy * (h * C::A[s])
         const KickDrift kd{V_.p, y_slot, h * rk_.B[s], h * rk_.A[s], P_[pp_ ^ 1].p};
         if (!rk_.fsal || s > 0 || starter_i_ == 0) {
@@ -183,6 +206,19 @@ int NBodyIntegration::srkn_step(double h, double *y_slot) {
     }
     time_ = time_ + h;
     starter_i_ += 1;
+    return EPH_OK;
+}
+
+// One SRKN stage on Double: the force-only launch (values) when the stage evaluates, then the compensated kick and drift
+int NBodyIntegration::srkn_stage_double(double hb, double ha, double *y_slot, double *ye_slot, bool eval) {
+    int st;
+    if (eval) {
+        if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, ASR_.p, force_kind(), lo_, hi_))) return st;
+        evals_++;
+    }                                                  // (FSAL first stage: the acceleration is the previous step's last)
+    const KickDriftDouble kd{ASR_.p, V_.p, VE_.p, y_slot, ye_slot, hb, ha, P_[pp_ ^ 1].p};
+    if ((st = launch_kick_drift_double(stream_, n_, npad_, kd))) return st;
+    pp_ ^= 1;
     return EPH_OK;
 }
 
@@ -202,6 +238,7 @@ int NBodyIntegration::startup_macro_step() {
     }
     const int nslot = (cur_ + L_ - 1) % L_;
     if ((st = launch_copy3(stream_, n_, npad_, Yslot(cur_), Yslot(nslot)))) return st;
+    if (compensated_ && (st = launch_copy3(stream_, n_, npad_, YEslot(cur_), YEslot(nslot)))) return st;   // clone_from copies the error parts
     cur_ = nslot;   // from here on the working state is the new front, as in the reference after the clone_from
     for (int s = 0; s < substeps_; ++s)
         if ((st = srkn_step(h_sub_, Yslot(nslot)))) return st;
@@ -255,8 +292,81 @@ int NBodyIntegration::resolve_timing() {
     return st;
 }
 
+// k x ELM2::advance on Double. At most 32 bodies (and not path 1): ONE launch of the single-workgroup kernel. Otherwise, per step,
+// the predictor of the next level, the force-only launch on its values, Cowell's velocity -- the last two element-wise pieces of
+// step s and the predictor of step s + 1 in one launch (double_step.hip).
+int NBodyIntegration::lm_batch_double(int64_t k) {
+    LmDoubleArgs d{};
+    LmArgs &a = d.a;
+    a.n = n_; a.npad = npad_; a.L = L_;
+    a.lo = 0; a.hi = n_;
+    a.Y = Y_.p; a.A = A_.p; a.V = V_.p;
+    d.YE = YE_.p; d.VE = VE_.p;
+    for (int j = 0; j < L_; ++j) { a.wa[j] = lm_.wa[j]; a.wb[j] = lm_.wb[j]; a.cw[j] = lm_.cw[j]; }
+    a.h = h_;
+    a.hh = h_ * h_ * lm_.inv_beta_d;
+    a.hc = h_ * lm_.inv_cowell_d;
+    a.kind = force_kind();
+    if (collect_) return EPH_ERR_UNSUPPORTED;                          // (gang_ready refuses a <Double> handle first)
+    if (path_ == 2 && n_ > kGangMaxN) {
+        set_last_error_text("a <Double> handle takes the single-workgroup kernel up to 32 bodies");
+        return EPH_ERR_UNSUPPORTED;
+    }
+    const bool persistent = n_ <= kGangMaxN && path_ != 1;
+    int st;
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    if (timing_) {
+        if (ev_pending_.size() >= 1024) (void)resolve_timing();
+        if (!ev_free_.empty()) { ev = ev_free_.back(); ev_free_.pop_back(); }
+        else { EPH_HIP(hipEventCreate(&ev.first)); EPH_HIP(hipEventCreate(&ev.second)); }
+        if (hipEventRecord(ev.first, stream_) != hipSuccess) {
+            ev_free_.push_back(ev);
+            set_last_error("hipEventRecord", hipGetLastError());
+            return EPH_ERR_HIP;
+        }
+    }
+    struct TimingGuard {
+        std::pair<hipEvent_t, hipEvent_t> &ev; std::vector<std::pair<hipEvent_t, hipEvent_t>> &free_list; bool armed;
+        ~TimingGuard() { if (armed && ev.second) free_list.push_back(ev); }
+    } timing_guard{ev, ev_free_, true};
+    a.cur = cur_;
+    a.pos_cur = P_[pp_].p;
+    a.pos_next = P_[pp_ ^ 1].p;
+    if (persistent) {
+        if ((st = launch_lm_double_small(pv_, stream_, d, k))) return st;
+        cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
+        if (timing_) kernel_launches_ += 1;
+    } else {
+        a.do_predict = 1;
+        d.do_cowell = 0;
+        if ((st = launch_lm_double_step(stream_, d))) return st;       // the first step's predictor alone
+        for (int64_t s = 1; s <= k; ++s) {
+            pp_ ^= 1;
+            cur_ = (cur_ + L_ - 1) % L_;
+            if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(cur_), force_kind(), 0, n_))) return st;
+            a.cur = cur_;
+            a.pos_cur = P_[pp_].p;
+            a.pos_next = P_[pp_ ^ 1].p;
+            a.do_predict = s < k;
+            d.do_cowell = 1;
+            if ((st = launch_lm_double_step(stream_, d))) return st;
+        }
+        if (timing_) kernel_launches_ += (uint64_t)k;
+    }
+    if (ev.second) {
+        EPH_HIP(hipEventRecord(ev.second, stream_));
+        ev_pending_.push_back(ev);
+        timing_guard.armed = false;
+    }
+    for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;               // problem.time = problem.time + h, per step
+    lm_i_ += (uint32_t)k;
+    evals_ += (uint64_t)k;
+    return EPH_OK;
+}
+
 // k x ELM2::advance   second_order/mod.rs:90-131
 int NBodyIntegration::lm_batch(int64_t k) {
+    if (compensated_) return lm_batch_double(k);
     LmArgs a{};
     a.n = n_; a.npad = npad_; a.L = L_;
     a.lo = lo_; a.hi = hi_;
@@ -412,7 +522,7 @@ int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
 }
 
 bool NBodyIntegration::gang_ready(int64_t k) const {
-    if (!is_multistep_ || !started() || sharded() || n_ > kGangMaxN || n_ <= 0 || (path_ != 0 && path_ != 2)) return false;
+    if (compensated_ || !is_multistep_ || !started() || sharded() || n_ > kGangMaxN || n_ <= 0 || (path_ != 0 && path_ != 2)) return false;
     if (k <= 0 || k > ((int64_t)1 << 30)) return false;
     int after = EPH_OK;
     return steps_available(k, &after) == k;

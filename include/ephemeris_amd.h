@@ -103,7 +103,30 @@ int32_t eph_accel_eval(int32_t n, const double *pos_xyz, const double *mu, doubl
  *                                              integration/src/methods.rs:37-40), or any SRKN table name
  *          "BlanesMoan6B" | "BlanesMoan11B" | "BlanesMoan14A" | "ForestRuth" | "McLachlanO4" |
  *          "McLachlanSS17" | "Pefrl" | "Ruth"  (FixedRungeKutta<SRKN>, methods.rs:22-29).
- * h is signed (Backward propagation = negative h). */
+ * h is signed (Backward propagation = negative h).
+ *
+ * COMPENSATED STATE. Every name above may be followed by the exact suffix "<Double>" ("QuinlanTremaine12<Double>",
+ * "Stormer13<Double>", "BlanesMoan14A<Double>", ...; case sensitive, no white space; any other suffix is
+ * EPH_ERR_BAD_ARGUMENT like an unknown name). The handle is then Rust's M over the state type Double<DVec3> of the
+ * reference's own convergence test (ephemeris/tests/solar_system_convergence.rs:12-199):
+ *   Integration<ODEProblem<f64, SecondOrderState<Vec<Double<DVec3>>>, NewtonianGravity>, M>
+ * Every position and velocity component carries a running error term, starting as Double::new(x) (error +0.0); every
+ * + - * / of the steppers on the variable type (ELM2's predictor, Cowell's velocity including (y - ym1) / h, SRKN's kick and
+ * drift, the start-up substeps) is Double's operator of that name (two_sum + fast_two_sum; Mul / Div on both parts). The
+ * force reads and accumulates values (same pair term, same summation order, eph_set_pair_variant applies); time, bound and
+ * underflow tests, counters: unchanged. On such a handle
+ *   - eph_nbody_get_state returns the value parts (what the reference's test reads), eph_nbody_get_acc the acceleration,
+ *     which has no error part. The error parts are not readable through the ABI;
+ *   - eph_nbody_clone carries the error parts: the clone continues bit-identically;
+ *   - eph_nbody_set_path takes 0 (auto), 1 (one launch per step piece, any n) and 2 (the single-workgroup kernel, at most 32
+ *     bodies -- else EPH_ERR_UNSUPPORTED at the next steady step); 3-6 are EPH_ERR_UNSUPPORTED with an eph_last_error text;
+ *   - eph_nbody_shard / eph_nbody_shard_peer are EPH_ERR_UNSUPPORTED (the handle stays usable), and so is eph_prop_create with
+ *     a "<Double>" name: the reference has no solout on Double;
+ *   - eph_nbody_advance_many advances it by the separate call, with the same results;
+ *   - eph_ephemeris_interpolation_errors works exactly like stepping by hand and comparing the value parts;
+ *   - eph_srkn_coeffs / eph_elm2_coeffs know base names only.
+ * A steady multistep advance of at most 32 bodies is ONE launch whatever the step count; everything else (more bodies,
+ * start-up, SRKN methods) runs a force launch and a compensated element-wise launch per step or stage. */
 typedef struct eph_nbody eph_nbody;
 int32_t eph_nbody_create(int32_t n, const double *pos_xyz, const double *vel_xyz, const double *mu, double t0,
                          double h, const char *method, eph_nbody **out);

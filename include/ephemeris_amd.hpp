@@ -165,16 +165,20 @@ private:
 };
 
 // Integration<NBodyProblem<DVec3>, M> without a solout: M::new(FixedMethodParams::new(h)).integrate(problem)
+// compensated = true: the state is the reference's Double<DVec3> (every position and velocity component carries a running error
+// term, ephemeris/tests/solar_system_convergence.rs:12-110): the method goes out as "<method><Double>"; state() reads the value parts.
 class NBodyIntegration {
 public:
     NBodyIntegration(const std::vector<DVec3> &y, const std::vector<DVec3> &dy, const std::vector<double> &gravitational_parameters, double time,
-                     double h, const char *method = "QuinlanTremaine12") : n_(static_cast<int32_t>(y.size())) {
+                     double h, const char *method = "QuinlanTremaine12", bool compensated = false)
+        : n_(static_cast<int32_t>(y.size())), compensated_(compensated) {
         if (dy.size() != y.size() || gravitational_parameters.size() != y.size()) throw std::invalid_argument("NBodyIntegration: sizes differ");
-        detail::check(eph_nbody_create(n_, detail::flat(y), detail::flat(dy), gravitational_parameters.data(), time, h, method, &h_), "eph_nbody_create");
+        const std::string name = std::string(method ? method : "") + (compensated ? "<Double>" : "");
+        detail::check(eph_nbody_create(n_, detail::flat(y), detail::flat(dy), gravitational_parameters.data(), time, h, name.c_str(), &h_), "eph_nbody_create");
     }
-    NBodyIntegration(NBodyIntegration &&o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_) {}
+    NBodyIntegration(NBodyIntegration &&o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_), compensated_(o.compensated_) {}
     NBodyIntegration &operator=(NBodyIntegration &&o) noexcept {
-        if (this != &o) { if (h_) eph_nbody_destroy(h_); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; }
+        if (this != &o) { if (h_) eph_nbody_destroy(h_); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; compensated_ = o.compensated_; }
         return *this;
     }
     NBodyIntegration(const NBodyIntegration &) = delete;
@@ -186,8 +190,9 @@ public:
     NBodyIntegration clone() const {
         eph_nbody *c = nullptr;
         detail::check(eph_nbody_clone(h_, &c), "eph_nbody_clone");
-        return NBodyIntegration(c, n_);
+        return NBodyIntegration(c, n_, compensated_);
     }
+    bool compensated() const { return compensated_; }
     // problem.{time, state.y, state.dy}, IntegratorState::step_count
     double state(std::vector<DVec3> &y, std::vector<DVec3> &dy, uint32_t *step_count = nullptr) const {
         y.resize(static_cast<size_t>(n_));
@@ -199,9 +204,10 @@ public:
     int32_t bodies() const { return n_; }
 
 private:
-    NBodyIntegration(eph_nbody *h, int32_t n) : h_(h), n_(n) {}
+    NBodyIntegration(eph_nbody *h, int32_t n, bool compensated) : h_(h), n_(n), compensated_(compensated) {}
     eph_nbody *h_ = nullptr;
     int32_t n_ = 0;
+    bool compensated_ = false;
 };
 
 // NBodyPropagator<D, DVec3, M, SplineInterpolators<D, DVec3, LeastSquaresFit>>  (nbody.rs:65-235; celestial.rs:156-186)
