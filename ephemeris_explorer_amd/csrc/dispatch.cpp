@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstdlib>
 
+#include "double_state.h"
 #include "eph_internal.h"
 
 namespace eph {
@@ -109,6 +110,13 @@ int launch_lm_persistent(int pv, hipStream_t s, const LmArgs &a, int64_t nsteps)
         return t->lm_small(s, b, nsteps);
     }
     return t->lm_persistent(s, a, nsteps);
+}
+int launch_lm_double_small(int pv, hipStream_t s, const LmDoubleArgs &d, int64_t nsteps) {
+    const PairKernels *t = table(pv);
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
+    if (d.a.n <= 0 || nsteps <= 0) return EPH_OK;
+    if (d.a.n > kGangMaxN) return EPH_ERR_UNSUPPORTED;
+    return t->lm_double_small(s, d, nsteps);
 }
 int launch_lm_small_many(int pv, hipStream_t s, const LmArgs *argv_dev, int count, int L, int64_t nsteps) {
     const PairKernels *t = table(pv);

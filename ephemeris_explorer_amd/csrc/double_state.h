@@ -101,7 +101,6 @@ __device__ __forceinline__ void kick_drift_double(const KickDriftDouble &kd, siz
 // double_step.hip (compiled once): the per-step forms, any n
 int launch_lm_double_step(hipStream_t s, const LmDoubleArgs &d);     // [Cowell of level a.cur] + [predictor of the next level, a.do_predict]
 int launch_kick_drift_double(hipStream_t s, int n, int npad, const KickDriftDouble &kd);
-// step_double_small.hip (once per evaluation order of the point-mass term): n <= kGangMaxN bodies, one workgroup, nsteps per launch
-int launch_lm_double_small(int pv, hipStream_t s, const LmDoubleArgs &d, int64_t nsteps);
+// (the single-workgroup form, step_double_small.hip, exists once per evaluation order: launch_lm_double_small, eph_internal.h)
 
 }  // namespace eph

@@ -61,28 +61,4 @@ int launch_kick_drift_double(hipStream_t s, int n, int npad, const KickDriftDoub
     return EPH_OK;
 }
 
-// the single-workgroup kernel exists once per evaluation order of the point-mass term (step_double_small.hip)
-namespace pv0 { int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps); }
-namespace pv1 { int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps); }
-namespace pv2 { int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps); }
-namespace pv3 { int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps); }
-namespace pv4 { int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps); }
-namespace pv5 { int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps); }
-namespace pv6 { int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps); }
-int launch_lm_double_small(int pv, hipStream_t s, const LmDoubleArgs &d, int64_t nsteps) {
-    static_assert(kPairVariants == 7, "one lm_double_small per evaluation order");
-    if (d.a.n <= 0 || nsteps <= 0) return EPH_OK;
-    if (d.a.n > kGangMaxN) return EPH_ERR_UNSUPPORTED;
-    switch (pv) {
-        case 0: return pv0::lm_double_small(s, d, nsteps);
-        case 1: return pv1::lm_double_small(s, d, nsteps);
-        case 2: return pv2::lm_double_small(s, d, nsteps);
-        case 3: return pv3::lm_double_small(s, d, nsteps);
-        case 4: return pv4::lm_double_small(s, d, nsteps);
-        case 5: return pv5::lm_double_small(s, d, nsteps);
-        case 6: return pv6::lm_double_small(s, d, nsteps);
-        default: return EPH_ERR_BAD_ARGUMENT;
-    }
-}
-
 }  // namespace eph

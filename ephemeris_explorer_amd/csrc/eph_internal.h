@@ -130,6 +130,9 @@ int launch_lm_persistent(int pv, hipStream_t s, const LmArgs &a, int64_t nsteps)
 // `count` single-workgroup systems (n <= kGangMaxN each, same L), one workgroup each, argv in device memory
 constexpr int kGangMaxN = 32;
 int launch_lm_small_many(int pv, hipStream_t s, const LmArgs *argv_dev, int count, int L, int64_t nsteps);
+// a `<Double>` handle's single-workgroup steps (LmDoubleArgs: double_state.h): n <= kGangMaxN bodies, nsteps per launch
+struct LmDoubleArgs;
+int launch_lm_double_small(int pv, hipStream_t s, const LmDoubleArgs &d, int64_t nsteps);
 // opt-in fast path: slice-parallel partial sums combined in slice order (NOT the reference's summation order)
 int fast_slices(int npad, bool approx = false);                     // S (the rsq form takes twice the waves)
 #ifndef EPH_F32_GROUP
@@ -161,6 +164,7 @@ struct PairKernels {                        // one evaluation order's launchers 
     int (*lm_persistent)(hipStream_t, const LmArgs &, int64_t);
     int (*lm_small)(hipStream_t, const LmArgs &, int64_t);
     int (*lm_small_many)(hipStream_t, const LmArgs *, int, int, int64_t);
+    int (*lm_double_small)(hipStream_t, const LmDoubleArgs &, int64_t);
     int (*lm_step_fast)(hipStream_t, const LmArgs &, double *, int, int, bool, float *, int, int, int, unsigned *);
     int (*craft_launch)(hipStream_t, const CraftArgs &, const CraftLaunch &);
     int (*debug_inv_r3)(hipStream_t, int64_t, const double *, double *, double *);

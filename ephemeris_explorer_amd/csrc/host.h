@@ -236,6 +236,7 @@ private:
     int srkn_step(double h, double *y_slot);  // FixedRungeKuttaIntegrator::advance (SRKN)
     int lm_batch(int64_t k);                  // k steady-state ELM2::advance
     int lm_batch_double(int64_t k);           // the same on a `<Double>` handle
+    void fill_lm_args(LmArgs &a) const;       // the fields of a batch's launch arguments that both set
     int srkn_stage_double(double hb, double ha, double *y_slot, double *ye_slot, bool eval);
     double *YEslot(int s) { return YE_.p + (size_t)s * 3 * npad_; }
     double *Yslot(int s) { return Y_.p + (size_t)s * 3 * npad_; }
@@ -251,6 +252,7 @@ private:
     // wait): waiting for the closing event inside advance() made the call synchronous and cost a 20-step block 2 % of its time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending_, ev_free_;
     int resolve_timing();
+    struct TimingGuard;                       // one such interval, opened and closed by a batch (nbody.cpp)
     // the last fused step of a batch left the NEXT step's predicted positions in P_[pp_ ^ 1] and in the ring slot the next step
     // takes (the oldest level's, dead by then): the next batch starts with its force evaluation instead of a predictor launch
     bool predicted_ = false;

@@ -273,7 +273,7 @@ int64_t NBodyIntegration::steps_available(int64_t k, int *status_after) const {
     return s;
 }
 
-// Every pending pair has BOTH events recorded (lm_batch pushes a pair only behind its closing record). A pair whose query fails
+// Every pending pair has BOTH events recorded (TimingGuard::close pushes a pair only behind its closing record). A pair whose query fails
 // (a device error in between) is skipped and recycled with the others: the list is always emptied, so one bad interval can neither
 // stop the accumulation nor fill the list until every later batch fails (advisor, round 4).
 int NBodyIntegration::resolve_timing() {
@@ -292,21 +292,53 @@ int NBodyIntegration::resolve_timing() {
     return st;
 }
 
+// One timed interval on a handle's stream (enable_timing): a pair of events around a batch's launches, read later (host.h). What
+// holds for the two event lists, stated here once:
+//   * a pair joins the pending list only behind its closing record (close): resolve_timing relies on both events being recorded;
+//   * every return between open and a successful close -- a failed opening record too -- hands the pair back to the free list;
+//   * the pending list is resolved when 1024 pairs wait (a failed interval is dropped there, not returned here).
+struct NBodyIntegration::TimingGuard {
+    NBodyIntegration &ig;
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};   // null: not open (this batch is not timed), or closed
+    ~TimingGuard() { if (ev.second) ig.ev_free_.push_back(ev); }
+    int open() {
+        if (!ig.timing_ || ig.collect_) return EPH_OK;         // (a gang's launch is timed by advance_many, around the one launch)
+        if (ig.ev_pending_.size() >= 1024) (void)ig.resolve_timing();
+        if (!ig.ev_free_.empty()) { ev = ig.ev_free_.back(); ig.ev_free_.pop_back(); }
+        else { EPH_HIP(hipEventCreate(&ev.first)); EPH_HIP(hipEventCreate(&ev.second)); }
+        if (hipEventRecord(ev.first, ig.stream_) == hipSuccess) return EPH_OK;
+        set_last_error("hipEventRecord", hipGetLastError());
+        return EPH_ERR_HIP;
+    }
+    int close() {
+        if (!ev.second) return EPH_OK;
+        EPH_HIP(hipEventRecord(ev.second, ig.stream_));
+        ig.ev_pending_.push_back(ev);
+        ev = {nullptr, nullptr};
+        return EPH_OK;
+    }
+};
+
+// what every steady batch's launches take from the handle: sizes, rings, weights, step sizes, the force kernel's kind
+void NBodyIntegration::fill_lm_args(LmArgs &a) const {
+    a.n = n_; a.npad = npad_; a.L = L_;
+    a.Y = Y_.p; a.A = A_.p; a.V = V_.p;
+    for (int j = 0; j < L_; ++j) { a.wa[j] = lm_.wa[j]; a.wb[j] = lm_.wb[j]; a.cw[j] = lm_.cw[j]; }
+    a.h = h_;
+    a.hh = h_ * h_ * lm_.inv_beta_d;     // h * h * Ratio::from_recip(C::BETA_D)
+    a.hc = h_ * lm_.inv_cowell_d;        // h * Ratio::from_recip(Self::BETA_D)
+    a.kind = force_kind();
+}
+
 // k x ELM2::advance on Double. At most 32 bodies (and not path 1): ONE launch of the single-workgroup kernel. Otherwise, per step,
 // the predictor of the next level, the force-only launch on its values, Cowell's velocity -- the last two element-wise pieces of
 // step s and the predictor of step s + 1 in one launch (double_step.hip).
 int NBodyIntegration::lm_batch_double(int64_t k) {
     LmDoubleArgs d{};
     LmArgs &a = d.a;
-    a.n = n_; a.npad = npad_; a.L = L_;
+    fill_lm_args(a);
     a.lo = 0; a.hi = n_;
-    a.Y = Y_.p; a.A = A_.p; a.V = V_.p;
     d.YE = YE_.p; d.VE = VE_.p;
-    for (int j = 0; j < L_; ++j) { a.wa[j] = lm_.wa[j]; a.wb[j] = lm_.wb[j]; a.cw[j] = lm_.cw[j]; }
-    a.h = h_;
-    a.hh = h_ * h_ * lm_.inv_beta_d;
-    a.hc = h_ * lm_.inv_cowell_d;
-    a.kind = force_kind();
     if (collect_) return EPH_ERR_UNSUPPORTED;                          // (gang_ready refuses a <Double> handle first)
     if (path_ == 2 && n_ > kGangMaxN) {
         set_last_error_text("a <Double> handle takes the single-workgroup kernel up to 32 bodies");
@@ -314,21 +346,8 @@ int NBodyIntegration::lm_batch_double(int64_t k) {
     }
     const bool persistent = n_ <= kGangMaxN && path_ != 1;
     int st;
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (timing_) {
-        if (ev_pending_.size() >= 1024) (void)resolve_timing();
-        if (!ev_free_.empty()) { ev = ev_free_.back(); ev_free_.pop_back(); }
-        else { EPH_HIP(hipEventCreate(&ev.first)); EPH_HIP(hipEventCreate(&ev.second)); }
-        if (hipEventRecord(ev.first, stream_) != hipSuccess) {
-            ev_free_.push_back(ev);
-            set_last_error("hipEventRecord", hipGetLastError());
-            return EPH_ERR_HIP;
-        }
-    }
-    struct TimingGuard {
-        std::pair<hipEvent_t, hipEvent_t> &ev; std::vector<std::pair<hipEvent_t, hipEvent_t>> &free_list; bool armed;
-        ~TimingGuard() { if (armed && ev.second) free_list.push_back(ev); }
-    } timing_guard{ev, ev_free_, true};
+    TimingGuard timing{*this};
+    if ((st = timing.open())) return st;
     a.cur = cur_;
     a.pos_cur = P_[pp_].p;
     a.pos_next = P_[pp_ ^ 1].p;
@@ -353,11 +372,7 @@ int NBodyIntegration::lm_batch_double(int64_t k) {
         }
         if (timing_) kernel_launches_ += (uint64_t)k;
     }
-    if (ev.second) {
-        EPH_HIP(hipEventRecord(ev.second, stream_));
-        ev_pending_.push_back(ev);
-        timing_guard.armed = false;
-    }
+    if ((st = timing.close())) return st;
     for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;               // problem.time = problem.time + h, per step
     lm_i_ += (uint32_t)k;
     evals_ += (uint64_t)k;
@@ -368,15 +383,9 @@ int NBodyIntegration::lm_batch_double(int64_t k) {
 int NBodyIntegration::lm_batch(int64_t k) {
     if (compensated_) return lm_batch_double(k);
     LmArgs a{};
-    a.n = n_; a.npad = npad_; a.L = L_;
+    fill_lm_args(a);
     a.lo = lo_; a.hi = hi_;
-    a.Y = Y_.p; a.A = A_.p; a.V = V_.p;
-    for (int j = 0; j < L_; ++j) { a.wa[j] = lm_.wa[j]; a.wb[j] = lm_.wb[j]; a.cw[j] = lm_.cw[j]; }
-    a.h = h_;
-    a.hh = h_ * h_ * lm_.inv_beta_d;     // h * h * Ratio::from_recip(C::BETA_D)
-    a.hc = h_ * lm_.inv_cowell_d;        // h * Ratio::from_recip(Self::BETA_D)
     a.samp = samp_;
-    a.kind = force_kind();
     int st;
     const bool fast = path_ == EPH_PATH_FAST || path_ == EPH_PATH_FAST_RSQ || path_ == EPH_PATH_F32_PAIRS;
     // on a target partition only the binary32 pair arithmetic runs (BASELINE configs[4] as stated); fast / fast-rsq stay single-device
@@ -397,34 +406,17 @@ int NBodyIntegration::lm_batch(int64_t k) {
     const bool persistent = n_ <= kSmallN && path_ != 1 && path_ != 3 && !fast;
     if (path_ == 2 && n_ > kSmallN) return EPH_ERR_UNSUPPORTED;
     if (collect_ && !persistent) return EPH_ERR_UNSUPPORTED;           // (advance_many checks gang_ready first)
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (timing_ && !collect_) {
-        if (ev_pending_.size() >= 1024) (void)resolve_timing();           // (a failed interval is dropped there, not returned here)
-        if (!ev_free_.empty()) { ev = ev_free_.back(); ev_free_.pop_back(); }
-        else { EPH_HIP(hipEventCreate(&ev.first)); EPH_HIP(hipEventCreate(&ev.second)); }
-        if (hipEventRecord(ev.first, stream_) != hipSuccess) {
-            ev_free_.push_back(ev);
-            set_last_error("hipEventRecord", hipGetLastError());
-            return EPH_ERR_HIP;
-        }
-    }
-    // the pair joins the pending list only once its closing event is recorded (below); every earlier return hands it back
-    struct TimingGuard {
-        std::pair<hipEvent_t, hipEvent_t> &ev; std::vector<std::pair<hipEvent_t, hipEvent_t>> &free_list; bool armed;
-        ~TimingGuard() { if (armed && ev.second) free_list.push_back(ev); }
-    } timing_guard{ev, ev_free_, true};
+    TimingGuard timing{*this};
+    if ((st = timing.open())) return st;
+    a.cur = cur_;
+    a.pos_cur = P_[pp_].p;
+    a.pos_next = P_[pp_ ^ 1].p;
     if (persistent) {
-        a.cur = cur_;
-        a.pos_cur = P_[pp_].p;
-        a.pos_next = P_[pp_ ^ 1].p;
         if (collect_) collect_->push_back(a);                           // launched by advance_many with the gang's others
         else if ((st = launch_lm_persistent(pv_, stream_, a, k))) return st;
         cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
         if (timing_) kernel_launches_ += 1;
     } else {
-        a.cur = cur_;
-        a.pos_cur = P_[pp_].p;
-        a.pos_next = P_[pp_ ^ 1].p;
         // a handle that can neither take the single-workgroup kernels nor exchange positions leaves the prediction of the step
         // after the batch behind (host.h predicted_): one launch and one launch boundary less per call
         const bool leave_prediction = n_ > kSmallN && !sharded();
@@ -459,11 +451,7 @@ int NBodyIntegration::lm_batch(int64_t k) {
         predicted_ = leave_prediction;
         if (timing_) kernel_launches_ += (uint64_t)k;
     }
-    if (ev.second) {
-        EPH_HIP(hipEventRecord(ev.second, stream_));
-        ev_pending_.push_back(ev);
-        timing_guard.armed = false;
-    }
+    if ((st = timing.close())) return st;
     if (collect_) deferred_time_steps_ += k;              // advance_many replays them once the gang is launched
     else for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;   // problem.time = problem.time + h, per step (the launch is already queued)
     lm_i_ += (uint32_t)k;

@@ -9,6 +9,7 @@ int lm_step_wg(hipStream_t s, int wb, const LmArgs &a);                         
 int lm_persistent(hipStream_t s, const LmArgs &a, int64_t nsteps);                                         // step_wave.hip
 int lm_small(hipStream_t s, const LmArgs &a, int64_t nsteps);                                              // step_small.hip
 int lm_small_many(hipStream_t s, const LmArgs *argv_dev, int count, int L, int64_t nsteps);                // step_small.hip
+int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps);                                 // step_double_small.hip
 int lm_step_fast(hipStream_t s, const LmArgs &a, double *partial, int S, int unroll, bool approx, float *posf, int f32_stage,
                  int conv_lo, int conv_cnt, unsigned *tickets);                                             // fast.hip
 int craft_launch(hipStream_t s, const CraftArgs &a, const CraftLaunch &how);                               // craft_sweep.hip

@@ -19,41 +19,16 @@ __device__ long long g_small_ticks[8];               // (tuning builds) shader-c
 __device__ long long g_small_place[4][1024];         // (tuning builds) HW_ID, XCC_ID + 1, start and end (100 MHz) of every workgroup
 #endif
 
-// ------------------------------------------------------------------------------------------------------
-// k_lm_small: n <= 64, the whole system in ONE workgroup, `nsteps` integrator steps per launch (second design
-// of the persistent kernel; k_lm_persistent above is the first and stays selectable for comparison).
-// Inside one workgroup the pair symmetry the reference uses CAN be shared: thread p owns the unordered pair
-// (i, j), i < j, computes d, n2, 1/(n2*sqrt(n2)) once and writes both directed contributions
-//     c(i<-j) =  d * (mu_j * inv)  -> U[i][j]   ("sources after the body")
-//     c(j<-i) = -d * (mu_i * inv)  -> Lw[j][i]  ("sources before the body")
-// exactly the reference's acceleration_paired halves. Rows of U / Lw are zero outside those ranges (written once
-// at kernel start), so the two ordered chains of a body are plain in-order sums over a row (adding +0.0 is exact;
-// the accumulators start at +0.0 and never become -0.0), one thread per (body, component, half):
-//     ddy[i] = (0 + c(0,i) + ... + c(i-1,i)) + (0 + c(i,i+1) + ... + c(i,n-1)).
-// Two barriers per step; history ring, velocity, predictor and Cowell formula live in the (body, component) thread.
-// ------------------------------------------------------------------------------------------------------
-// the step loop of k_lm_small unrolled over the L ring rotations: copy K runs at rotation (L - K) % L
-template <typename Step, int... Ks>
-__device__ __forceinline__ void small_steps(Step &step, long long &s, long long nsteps, int &rot, bool &more,
-                                            std::integer_sequence<int, Ks...>) {
-    constexpr int L = sizeof...(Ks);
-    (void)std::initializer_list<int>{(more ? (step(std::integral_constant<int, (L - Ks) % L>{}, s),
-                                              rot = (L - Ks + L - 1) % L, more = ++s <= nsteps, 0)
-                                           : 0)...};
-}
-constexpr int kSmallThreads = 512;        // eight waves: one unordered pair per thread (496 at 32 bodies), the 3 n chains x 2 halves in waves 0-2
-constexpr int kSmallThreads2 = 256;       // the TWO form (gangs of more systems than CUs): four waves, two unordered pairs per thread
-constexpr int kSmallMaxN = 32;           // bodies (the reference's shipped system has exactly 32); 33..64 -> k_lm_persistent
-constexpr int kSmallRow = 32 + 2;        // doubles per row: 16-byte aligned rows an odd number of 16-byte units apart
-constexpr int kSmallRows = 3 * kSmallMaxN;
+#include "small_frame.h"
+
+// k_lm_small: the frame of small_frame.h around a plain (body, component) state (second design of the persistent kernel;
+// k_lm_persistent of step_wave.hip is the first and stays selectable for comparison).
 // -DEPH_EXPERIMENTS=1 -DEPH_SMALL_ACCOUNT=1 (tuning build, scripts/build_exp.sh): thread 0 of k_lm_small accumulates shader-clock ticks per phase
 // of a step into g_small_ticks[3..7] (wait at barrier A | sum1 + pair | wait at barrier B | row sums | sum2 + hand-over)
 #if !EPH_EXPERIMENTS || !defined(EPH_SMALL_ACCOUNT)
 #undef EPH_SMALL_ACCOUNT
 #define EPH_SMALL_ACCOUNT 0
 #endif
-// (ONE rolled copy of the step, the history shifted through the registers every step -- 24 v_mov_b64 -- instead of twelve copies,
-// one per ring rotation (45 KB of code): measured slower at every gang size, profiles/r03_small_kernel_evidence.md.)
 #define SMALL_TICK(k) do { if constexpr (EPH_SMALL_ACCOUNT) { const long long now_ = (long long)__builtin_readcyclecounter(); acct[k] += now_ - acct_t; acct_t = now_; } } while (0)
 
 // k_lm_small, round 3. The per-phase tick accounting of round 2's kernel (thread 0, 32 bodies, 2125 ticks per step:
@@ -93,7 +68,7 @@ __global__ void __launch_bounds__(TWO ? kSmallThreads2 : kSmallThreads) k_lm_sma
     const int wg_flags = a.wg_flags;
 
     const int nrow = (n + 15) & ~15;   // row length the chains walk (the padding holds zeros)
-    for (int k = tid; k < kSmallRows * kSmallRow; k += blockDim.x) { (&U[0][0])[k] = 0.0; (&Lw[0][0])[k] = 0.0; }
+    small_zero_rows(U, Lw, tid);
     if (tid < kTile) sP[tid] = a.pos_cur[tid < n ? tid : n - 1];
     // history and coefficients live in VGPRs for the whole launch: yv[j] / av[j] = level (newest - j).
     // (Kernel arguments would otherwise be re-fetched through the scalar cache every step.)
@@ -120,21 +95,14 @@ __global__ void __launch_bounds__(TWO ? kSmallThreads2 : kSmallThreads) k_lm_sma
         samp_left = samp_m ? samp_m - a.samp.phase[my_i] % samp_m : 0;
         samp_slot = a.samp.offset[my_i];
     }
-    // this thread's unordered pair (i < j), row-major over the strict upper triangle (n <= 32: at most 496 pairs for 512 threads),
-    // decoded once. A slot without a pair runs pair (0, 1) again and stores nothing: straight-line code.
+    // this thread's unordered pair (i < j), decoded once.
     // TWO (round 5): pairs `tid` and `tid + 256` in FOUR waves instead of one pair per thread in eight. Measured for one system it is
     // SLOWER (0.854 against 0.784 us per step at 32 bodies: one wave's two interleaved interactions cover less latency than two
     // waves' one each) -- but two such workgroups fit a CU, and a gang of more systems than the chip has CUs gains a third
     // (1024 systems: 2.63 against 3.51 us per step of the gang, 1.25e10 body-steps/s): lm_small_many takes it above 256 systems.
-    auto decode = [&](int q, int &pi, int &pj) {
-        pi = 0; pj = 1;
-        if (q < npairs) {
-            int i = 0;
-            while ((i + 1) * (2 * n - i - 2) / 2 <= q) ++i;
-            pi = i;
-            pj = i + 1 + (q - i * (2 * n - i - 1) / 2);
-        }
-    };
+    // (`decode` and `pair` are local lambdas around the frame's functions, not direct calls: the form in which this kernel's code
+    // stays instruction for instruction what it was, profiles/small_frame_refactor.md)
+    auto decode = [&](int q, int &pi, int &pj) { small_decode<const int &>(q, n, npairs, pi, pj); };
     int pi0, pj0, pi1 = 0, pj1 = 1;
     decode(tid, pi0, pj0);
     if constexpr (TWO) decode(tid + kSmallThreads2, pi1, pj1);
@@ -142,62 +110,8 @@ __global__ void __launch_bounds__(TWO ? kSmallThreads2 : kSmallThreads) k_lm_sma
     const bool live1 = TWO && tid + kSmallThreads2 < npairs && !(wg_flags & 1);
     __syncthreads();
 
-    // Every thread runs the pair arithmetic: straight-line code, so the scheduler interleaves it with the predictor's
-    // position chain (sum1) instead of executing one exec-masked region after the other. The wrapper-free sqrt /
-    // reciprocal sequences run first and unconditionally; the range test that validates them (pair_term.h) is decided
-    // behind them, where the branch no longer stalls the wave, and an out-of-range operand anywhere in the wave redoes
-    // the term in the full IEEE form.
-    // `before_branch()` runs between the wrapper-free results and the (rare, wave-uniform) branch that redoes them in the full
-    // IEEE form: the owner waves pin the predictor's position chain there, so that it is emitted in the SAME block as the
-    // sequences and fills their issue gaps; without it the compiler places the chain behind the stores (round 5, read off the ISA).
     auto pair = [&](const double4 &vi, const double4 &vj, const double4 &wi, const double4 &wj, auto &&before_branch) {
-        const double dx = vj.x - vi.x, dy = vj.y - vi.y, dz = vj.z - vi.z;
-        const double n2 = dx * dx + dy * dy + dz * dz;
-        double ex = 0.0, ey = 0.0, ez = 0.0, m2 = 1.0;
-        if constexpr (TWO) { ex = wj.x - wi.x; ey = wj.y - wi.y; ez = wj.z - wi.z; m2 = ex * ex + ey * ey + ez * ez; }
-        double ax, ay, az, bx, by, bz, cx = 0.0, cy = 0.0, cz = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
-        {
-            // (TWO: the compiler emits the two reciprocal-cube sequences one after the other; writing them stage by stage with the
-            // order pinned, as pair_finish_staged does for the workgroup kernel, was measured: no change, 0.87 us either way)
-            const PairDen den = pair_den<true>(n2);
-            pair_apply<true>(den, dx, dy, dz, vj.w, ax, ay, az);
-            pair_apply<true>(den, -dx, -dy, -dz, vi.w, bx, by, bz);
-            if constexpr (TWO) {
-                const PairDen den1 = pair_den<true>(m2);
-                pair_apply<true>(den1, ex, ey, ez, wj.w, cx, cy, cz);
-                pair_apply<true>(den1, -ex, -ey, -ez, wi.w, gx, gy, gz);
-            }
-        }
-        // the wrapper-free results exist HERE (otherwise the compiler sinks them into the else-side of the branch below)
-        asm volatile("" : "+v"(ax), "+v"(ay), "+v"(az), "+v"(bx), "+v"(by), "+v"(bz));
-        if constexpr (TWO) asm volatile("" : "+v"(cx), "+v"(cy), "+v"(cz), "+v"(gx), "+v"(gy), "+v"(gz));
-        before_branch();
-        if (__builtin_amdgcn_ballot_w64(!(in_range(n2) && (!TWO || in_range(m2)))) != 0) {
-            const PairDen den = pair_den<false>(n2);
-            pair_apply<false>(den, dx, dy, dz, vj.w, ax, ay, az);
-            pair_apply<false>(den, -dx, -dy, -dz, vi.w, bx, by, bz);
-            if constexpr (TWO) {
-                const PairDen den1 = pair_den<false>(m2);
-                pair_apply<false>(den1, ex, ey, ez, wj.w, cx, cy, cz);
-                pair_apply<false>(den1, -ex, -ey, -ez, wi.w, gx, gy, gz);
-            }
-        }
-        if (live0) {
-            U[pi0 * 3 + 0][pj0] = ax;
-            U[pi0 * 3 + 1][pj0] = ay;
-            U[pi0 * 3 + 2][pj0] = az;
-            Lw[pj0 * 3 + 0][pi0] = bx;
-            Lw[pj0 * 3 + 1][pi0] = by;
-            Lw[pj0 * 3 + 2][pi0] = bz;
-        }
-        if (live1) {
-            U[pi1 * 3 + 0][pj1] = cx;
-            U[pi1 * 3 + 1][pj1] = cy;
-            U[pi1 * 3 + 2][pj1] = cz;
-            Lw[pj1 * 3 + 0][pi1] = gx;
-            Lw[pj1 * 3 + 1][pi1] = gy;
-            Lw[pj1 * 3 + 2][pi1] = gz;
-        }
+        small_pair<TWO>(U, Lw, vi, vj, wi, wj, pi0, pj0, pi1, pj1, live0, live1, before_branch);
     };
 
     // ---- predictor (ELM2::advance) of the first step, in the (body, comp) threads
@@ -256,29 +170,9 @@ __global__ void __launch_bounds__(TWO ? kSmallThreads2 : kSmallThreads) k_lm_sma
         SMALL_TICK(1);
         lds_barrier();     // contributions visible
         SMALL_TICK(2);
-        // ---- ordered chains: plain in-order sums over the rows (zeros outside each chain's range; adding +0.0 is exact and
-        // the sums never are -0.0), every read in flight before the first add
+        // ---- ordered chains: plain in-order sums over the rows
         double acc = 0.0;
-        if (chain_thread && !(wg_flags & 2)) {
-            const double *row = half ? &U[chain][0] : &Lw[chain][0];
-            auto sum_blocks = [&](auto nb) {
-                constexpr int NB = decltype(nb)::value;
-                // (the optimiser hoists the common first eight reads and two adds of the two row lengths in front of the branch and
-                // issues the long row's other eight reads behind sixteen adds. Forcing all sixteen reads in front of the first add
-                // was SLOWER -- row sums 610 -> 677 ticks: a lone wave's ds_read_b128 costs it ~12 issue cycles each and overlaps
-                // nothing of its own, profiles/r02_chain2_ubench.txt -- so the accident stays; round 5)
-                double2 r[8 * NB];
-#pragma unroll
-                for (int k = 0; k < 8 * NB; ++k) r[k] = *reinterpret_cast<const double2 *>(row + 2 * k);
-#pragma unroll
-                for (int k = 0; k < 8 * NB; ++k) {
-                    acc = acc + r[k].x;
-                    acc = acc + r[k].y;
-                }
-            };
-            if (nrow == 16) sum_blocks(std::integral_constant<int, 1>{});
-            else sum_blocks(std::integral_constant<int, 2>{});
-        }
+        if (chain_thread && !(wg_flags & 2)) acc = small_row_sum(half ? &U[chain][0] : &Lw[chain][0], nrow);
         // the partner half sits in the adjacent lane: a DPP quad permutation, not an LDS round trip (ds_bpermute)
         const double other = dpp_xor1(acc);
         if constexpr (EPH_SMALL_ACCOUNT) asm volatile("" :: "v"(other));
@@ -343,11 +237,10 @@ __global__ void __launch_bounds__(TWO ? kSmallThreads2 : kSmallThreads) k_lm_sma
 #endif
 
     if (owner) {
-        const int cur = (int)(((long long)a.cur - nsteps % L + L) % L);   // slot of the newest level after nsteps
+        const int cur = small_newest_slot<L>(a.cur, nsteps);
 #pragma unroll
-        for (int p = 0; p < L; ++p) {                     // register p holds level (newest - j), j = (p - rot) mod L
-            const int j = (p - rot + L) % L;
-            const int slot = (cur + j) % L;
+        for (int p = 0; p < L; ++p) {
+            const int slot = (cur + small_level<L>(p, rot)) % L;
             a.Y[slot * lvl + off] = yv[p];
             a.A[slot * lvl + off] = av[p];
         }

@@ -532,6 +532,7 @@ int debug_quot(hipStream_t s, int64_t n, const double *x, const double *a, doubl
 // aggregate would be emitted for the device as well, where host functions do not exist.
 const PairKernels *pair_table() {
     static const PairKernels t = {accel_wave,   accel_wg,     lm_step_wave, lm_step_wg,         lm_persistent, lm_small,       lm_small_many,
+                                  lm_double_small,
                                   lm_step_fast, craft_launch, debug_inv_r3, debug_inv_r3_sweep, debug_quot,    debug_wg_cycles, kPairVariant};
     return &t;
 }

@@ -116,6 +116,20 @@ def test_sizes_where_the_kernel_or_the_padding_changes(gpu, n):
         assert_state(g, want[18], 18, (n, path))
 
 
+@pytest.mark.parametrize("n", [16, 17])
+def test_row_lengths_and_a_ring_write_back_in_mid_rotation(gpu, n):
+    """Stormer13 (L = 13). 16 bodies: rows of 16; 17 bodies: rows of 32 with fifteen zeros of padding, and the owner threads
+    spill into a second wave. After the 13 start-up steps ONE launch of 31 steps: two full ring rotations and five steps, so the
+    write-back runs at a rotation that is neither 0 nor L - 1."""
+    from ephemeris_explorer_amd.workloads import plummer
+    pos, vel, mu = plummer(n)
+    h = 1.0 / 1024.0
+    g = gpu.NBodyIntegration(pos, vel, mu, 0.0, h, "Stormer13", compensated=True)
+    g.advance(13)
+    g.advance(31)
+    assert_state(g, oracle_after(pos, vel, mu, 0.0, h, "Stormer13", 44), 44, ("Stormer13", n))
+
+
 def test_split_advances_clones_and_a_plain_neighbour(gpu, full):
     s = full
     args = (s.pos, s.vel, s.mu, s.epoch, s.dt, "QuinlanTremaine12")
