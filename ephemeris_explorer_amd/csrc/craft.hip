@@ -213,7 +213,7 @@ int eph::craft_sort(eph_craft_batch *b, bool knot0_to_lanes) {
     StreamIdleOnExit idle(b->stream);                  // (declared after tau: a failed allocation below leaves with k_craft_tau done)
     EPH_LAUNCH("k_craft_tau", k_craft_tau, dim3((unsigned)((n + 255) / 256)), dim3(256), b->stream, n, b->eph->n_bodies, b->eph->bodies.p,
                b->eph->coeffs.p, b->time.p, b->y.p, tau.p);
-    if ((st = b->perm.alloc(n4)) || (st = b->slot_of.alloc(n4))) return st;
+    if ((st = alloc_buffers(b, BatchDims{n, 0, 0, 0, 0, 0}, [](BufGroup g) { return g == BufGroup::deal; }))) return st;   // perm, slot_of: n4 each
     PinnedStage stage(2 * n4 * sizeof(int));
     if (stage.status()) return stage.status();
     const unsigned cgrid = (unsigned)std::min<size_t>((n4 / 4 + 255) / 256, 4096);
@@ -341,13 +341,15 @@ int eph::burn_erkn_check(long long n, const int64_t *burn_offset, const int32_t 
     return EPH_OK;
 }
 
-template <typename T>
-static int clone_buf(const DevBuf<T> &src, DevBuf<T> &dst, hipStream_t s) {
-    if (!src.p) return EPH_OK;
-    int st = dst.alloc(src.count);
-    if (st) return st;
-    hipError_t e = hipMemcpyAsync(dst.p, src.p, sizeof(T) * src.count, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) { set_last_error("hipMemcpyAsync (clone)", e); return EPH_ERR_HIP; }
+int eph::craft_batch_shell(const eph_craft_batch &model, long long n, int max_knots, std::unique_ptr<eph_craft_batch> &out) {
+    out.reset(new eph_craft_batch());                                 // (a failure below: it leaves with the caller's pointer)
+    eph_craft_batch *b = out.get();
+    b->pv = model.pv; b->eph = model.eph; b->device = model.device; b->rk = model.rk; b->params = model.params; b->events = model.events;
+    b->max_tr = model.max_tr; b->max_ap = model.max_ap; b->retry = model.retry; b->body_order = model.body_order;
+    b->heterogeneous = model.heterogeneous; b->n = n; b->max_knots = max_knots;
+    EPH_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    EPH_HIP(hipEventCreate(&b->ev0));
+    EPH_HIP(hipEventCreate(&b->ev1));
     return EPH_OK;
 }
 
@@ -366,19 +368,13 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
         int st = burn_csr_check(n_craft, burn_offset, burn_start, burn_end, burn_acc, burn_ref, e->n_bodies, nullptr, true);
         if (st || (st = check_device())) return st;
         std::shared_lock<std::shared_mutex> table_lock(e->mu);       // (the deal to the lanes reads the table)
-        std::unique_ptr<eph_craft_batch> b(new eph_craft_batch());
-        if (!find_erk(method, &b->rk) || !b->rk.has_embedded) return EPH_ERR_BAD_ARGUMENT;
-        if (b->rk.nystrom == 2 && (st = burn_erkn_check(n_craft, burn_offset, burn_ref, nullptr))) return st;
-        b->pv = default_pair_variant();
-        b->eph = e;
-        b->n = n_craft;
-        b->max_knots = max_knots;
-        b->params = *params;
-        b->device = e->device;
-        EPH_HIP(hipSetDevice(b->device));
-        EPH_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-        EPH_HIP(hipEventCreate(&b->ev0));
-        EPH_HIP(hipEventCreate(&b->ev1));
+        eph_craft_batch model;                                       // the settings a batch carries, from the arguments
+        if (!find_erk(method, &model.rk) || !model.rk.has_embedded) return EPH_ERR_BAD_ARGUMENT;
+        if (model.rk.nystrom == 2 && (st = burn_erkn_check(n_craft, burn_offset, burn_ref, nullptr))) return st;
+        model.pv = default_pair_variant(); model.eph = e; model.params = *params; model.device = e->device;
+        EPH_HIP(hipSetDevice(model.device));
+        std::unique_ptr<eph_craft_batch> b;
+        if ((st = craft_batch_shell(model, n_craft, max_knots, b))) return st;
         const long long n = n_craft;
         // Timeline::new per craft  spacecraft.rs:129-152
         std::vector<long long> seg_off(n + 1, 0);
@@ -395,16 +391,7 @@ int32_t eph_craft_batch_create(const eph_ephemeris *e, int64_t n_craft, const do
             cur[i] = idx;
         }
         seg_off[n] = (long long)segs.size();
-        const size_t nn = (size_t)std::max<long long>(n, 1);
-        if ((st = b->time.alloc(nn)) || (st = b->y.alloc(6 * nn)) || (st = b->next_h.alloc(nn)) ||
-            (st = b->klast.alloc(6 * nn)) || (st = b->kfirst.alloc(6 * nn)) || (st = b->last_knot.alloc(nn)) || (st = b->n_attempts.alloc(nn)) ||
-            (st = b->rk_i.alloc(nn)) || (st = b->steps.alloc(nn)) || (st = b->cur_seg.alloc(nn)) ||
-            (st = b->status.alloc(nn)) || (st = b->nknots.alloc(nn)) || (st = b->seg_off.alloc(n + 1)) ||
-            (st = b->segs.alloc(std::max<size_t>(segs.size(), 1))) || (st = b->knot_t.alloc(nn * max_knots)) ||
-            (st = b->knot_y.alloc(6 * nn * max_knots)) || (st = b->rk_dev.alloc(1)) || (st = b->queue.alloc(1)) ||
-            (st = b->summary.alloc(nn)) ||             // (here, not at the first eph_craft_batch_summary: keeps hipMalloc out of a sweep)
-            (st = b->t_start.alloc(nn)))
-            return st;
+        if ((st = alloc_state(b.get(), n, max_knots, segs.size()))) return st;
         EPH_HIP(hipMemcpy(b->rk_dev.p, &b->rk, sizeof(ErkCoeffs), hipMemcpyHostToDevice));
         if (n > 0) {
             std::vector<double> ysoa(6 * n), hs(n, params->h_init);
@@ -669,36 +656,11 @@ int32_t eph_craft_batch_clone(eph_craft_batch *b, eph_craft_batch **out) {
         *out = nullptr;
         EPH_HIP(hipSetDevice(b->device));
         EPH_HIP(hipStreamSynchronize(b->stream));
-        std::unique_ptr<eph_craft_batch> c(new eph_craft_batch());
-        c->pv = b->pv; c->eph = b->eph; c->device = b->device; c->n = b->n; c->max_knots = b->max_knots; c->rk = b->rk;
-        c->params = b->params; c->events = b->events; c->max_tr = b->max_tr; c->max_ap = b->max_ap;
-        c->heterogeneous = b->heterogeneous;
-        c->retry = b->retry; c->body_order = b->body_order;
-        EPH_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        EPH_HIP(hipEventCreate(&c->ev0));
-        EPH_HIP(hipEventCreate(&c->ev1));
-        hipStream_t s = c->stream;
+        std::unique_ptr<eph_craft_batch> c;
         int st;
-        if ((st = clone_buf(b->time, c->time, s)) || (st = clone_buf(b->y, c->y, s)) || (st = clone_buf(b->next_h, c->next_h, s)) ||
-            (st = clone_buf(b->klast, c->klast, s)) || (st = clone_buf(b->kfirst, c->kfirst, s)) || (st = clone_buf(b->last_knot, c->last_knot, s)) ||
-            (st = clone_buf(b->knot_t, c->knot_t, s)) || (st = clone_buf(b->knot_y, c->knot_y, s)) ||
-            (st = clone_buf(b->n_attempts, c->n_attempts, s)) || (st = clone_buf(b->rk_i, c->rk_i, s)) ||
-            (st = clone_buf(b->steps, c->steps, s)) || (st = clone_buf(b->cur_seg, c->cur_seg, s)) ||
-            (st = clone_buf(b->status, c->status, s)) || (st = clone_buf(b->nknots, c->nknots, s)) ||
-            (st = clone_buf(b->seg_off, c->seg_off, s)) || (st = clone_buf(b->segs, c->segs, s)) ||
-            (st = clone_buf(b->rk_dev, c->rk_dev, s)) || (st = clone_buf(b->soi, c->soi, s)) ||
-            (st = clone_buf(b->tr_time, c->tr_time, s)) || (st = clone_buf(b->ap_time, c->ap_time, s)) ||
-            (st = clone_buf(b->ap_dist, c->ap_dist, s)) || (st = clone_buf(b->ev_seg, c->ev_seg, s)) ||
-            (st = clone_buf(b->ntr, c->ntr, s)) || (st = clone_buf(b->nap, c->nap, s)) ||
-            (st = clone_buf(b->ev_status, c->ev_status, s)) || (st = clone_buf(b->tr_body, c->tr_body, s)) ||
-            (st = clone_buf(b->ap_body, c->ap_body, s)) || (st = clone_buf(b->ap_kind, c->ap_kind, s)) ||
-            (st = clone_buf(b->perm, c->perm, s)) || (st = clone_buf(b->slot_of, c->slot_of, s)) || (st = clone_buf(b->bodies_ordered, c->bodies_ordered, s)) || (st = clone_buf(b->body_order_dev, c->body_order_dev, s)) || (st = c->queue.alloc(1)) ||
-            (st = clone_buf(b->t_start, c->t_start, s)))
-            return st;
-        c->h_slot = b->h_slot;
-        c->h_seg_off = b->h_seg_off;
-        c->h_segs = b->h_segs;
-        EPH_HIP(hipStreamSynchronize(s));
+        if ((st = craft_batch_shell(*b, b->n, b->max_knots, c)) || (st = copy_buffers(b, c.get(), c->stream))) return st;
+        c->h_slot = b->h_slot; c->h_seg_off = b->h_seg_off; c->h_segs = b->h_segs;
+        EPH_HIP(hipStreamSynchronize(c->stream));
         *out = c.release();
         return EPH_OK;
     EPH_GUARD_END

@@ -1,6 +1,6 @@
-// craft_batch.h -- struct eph_craft_batch (craft.hip owns it) and what the units that read or restart a batch on the device share
-// (craft_events.hip, craft_eval.hip, craft_plot.hip, craft_separation.hip, craft_restart.hip): the view of the knot slabs a kernel
-// takes, the request-to-lane map, the pass timing of the EPH_TRACE_* variables, and the calls that cross between the units.
+// craft_batch.h -- struct eph_craft_batch (craft.hip owns it) and what the units that build, read or restart a batch share (craft_events,
+// craft_eval, craft_plot, craft_markers, craft_separation, craft_restart, craft_gather .hip): the statement of its device buffers with the
+// walks built on it, the knot slabs as a kernel takes them, the request-to-lane map, the EPH_TRACE_* pass timing, the calls between units.
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -56,6 +56,66 @@ struct eph_craft_batch {
 };
 
 namespace eph {
+// ---- The batch's device buffers, stated once ------------------------------------------------------------------------------------
+// for_each_buffer names every DevBuf member of eph_craft_batch with its shape; allocation and eph_craft_batch_clone are walks over it. A NEW
+// BUFFER IS ADDED TO THE STRUCT AND TO THAT LIST AND NOWHERE ELSE: beyond them a name appears only where a kernel argument block is filled,
+// where a reader copies the buffer out and where its contents are initialised.
+enum class BufGroup { craft, timeline, events, deal, body_order, single, scratch };
+// rows x one element per: craft, craft and knot / transition / apsis (the slabs, [depth][rows][craft]), craft + 1, segment, body, lane, batch
+enum class BufExtent { craft, knots, transitions, apsides, craft_plus_one, segments, bodies, lanes, one };
+enum class BufClone { copy, fresh, first_use };                              // copied | allocated, contents not carried | left empty
+struct BufShape { BufGroup group; BufExtent extent; int rows = 1; BufClone clone = BufClone::copy; };
+struct BatchDims { long long n; int max_knots; size_t n_segs; int max_tr, max_ap, n_bodies; };
+inline size_t buffer_count(const BufShape &s, const BatchDims &d) {
+    const size_t n = (size_t)d.n, per_craft = (size_t)s.rows * std::max<size_t>(n, 1);
+    const size_t count[] = {per_craft, per_craft * std::max(d.max_knots, 1), per_craft * std::max(d.max_tr, 1), per_craft * std::max(d.max_ap, 1), n + 1,
+                            std::max<size_t>(d.n_segs, 1), (size_t)std::max(d.n_bodies, 1), (n + 3) & ~(size_t)3, 1};   // in BufExtent's order
+    return count[(int)s.extent];                                         // (lanes: whole 16-byte granules, craft_sort's k_copy16)
+}
+template <typename F>            // f(pointer to the member, its shape) for every buffer, until one returns a status other than EPH_OK: that status
+int for_each_buffer(F &&f) {
+    using B = eph_craft_batch; using G = BufGroup; using E = BufExtent;
+    constexpr BufShape craft1{G::craft, E::craft}, craft6{G::craft, E::craft, 6}, knots1{G::craft, E::knots}, knots6{G::craft, E::knots, 6};
+    constexpr BufShape offsets{G::timeline, E::craft_plus_one}, segments{G::timeline, E::segments}, deal{G::deal, E::lanes};
+    constexpr BufShape radii{G::events, E::bodies}, event1{G::events, E::craft}, tr{G::events, E::transitions}, ap{G::events, E::apsides};
+    constexpr BufShape order{G::body_order, E::bodies}, single{G::single, E::one};
+    constexpr BufShape counter{G::single, E::one, 1, BufClone::fresh};            // queue: reset before every sweep that uses it
+    constexpr BufShape scratch{G::scratch, E::craft, 1, BufClone::first_use};     // summary: never copied
+    int st;
+    (void)((st = f(&B::time, craft1)) || (st = f(&B::y, craft6)) || (st = f(&B::next_h, craft1)) || (st = f(&B::klast, craft6)) || (st = f(&B::kfirst, craft6)) ||
+        (st = f(&B::last_knot, craft1)) || (st = f(&B::t_start, craft1)) || (st = f(&B::n_attempts, craft1)) || (st = f(&B::rk_i, craft1)) ||
+        (st = f(&B::steps, craft1)) || (st = f(&B::cur_seg, craft1)) || (st = f(&B::status, craft1)) || (st = f(&B::nknots, craft1)) ||
+        (st = f(&B::knot_t, knots1)) || (st = f(&B::knot_y, knots6)) || (st = f(&B::seg_off, offsets)) || (st = f(&B::segs, segments)) ||
+        (st = f(&B::soi, radii)) || (st = f(&B::ev_seg, event1)) || (st = f(&B::ntr, event1)) || (st = f(&B::nap, event1)) || (st = f(&B::ev_status, event1)) ||
+        (st = f(&B::tr_time, tr)) || (st = f(&B::tr_body, tr)) || (st = f(&B::ap_time, ap)) || (st = f(&B::ap_dist, ap)) || (st = f(&B::ap_body, ap)) ||
+        (st = f(&B::ap_kind, ap)) || (st = f(&B::perm, deal)) || (st = f(&B::slot_of, deal)) || (st = f(&B::bodies_ordered, order)) ||
+        (st = f(&B::body_order_dev, order)) || (st = f(&B::rk_dev, single)) || (st = f(&B::queue, counter)) || (st = f(&B::summary, scratch)));
+    return st;
+}
+template <typename Keep>                                               // the buffers of the groups `keep` says yes to, at d's element counts
+int alloc_buffers(eph_craft_batch *b, const BatchDims &d, Keep &&keep) {
+    return for_each_buffer([&](auto member, const BufShape &s) { return keep(s.group) ? (b->*member).alloc(buffer_count(s, d)) : EPH_OK; });
+}
+// what create and gather allocate before the contents arrive: per-craft state, knot slabs, the timeline CSR of n_segs segments, rk_dev,
+// queue and summary (here, not at the first eph_craft_batch_summary: keeps hipMalloc out of a sweep)
+inline int alloc_state(eph_craft_batch *b, long long n, int max_knots, size_t n_segs) {
+    const auto mine = [](BufGroup g) { return g != BufGroup::events && g != BufGroup::deal && g != BufGroup::body_order; };
+    return alloc_buffers(b, BatchDims{n, max_knots, n_segs, 0, 0, 0}, mine);
+}
+// what enable_events and gather allocate: the event state, the event slabs and the sphere radii of b
+inline int alloc_events(eph_craft_batch *b, int max_tr, int max_ap) {
+    return alloc_buffers(b, BatchDims{b->n, 0, 0, max_tr, max_ap, b->eph->n_bodies}, [](BufGroup g) { return g == BufGroup::events; });
+}
+// eph_craft_batch_clone's walk: every buffer `src` has, by src's count, on stream `s`; the caller synchronises
+inline int copy_buffers(const eph_craft_batch *src, eph_craft_batch *dst, hipStream_t s) {
+    return for_each_buffer([&](auto m, const BufShape &sh) {
+        return sh.clone == BufClone::copy ? copy_buf(src->*m, dst->*m, s) : sh.clone == BufClone::fresh ? (dst->*m).alloc((src->*m).count) : (int)EPH_OK;
+    });
+}
+// craft.hip: a new batch of n craft with its stream and two events on model's device (which is current) and model's settings -- pv, eph,
+// device, rk, params, events, max_tr, max_ap, retry, body_order, heterogeneous -- and no buffer
+int craft_batch_shell(const eph_craft_batch &model, long long n, int max_knots, std::unique_ptr<eph_craft_batch> &out);
+
 bool craft_wave_form(long long n_craft);                  // craft.hip: one wave per craft (few spacecraft) or one thread
 int craft_events_search(eph_craft_batch *b, hipStream_t s);   // craft_events.hip: the event search on the steps a sweep just took
 // craft.hip: the creation rule's deal of a thread-per-craft batch to the lanes from its current time and state (perm, slot_of, h_slot;

@@ -234,13 +234,7 @@ int32_t eph_craft_batch_enable_events(eph_craft_batch *b, const double *soi_radi
         EPH_HIP(hipSetDevice(b->device));
         const size_t nn = (size_t)std::max<long long>(b->n, 1);
         const int nb = b->eph->n_bodies;
-        int st;
-        if ((st = b->soi.alloc(std::max(nb, 1))) || (st = b->ev_seg.alloc(nn)) || (st = b->ntr.alloc(nn)) ||
-            (st = b->nap.alloc(nn)) || (st = b->ev_status.alloc(nn)) || (st = b->tr_time.alloc(nn * max_transitions)) ||
-            (st = b->tr_body.alloc(nn * max_transitions)) || (st = b->ap_time.alloc(nn * max_apsides)) ||
-            (st = b->ap_dist.alloc(nn * max_apsides)) || (st = b->ap_body.alloc(nn * max_apsides)) ||
-            (st = b->ap_kind.alloc(nn * max_apsides)))
-            return st;
+        if (const int st = alloc_events(b, max_transitions, max_apsides)) return st;
         if (nb) EPH_HIP(hipMemcpy(b->soi.p, soi_radius, sizeof(double) * nb, hipMemcpyHostToDevice));
         EPH_HIP(hipMemset(b->ev_seg.p, 0xff, sizeof(int) * nn));       // -1: new_solution pending
         EPH_HIP(hipMemset(b->ntr.p, 0, sizeof(int) * nn));

@@ -212,15 +212,6 @@ static int gather_slabs(GatherWork &w) {
     return w.trace_slabs.copy_end();
 }
 
-template <typename T>
-static int copy_buf(const DevBuf<T> &src, DevBuf<T> &dst, hipStream_t s) {
-    if (!src.p) return EPH_OK;
-    const int st = dst.alloc(src.count);
-    if (st) return st;
-    EPH_HIP(hipMemcpyAsync(dst.p, src.p, sizeof(T) * src.count, hipMemcpyDeviceToDevice, s));
-    return EPH_OK;
-}
-
 }  // namespace eph
 
 using namespace eph;
@@ -270,38 +261,23 @@ int32_t eph_craft_batch_gather(int32_t n_sources, eph_craft_batch *const *source
         }
         // ---- built aside in a fresh batch; `out` is written on success only ----
         std::shared_lock<std::shared_mutex> table_lock(b0->eph->mu);       // (the deal to the lanes reads the table)
-        std::unique_ptr<eph_craft_batch> c(new eph_craft_batch());
-        c->pv = b0->pv; c->eph = b0->eph; c->device = b0->device; c->n = n_out; c->max_knots = plan.max_knots; c->rk = b0->rk;
-        c->params = b0->params; c->events = plan.events; c->max_tr = plan.max_tr; c->max_ap = plan.max_ap;
-        c->retry = plan.retry; c->body_order = b0->body_order;
+        std::unique_ptr<eph_craft_batch> c;
+        if ((st = craft_batch_shell(*b0, n_out, plan.max_knots, c))) return st;       // source 0's settings, but the plan's:
+        c->events = plan.events; c->max_tr = plan.max_tr; c->max_ap = plan.max_ap; c->retry = plan.retry;
         // `heterogeneous` only picks the queue form for an undealt batch. Set conservatively, not recomputed: true when a source says
         // so of its own craft or when the craft come from several batches, whose time scales nobody has compared.
         c->heterogeneous = n_sources > 1;
         for (int s = 0; s < n_sources; ++s) c->heterogeneous = c->heterogeneous || sources[s]->heterogeneous;
-        EPH_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        EPH_HIP(hipEventCreate(&c->ev0));
-        EPH_HIP(hipEventCreate(&c->ev1));
-        const size_t n = (size_t)n_out, nn = std::max<size_t>(n, 1), mk = (size_t)std::max(plan.max_knots, 1);
+        const size_t n = (size_t)n_out;
         GatherWork w(c.get(), sources, &plan);
-        if ((st = c->time.alloc(nn)) || (st = c->y.alloc(6 * nn)) || (st = c->next_h.alloc(nn)) || (st = c->klast.alloc(6 * nn)) ||
-            (st = c->kfirst.alloc(6 * nn)) || (st = c->last_knot.alloc(nn)) || (st = c->n_attempts.alloc(nn)) || (st = c->rk_i.alloc(nn)) ||
-            (st = c->steps.alloc(nn)) || (st = c->cur_seg.alloc(nn)) || (st = c->status.alloc(nn)) || (st = c->nknots.alloc(nn)) ||
-            (st = c->seg_off.alloc(n + 1)) || (st = c->segs.alloc(std::max<size_t>(plan.segs.size(), 1))) || (st = c->knot_t.alloc(nn * mk)) ||
-            (st = c->knot_y.alloc(6 * nn * mk)) || (st = c->rk_dev.alloc(1)) || (st = c->queue.alloc(1)) || (st = c->summary.alloc(nn)) ||
-            (st = c->t_start.alloc(nn)) || (st = w.d_idx.alloc(4 * nn)))
+        if ((st = alloc_state(c.get(), n_out, plan.max_knots, plan.segs.size())) || (st = w.d_idx.alloc(4 * std::max<size_t>(n, 1))) ||
+            (plan.events && (st = alloc_events(c.get(), plan.max_tr, plan.max_ap))))
             return st;
-        if (plan.events) {
-            const size_t mt = (size_t)std::max(plan.max_tr, 1), ma = (size_t)std::max(plan.max_ap, 1);
-            if ((st = c->ev_seg.alloc(nn)) || (st = c->ntr.alloc(nn)) || (st = c->nap.alloc(nn)) || (st = c->ev_status.alloc(nn)) ||
-                (st = c->tr_time.alloc(nn * mt)) || (st = c->tr_body.alloc(nn * mt)) || (st = c->ap_time.alloc(nn * ma)) ||
-                (st = c->ap_dist.alloc(nn * ma)) || (st = c->ap_body.alloc(nn * ma)) || (st = c->ap_kind.alloc(nn * ma)))
-                return st;
-        }
         {
             StreamIdleOnExit idle(c->stream);
-            if ((st = copy_buf(b0->soi, c->soi, c->stream)) || (st = copy_buf(b0->bodies_ordered, c->bodies_ordered, c->stream)) ||
-                (st = copy_buf(b0->body_order_dev, c->body_order_dev, c->stream)))
-                return st;
+            if (plan.events) EPH_HIP(hipMemcpyAsync(c->soi.p, b0->soi.p, sizeof(double) * c->soi.count, hipMemcpyDeviceToDevice, c->stream));
+            if ((st = copy_buf(b0->bodies_ordered, c->bodies_ordered, c->stream))) return st;
+            if ((st = copy_buf(b0->body_order_dev, c->body_order_dev, c->stream))) return st;
             EPH_HIP(hipMemcpy(c->rk_dev.p, &c->rk, sizeof(ErkCoeffs), hipMemcpyHostToDevice));
             EPH_HIP(hipMemcpy(c->seg_off.p, plan.seg_off.data(), sizeof(long long) * (n + 1), hipMemcpyHostToDevice));
             if (!plan.segs.empty())

@@ -101,6 +101,14 @@ int upload(DevBuf<T> &dst, const T *src, size_t count) {
     if (count) EPH_HIP(hipMemcpy(dst.p, src, sizeof(T) * count, hipMemcpyHostToDevice));
     return EPH_OK;
 }
+// a fresh allocation of src's size with src's contents, copied on stream `s` (the caller synchronises); nothing for an empty src
+template <typename T>
+int copy_buf(const DevBuf<T> &src, DevBuf<T> &dst, hipStream_t s) {
+    if (!src.p) return EPH_OK;
+    if (const int st = dst.alloc(src.count)) return st;
+    EPH_HIP(hipMemcpyAsync(dst.p, src.p, sizeof(T) * src.count, hipMemcpyDeviceToDevice, s));
+    return EPH_OK;
+}
 
 // Direct-write transport of the exchange step (peer.hip): every rank owns a mailbox that its peers map through
 // hipIpc and write into; no collective library involved.

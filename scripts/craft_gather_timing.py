@@ -8,8 +8,9 @@ the same run (hipMemcpyAsync of the whole slabs: code the gather does not touch)
           permutation as the identity; it is the uncoalesced worst case on an undealt one (--deal undealt: EPH_CRAFT_SORT=0)
   frame   the app's frame: 8 one-ship batches (the Mars Transfer Ship to 1951-01-01, events on) gathered into one batch, and what one
           plot_segments + plot_markers pass costs on the one batch against eight passes on the eight batches
+  lifecycle  eph_craft_batch_create of the sweep shape's batch and eph_craft_batch_clone of the fresh batch, wall times only
 
-    python scripts/craft_gather_timing.py [--case sweep|frame|both] [--deal dealt|undealt] [--craft N] [--knots K] [--reps R]
+    python scripts/craft_gather_timing.py [--case sweep|frame|both|lifecycle] [--deal dealt|undealt] [--craft N] [--knots K] [--reps R]
                                           [--out FILE.json]
 
 Per the measuring guide: one warm-up call, then the median of R >= 5 calls (min .. max beside it); needed bytes = 56 B per used knot of
@@ -109,6 +110,32 @@ def sweep_case(args):
     return {"shape": {"craft": n, "knots": knots, "slab_bytes": slab_bytes}, "deal": args.deal, "rows": rows}
 
 
+def lifecycle_case(args):
+    """create and clone on their own: the sweep shape's batch created (its knot slabs are allocated, one knot of each craft is
+    written) and that fresh batch cloned (whole slabs), a host clock around each call, one warm-up of each first"""
+    n, knots = args.craft, args.knots
+    rng = np.random.default_rng(20261020)
+    eph = ea.Ephemeris(ea.Solution.from_parts([0.0], [2.0 ** 30], [[np.zeros((2, 3))]]), [MU])
+    r = 7000.0 * 8.0 ** rng.random(n)
+    ang = rng.random(n) * 2.0 * np.pi
+    pos = np.stack([r * np.cos(ang), r * np.sin(ang), np.zeros(n)], axis=1)
+    vel = np.stack([-np.sqrt(MU / r) * np.sin(ang), np.sqrt(MU / r) * np.cos(ang), np.zeros(n)], axis=1)
+    params = ea.AdaptiveParams.default(1e-3)
+    wall = {"create": [], "clone": []}
+    for rep in range(args.reps + 1):
+        t0 = time.perf_counter()
+        batch = ea.SpacecraftBatch(eph, 0.0, pos, vel, "Verner87", params, max_knots=knots)
+        t1 = time.perf_counter()
+        c = batch.clone()
+        t2 = time.perf_counter()
+        del c, batch
+        if rep:
+            wall["create"].append((t1 - t0) * 1e3), wall["clone"].append((t2 - t1) * 1e3)
+    row = {"case": "lifecycle", "craft": n, "knots": knots, **{k: spread(v) for k, v in wall.items()}}
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def frame_case(args):
     from craft_markers_timing import system_to
     from ephemeris_explorer_amd.systems import parse_epoch, soi_parents, soi_radii
@@ -155,7 +182,7 @@ def frame_case(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=("sweep", "frame", "both"), default="both")
+    ap.add_argument("--case", choices=("sweep", "frame", "both", "lifecycle"), default="both")
     ap.add_argument("--deal", choices=("dealt", "undealt"), default="dealt",
                     help="undealt: EPH_CRAFT_SORT=0, knot columns in craft order on both sides (the library reads it once per process)")
     ap.add_argument("--craft", type=int, default=262144)
@@ -173,6 +200,8 @@ def main():
         result["sweep"] = sweep_case(args)
     if args.case in ("frame", "both"):
         result["frame"] = frame_case(args)
+    if args.case == "lifecycle":
+        result["lifecycle"] = lifecycle_case(args)
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")

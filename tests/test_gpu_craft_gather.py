@@ -11,7 +11,9 @@ oracle alone (gather_preconditions; tests/test_craft_gather_scene.py asserts the
 Wave forms in this process; the three thread forms (k_craft_propagate dealt, undealt, k_craft_queue) in one child process each (the
 form is read once per process; this file run as a script), every child under its own timeout; after a child that died of a signal or
 ran into its timeout the remaining children are not started. The commit rule runs in a child on the test-hooks library
-(eph_debug_fail_alloc: a host function returns an error code, no fault is provoked)."""
+(eph_debug_fail_alloc: a host function returns an error code, no fault is provoked), and so do its three siblings for the calls that
+share the gather's statement of the batch's buffers (csrc/craft_batch.h): create, clone and enable_events. Each of the four also asserts
+how many device allocations its call makes (ALLOCATIONS): a buffer dropped from, or added to, a walk over the statement moves a count."""
 import ctypes as C
 import os
 import subprocess
@@ -299,6 +301,16 @@ def test_failed_craft_resume_in_the_gathered_batch(gpu, pieces, method, rearm_be
     """the craft fail at the table's end (EvalFailed: for an FSAL pair k[0] and k[S-1] are swapped and the failing stage zeroed); they
     are gathered, permuted, one craft twice; the table is appended; retry_failed (on the gathered batch, or on the source before the
     gather: the flag is carried) and propagate: bit-equal to the oracle's resumed run"""
+    failed_craft_resume(gpu, pieces, method, rearm_before, [2, 0, 3, 1, 0], lambda batch, order: batch.select(order))
+
+
+@pytest.mark.parametrize("rearm_before", [False, True])
+def test_failed_craft_resume_in_a_clone(gpu, pieces, rearm_before):
+    """the same through eph_craft_batch_clone, on the FSAL pair: klast, kfirst and the retry flag are read through a plain copy"""
+    failed_craft_resume(gpu, pieces, FSAL_METHOD, rearm_before, [0, 1, 2, 3], lambda batch, order: batch.clone())
+
+
+def failed_craft_resume(gpu, pieces, method, rearm_before, order, make):
     s, pcs = pieces
     ship = _ship()
     eph, olive = _live(gpu, s, pcs[0])
@@ -311,10 +323,9 @@ def test_failed_craft_resume_in_the_gathered_batch(gpu, pieces, method, rearm_be
     for i, c in enumerate(crafts):
         assert c.step_to(end) == orc.EVAL_FAILED
         _compare(batch, i, c, gpu.EVAL_FAILED, f"{method} craft {i}: the table's end")
-    order = [2, 0, 3, 1, 0]
     if rearm_before:
         batch.retry_failed()
-    g = batch.select(order)
+    g = make(batch, order)
     for i, o in enumerate(order):
         _compare(g, i, crafts[o], gpu.EVAL_FAILED, f"{method} gathered craft {i}")
     both = [g, batch]                                     # the source is given the same calls, independently
@@ -552,11 +563,40 @@ def test_sources_that_disagree_are_refused(gpu):
 
 
 # ---- commit rule ---------------------------------------------------------------------------------------------------------------------
+# Device allocations each call makes for the batch its case builds: the number of k at which the call fails before it first succeeds.
+# Every buffer of the batch is one of them, so a buffer dropped from (or added to) a call moves its count.
+ALLOCATIONS = {"commit-rule": 35,      # gather (no body order set): 20 of the state, the index scratch, 10 event slabs, soi, 3 of the deal
+               "clone-rule": 34,       # every buffer of the source but `summary`: 33 copied, the queue fresh
+               "create-rule": 23,      # 20 of the state, 3 of the deal
+               "events-rule": 11}      # soi, 4 per-craft event arrays, 6 event slabs
+
+
+def failing_allocations(ea, H, call, on_failure):
+    """call() -> (status, *out, text) with the k-th allocation failing, k = 1, 2, ...: every failure is ERR_OUT_OF_MEMORY with the injected
+    text and a countdown that has disarmed itself, then on_failure(k, *out) -> (failures before the first success, that success's *out)"""
+    for k in range(1, 200):
+        assert H.fail_alloc(k) == 0
+        st, out, text = call()
+        left = H.fail_alloc(0)
+        if st == ea.OK:
+            return k - 1, out
+        assert st == ea.ERR_OUT_OF_MEMORY and "injected allocation failure" in text, (k, st, out, text)
+        assert left == 0, f"k = {k}: the countdown is still armed"
+        on_failure(k, out)
+    raise AssertionError("no success by k = 199")
+
+
+def unchanged(batches, before, what):
+    for s, b in enumerate(batches):
+        now = readable(b)
+        for i in range(b.n):
+            same_craft(now, i, before[s], i, f"{what}: source {s}")
+
+
 def commit_rule_case(ea):
     """fail the k-th allocation for every k the call makes: an error status, *out NULL, the sources bit-equal to a snapshot; then the call
     succeeds and is correct. Thread form: the deal's own allocations are among them"""
     import hooks
-    H = hooks.load()
     sc, res, lists = gather_preconditions(METHOD)
     end = sc.calls[-1][1]
     eph = ea.Ephemeris(ea.Solution.from_parts(*sc.table), sc.mu)
@@ -568,22 +608,11 @@ def commit_rule_case(ea):
     source_of = rng.integers(0, 2, 132).astype(np.int32)
     craft_of = np.where(source_of == 0, rng.integers(0, 100, 132), rng.integers(0, 36, 132)).astype(np.int64)
     before = [readable(b) for b in srcs]
-    failures = 0
-    for k in range(1, 200):
-        assert H.fail_alloc(k) == 0
-        st, out, text = raw_gather(ea, srcs, source_of, craft_of)
-        left = H.fail_alloc(0)
-        if st == ea.OK:
-            break
-        failures += 1
-        assert st == ea.ERR_OUT_OF_MEMORY and out is None and "injected allocation failure" in text, (k, st, out, text)
-        assert left == 0, f"k = {k}: the countdown is still armed"
-        for s, b in enumerate(srcs):
-            now = readable(b)
-            for i in range(b.n):
-                same_craft(now, i, before[s], i, f"k = {k}: source {s}")
-    else:
-        raise AssertionError("no success by k = 199")
+
+    def failed(k, out):
+        assert out is None, (k, out)
+        unchanged(srcs, before, f"k = {k}")
+    failures, out = failing_allocations(ea, hooks.load(), lambda: raw_gather(ea, srcs, source_of, craft_of), failed)
     assert failures >= 30, failures                                      # every per-craft array, the slabs, the event slabs, the deal
     good = ea.SpacecraftBatch._adopt(C.c_void_p(out), ephemeris=eph, n=len(craft_of), params=srcs[0].params)
     same_as_sources(good, srcs, source_of, craft_of, "after the failures, at the gather")
@@ -594,9 +623,129 @@ def commit_rule_case(ea):
     return failures
 
 
+def swapped_order(sc):
+    """a non-identity body order. Only body 0 of scene T has mass, so the sums keep their bits and the oracle's run stays the reference"""
+    order = np.arange(sc.n_bodies, dtype=np.int32)
+    order[[1, 2]] = order[[2, 1]]
+    return order
+
+
+def full_batch(ea, eph, sc):
+    """the 136 craft as a batch that owns every optional buffer: dealt (thread form), events on, a body order set"""
+    return batch_of(ea, eph, sc, METHOD, np.arange(sc.n)).set_body_order(swapped_order(sc))
+
+
+def attributes_of(b):
+    return {k: v for k, v in vars(b).items() if k not in ("_L", "_h", "_owned")}
+
+
+def clone_rule_case(ea):
+    """eph_craft_batch_clone under the same rule: every failure leaves *out NULL and the source as it was; the first success is the source,
+    and goes on like it and like the oracle"""
+    import hooks
+    sc, res, lists = gather_preconditions(METHOD)
+    end = sc.calls[-1][1]
+    eph = ea.Ephemeris(ea.Solution.from_parts(*sc.table), sc.mu)
+    src = full_batch(ea, eph, sc)
+    src.propagate(0.4 * end)
+    before = [readable(src)]
+
+    def raw_clone():
+        out = C.c_void_p(0x5A5A5A5A)
+        st = ea._lib().eph_craft_batch_clone(src._h, C.byref(out))
+        return st, out.value, ea._lib().eph_last_error().decode()
+
+    def failed(k, out):
+        assert out is None, (k, out)
+        unchanged([src], before, f"k = {k}")
+    failures, out = failing_allocations(ea, hooks.load(), raw_clone, failed)
+    good = ea.SpacecraftBatch._adopt(C.c_void_p(out), **attributes_of(src))
+    everyone = [0] * sc.n, np.arange(sc.n)
+    same_as_sources(good, [src], *everyone, "after the failures, at the clone")
+    for b in (good, src):
+        b.propagate(end)
+    same_as_sources(good, [src], *everyone, "after the failures, at the end")
+    compare_sweep(good, res, "clone after the failures")
+    compare_events(good, lists, "clone after the failures")
+    return failures
+
+
+def create_rule_case(ea):
+    """eph_craft_batch_create under the same rule: `out` is written on success only; the first success, its events enabled, runs like the
+    oracle and like a batch created with no failure injected"""
+    import hooks
+    sc, res, lists = gather_preconditions(METHOD)
+    end = sc.calls[-1][1]
+    eph = ea.Ephemeris(ea.Solution.from_parts(*sc.table), sc.mu)
+    params = params_of(ea, sc)
+    t0, pos, vel = ea._f64(sc.t0), ea._f64(sc.pos).reshape(-1, 3), ea._f64(sc.vel).reshape(-1, 3)
+    untouched = 0x5A5A5A5A
+
+    def raw_create():
+        out = C.c_void_p(untouched)
+        st = ea._lib().eph_craft_batch_create(eph._h, sc.n, ea._p(t0), ea._p(pos), ea._p(vel), METHOD.encode(), C.byref(params),
+                                              *ea._burn_csr(sc.burns, sc.n), int(sc.max_knots), C.byref(out))
+        return st, out.value, ea._lib().eph_last_error().decode()
+
+    def failed(k, out):
+        assert out == untouched, (k, out)
+    failures, out = failing_allocations(ea, hooks.load(), raw_create, failed)
+    good = ea.SpacecraftBatch._adopt(C.c_void_p(out), ephemeris=eph, n=sc.n, params=params)
+    plain = batch_of(ea, eph, sc, METHOD, np.arange(sc.n), events=False)
+    for b in (good, plain):
+        b.enable_events(sc.soi, max_transitions=sc.max_tr, max_apsides=sc.max_ap).set_body_order(swapped_order(sc))
+        b.propagate(end)
+    same_as_sources(good, [plain], [0] * sc.n, np.arange(sc.n), "created after the failures against a plain creation")
+    compare_sweep(good, res, "created after the failures")
+    compare_events(good, lists, "created after the failures")
+    return failures
+
+
+def events_rule_case(ea):
+    """eph_craft_batch_enable_events failing at its k-th allocation leaves a batch on which a second call succeeds, and which then runs
+    bit for bit like a batch whose first call succeeded (and like the oracle)"""
+    import hooks
+    H = hooks.load()
+    sc, res, lists = gather_preconditions(METHOD)
+    end = sc.calls[-1][1]
+    eph = ea.Ephemeris(ea.Solution.from_parts(*sc.table), sc.mu)
+    soi = ea._f64(sc.soi)
+    reference = full_batch(ea, eph, sc)
+    reference.propagate(end)
+    compare_sweep(reference, res, "enabled at once")
+    compare_events(reference, lists, "enabled at once")
+    want = readable(reference)
+    for k in range(1, 200):
+        b = batch_of(ea, eph, sc, METHOD, np.arange(sc.n), events=False).set_body_order(swapped_order(sc))
+        assert H.fail_alloc(k) == 0
+        st = ea._lib().eph_craft_batch_enable_events(b._h, ea._p(soi), int(sc.max_tr), int(sc.max_ap))
+        text, left = ea._lib().eph_last_error().decode(), H.fail_alloc(0)
+        if st == ea.OK:
+            return k - 1
+        assert st == ea.ERR_OUT_OF_MEMORY and "injected allocation failure" in text and left == 0, (k, st, text, left)
+        b.enable_events(sc.soi, max_transitions=sc.max_tr, max_apsides=sc.max_ap)
+        b.propagate(end)
+        got = readable(b)
+        for i in range(b.n):
+            same_craft(got, i, want, i, f"enabled at the second call after a failure at allocation {k}: craft {i}")
+    raise AssertionError("no success by k = 199")
+
+
+RULE_CASES = {"commit-rule": commit_rule_case, "clone-rule": clone_rule_case, "create-rule": create_rule_case, "events-rule": events_rule_case}
+
+
+def run_rule_child(case):
+    run_case_child(case, dict(os.environ, EPH_AMD_LIBRARY=str(HOOKS_LIB), EPH_CRAFT_FORM="thread", EPH_CRAFT_SORT="2", EPH_CRAFT_QUEUE="0"))
+
+
 def test_commit_rule_under_failing_allocations(gpu):
-    run_case_child("commit-rule", dict(os.environ, EPH_AMD_LIBRARY=str(HOOKS_LIB), EPH_CRAFT_FORM="thread", EPH_CRAFT_SORT="2",
-                                       EPH_CRAFT_QUEUE="0"))
+    run_rule_child("commit-rule")
+
+
+@pytest.mark.parametrize("case", ["clone-rule", "create-rule", "events-rule"])
+def test_lifecycle_calls_under_failing_allocations(gpu, case):
+    """create, clone and enable_events of the 136-craft batch that owns every optional buffer, each in a child like the gather's"""
+    run_rule_child(case)
 
 
 # ---- the example ---------------------------------------------------------------------------------------------------------------------
@@ -618,8 +767,10 @@ if __name__ == "__main__":
     import ephemeris_explorer_amd as ea
     case = sys.argv[1]
     try:
-        if case == "commit-rule":
-            print(f"failures {commit_rule_case(ea)}")
+        if case in RULE_CASES:
+            failures = RULE_CASES[case](ea)
+            print(f"{case}: failures {failures}")
+            assert failures == ALLOCATIONS[case], f"{failures} allocations, {ALLOCATIONS[case]} before"
         else:
             assert os.environ.get("EPH_CRAFT_FORM") == "thread"
             thread_form_cases(ea)
