@@ -12,7 +12,7 @@ HOOKS_LIB = HERE / "libephemeris_amd_testhooks.so"
 HOOKS_SOURCES = ["debug_api.cpp", "debug_kernels.hip"]
 N_PAIR_VARIANTS = 7      # csrc/pair_term.h: the evaluation orders of the unpinned point-mass term, all in the one library
 # compiled once per evaluation order (-DEPH_PAIR_VARIANT=k, every symbol in namespace eph::pv<k>; csrc/pair_ns.h)
-PAIR_SOURCES = ["step_wg.hip", "step_wave.hip", "step_small.hip", "step_double_small.hip", "fast.hip", "craft_sweep.hip"]
+PAIR_SOURCES = ["step_wg.hip", "step_wave.hip", "step_small.hip", "step_double_small.hip", "step_srkn_small.hip", "fast.hip", "craft_sweep.hip"]
 # compiled once
 SOURCES = ["solout.hip", "double_step.hip", "craft.hip", "craft_events.hip", "ephemeris_table.hip", "evaluators.hip", "craft_eval.hip", "craft_restart.hip", "craft_gather.hip", "craft_plot.hip", "craft_markers.hip", "craft_separation.hip", "peer.hip", "dispatch.cpp", "mem.cpp", "coeffs.cpp", "nbody.cpp", "propagator.cpp", "shard.cpp", "api.cpp"]
 EXPORTS = CSRC / "exports.map"      # linker version script: only eph_* is a dynamic symbol

@@ -1,6 +1,8 @@
 """convergence::<M>(problem, h0) of the reference's own integration test, ephemeris/tests/solar_system_convergence.rs:225-285,
 on the device: the doubling sweep of step sizes whose answers that test asserts (QuinlanTremaine12 -> 10 min, Stormer13 -> 5 min,
-BlanesMoan14A -> 10 min). Every run is a compensated NBodyIntegration (state Double<DVec3>, method "<M><Double>"), as in the test."""
+BlanesMoan14A -> 10 min). Every run is a compensated NBodyIntegration (state Double<DVec3>, method "<M><Double>"), as in the test.
+At the shipped system's 32 bodies all three answers run as single launches: a run's steady steps are one launch of
+k_lm_double_small for the two multistep methods, and the whole run is one launch of k_srkn_double_small for BlanesMoan14A."""
 import functools
 
 import numpy as np

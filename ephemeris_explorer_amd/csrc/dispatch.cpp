@@ -25,6 +25,22 @@ static const PairKernels *table(int pv) {
     return pv >= 0 && pv < kPairVariants ? t[pv] : nullptr;
 }
 
+// (the SRKN single-workgroup kernels export their launchers through a table of their own: PairKernels lives in step_wave.hip)
+namespace pv0 { const SrknSmallKernels *srkn_small_table(); }
+namespace pv1 { const SrknSmallKernels *srkn_small_table(); }
+namespace pv2 { const SrknSmallKernels *srkn_small_table(); }
+namespace pv3 { const SrknSmallKernels *srkn_small_table(); }
+namespace pv4 { const SrknSmallKernels *srkn_small_table(); }
+namespace pv5 { const SrknSmallKernels *srkn_small_table(); }
+namespace pv6 { const SrknSmallKernels *srkn_small_table(); }
+
+static const SrknSmallKernels *srkn_table(int pv) {
+    static const SrknSmallKernels *const t[kPairVariants] = {pv0::srkn_small_table(), pv1::srkn_small_table(), pv2::srkn_small_table(),
+                                                             pv3::srkn_small_table(), pv4::srkn_small_table(), pv5::srkn_small_table(),
+                                                             pv6::srkn_small_table()};
+    return pv >= 0 && pv < kPairVariants ? t[pv] : nullptr;
+}
+
 static std::atomic<int> g_default_pv{-1};
 int default_pair_variant() {
     int v = g_default_pv.load(std::memory_order_relaxed);
@@ -117,6 +133,20 @@ int launch_lm_double_small(int pv, hipStream_t s, const LmDoubleArgs &d, int64_t
     if (d.a.n <= 0 || nsteps <= 0) return EPH_OK;
     if (d.a.n > kGangMaxN) return EPH_ERR_UNSUPPORTED;
     return t->lm_double_small(s, d, nsteps);
+}
+int launch_srkn_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
+    const SrknSmallKernels *t = srkn_table(pv);
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
+    if (a.n <= 0 || nsteps <= 0) return EPH_OK;
+    if (a.n > kGangMaxN || a.stages < 1 || a.stages > 32) return EPH_ERR_UNSUPPORTED;
+    return t->srkn_small(s, a, nsteps);
+}
+int launch_srkn_double_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
+    const SrknSmallKernels *t = srkn_table(pv);
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
+    if (a.n <= 0 || nsteps <= 0) return EPH_OK;
+    if (a.n > kGangMaxN || a.stages < 1 || a.stages > 32 || !a.YE || !a.VE) return EPH_ERR_UNSUPPORTED;
+    return t->srkn_double_small(s, a, nsteps);
 }
 int launch_lm_small_many(int pv, hipStream_t s, const LmArgs *argv_dev, int count, int L, int64_t nsteps) {
     const PairKernels *t = table(pv);

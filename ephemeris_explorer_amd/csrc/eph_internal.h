@@ -133,6 +133,25 @@ int launch_lm_small_many(int pv, hipStream_t s, const LmArgs *argv_dev, int coun
 // a `<Double>` handle's single-workgroup steps (LmDoubleArgs: double_state.h): n <= kGangMaxN bodies, nsteps per launch
 struct LmDoubleArgs;
 int launch_lm_double_small(int pv, hipStream_t s, const LmDoubleArgs &d, int64_t nsteps);
+// a symplectic (SRKN) handle's single-workgroup steps (step_srkn_small.hip): n <= kGangMaxN bodies, nsteps steps of `stages` stages
+// per launch. Stage s: the force at the stage positions (skipped for an FSAL table's first stage once a step has been taken), then
+// v += a * hb[s]; y += v * ha[s] on the plain state or on Double (YE / VE: the error parts, `<Double>` handles only).
+struct SrknSmallArgs {
+    int n, npad;
+    int stages, fsal;
+    uint32_t starter_i;        // steps the handle has taken on entry: an FSAL table evaluates its first stage at step 0 only
+    Body4 *pos[2];             // both packed buffers: pos[0] holds the positions on entry, both hold the newest on exit
+    double *Y, *V, *ASR;       // ring slot 0, velocity, the last evaluated acceleration (the FSAL carry across launches)
+    double *YE, *VE;
+    double hb[32], ha[32];     // h * B[s], h * A[s]: the bound of SrknCoeffs
+    SampleArgs samp;           // plain kernel only
+};
+struct SrknSmallKernels {      // one evaluation order's launchers, filled in step_srkn_small.hip
+    int (*srkn_small)(hipStream_t, const SrknSmallArgs &, int64_t);
+    int (*srkn_double_small)(hipStream_t, const SrknSmallArgs &, int64_t);
+};
+int launch_srkn_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
+int launch_srkn_double_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
 // opt-in fast path: slice-parallel partial sums combined in slice order (NOT the reference's summation order)
 int fast_slices(int npad, bool approx = false);                     // S (the rsq form takes twice the waves)
 #ifndef EPH_F32_GROUP

@@ -242,6 +242,8 @@ private:
     int alloc_buffers();
     int startup_macro_step();                 // one LinearMultistepIntegrator::advance in the start-up regime
     int srkn_step(double h, double *y_slot);  // FixedRungeKuttaIntegrator::advance (SRKN)
+    int srkn_batch(int64_t k);                // k of them in one launch of the single-workgroup kernel (step_srkn_small.hip)
+    bool srkn_small_ready() const { return !is_multistep_ && n_ >= 1 && n_ <= kGangMaxN && !sharded() && (path_ == 0 || path_ == 2); }
     int lm_batch(int64_t k);                  // k steady-state ELM2::advance
     int lm_batch_double(int64_t k);           // the same on a `<Double>` handle
     void fill_lm_args(LmArgs &a) const;       // the fields of a batch's launch arguments that both set

@@ -6,7 +6,7 @@
 //   SubstepperIntegrator::advance               integration/src/multistep/mod.rs:97-108
 //   FixedRungeKuttaIntegrator::advance + SRKN   integration/src/runge_kutta/mod.rs:106-126, nystrom/symplectic.rs:69-102
 // The host replays the reference's scalar bookkeeping (time, bound, step counters) with the reference's f64
-// operations; all vector arithmetic runs in the HIP kernels of step_wg.hip / step_wave.hip / step_small.hip / fast.hip / solout.hip.
+// operations; all vector arithmetic runs in the HIP kernels of step_wg.hip / step_wave.hip / step_small.hip / step_srkn_small.hip / fast.hip / solout.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -459,6 +459,32 @@ int NBodyIntegration::lm_batch(int64_t k) {
     return EPH_OK;
 }
 
+// k x srkn_step(h_, Yslot(0)) in ONE launch of the single-workgroup kernel (srkn_small_ready); the caller has established that
+// neither of srkn_step's two tests fires in these k steps (steps_available)
+int NBodyIntegration::srkn_batch(int64_t k) {
+    SrknSmallArgs a{};
+    a.n = n_; a.npad = npad_;
+    a.stages = rk_.stages; a.fsal = rk_.fsal ? 1 : 0;
+    a.starter_i = starter_i_;
+    a.pos[0] = P_[pp_].p; a.pos[1] = P_[pp_ ^ 1].p;
+    a.Y = Yslot(0); a.V = V_.p; a.ASR = ASR_.p;
+    a.YE = compensated_ ? YEslot(0) : nullptr; a.VE = compensated_ ? VE_.p : nullptr;
+    for (int s = 0; s < rk_.stages; ++s) { a.hb[s] = h_ * rk_.B[s]; a.ha[s] = h_ * rk_.A[s]; }
+    a.samp = samp_;
+    int st;
+    TimingGuard timing{*this};
+    if ((st = timing.open())) return st;
+    if ((st = compensated_ ? launch_srkn_double_small(pv_, stream_, a, k) : launch_srkn_small(pv_, stream_, a, k))) return st;
+    if (timing_) kernel_launches_ += 1;
+    if ((st = timing.close())) return st;
+    // the bookkeeping of k calls of srkn_step (the launch is already queued)
+    for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;
+    const uint64_t per_step = (uint64_t)(rk_.fsal ? rk_.stages - 1 : rk_.stages);
+    evals_ += (uint64_t)k * per_step + (rk_.fsal && starter_i_ == 0 ? 1 : 0);
+    starter_i_ += (uint32_t)k;
+    return EPH_OK;
+}
+
 int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
     if (failed_) { if (done_out) *done_out = 0; return failed_; }     // a gang launch failed after this handle's bookkeeping had moved
     EPH_HIP(hipSetDevice(device_));
@@ -466,7 +492,19 @@ int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
     int st = EPH_OK;
     const SampleArgs samp = samp_;
     while (done < n_steps) {
-        if (!is_multistep_) {
+        if (srkn_small_ready() && !(done > 0 && samp.period)) {
+            // at most 32 bodies: the steps that can be taken, in one launch (the kernel's sampling countdown starts at this
+            // advance()'s first step, so a sampled call that comes round again -- more than 2^30 steps -- finishes below)
+            int after = EPH_OK;
+            int64_t want = n_steps - done;
+            if (want > (int64_t)1 << 30) want = (int64_t)1 << 30;
+            const int64_t k = steps_available(want, &after);
+            if (k > 0) {
+                if ((st = srkn_batch(k))) break;
+                done += k;
+            }
+            if (k < want) { st = after; break; }
+        } else if (!is_multistep_) {
             if ((st = srkn_step(h_, Yslot(0)))) break;
             done++;
             if ((st = launch_sample(stream_, n_, npad_, Yslot(0), samp, (uint32_t)done))) break;

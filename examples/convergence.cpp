@@ -8,7 +8,8 @@
 //   (needs an MI355X; without a device the first compute call throws Error{EPH_ERR_NO_DEVICE}: exit 77)
 //
 // The reference's answers on its 34-body system over 366 days, and this library's on the committed 32-body one over 365:
-// QuinlanTremaine12 -> 600 s, Stormer13 -> 300 s (BlanesMoan14A -> 600 s: an SRKN stage is a launch of its own, expect minutes).
+// QuinlanTremaine12 -> 600 s, Stormer13 -> 300 s, BlanesMoan14A -> 600 s (pass the method as the second argument; at 32 bodies
+// every run of a sweep is a single launch, the BlanesMoan14A sweep about 16 s in all).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
