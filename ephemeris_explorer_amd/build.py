@@ -23,6 +23,9 @@ HEADERS = sorted(p.name for pat in ("*.h", "*.inc", "exports.map") for p in CSRC
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 FLAGS += os.environ.get("EPH_EXTRA_FLAGS", "").split()
+# per-source flags. step_wg.hip: the leading scalar and pointer arguments of its kernels arrive in SGPRs (kernarg preload: the six
+# hot arguments of k_lm_step_wg, csrc/step_wg.hip), so no wave waits for the kernarg segment before its first loads
+SOURCE_FLAGS = {"step_wg.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=6"]}
 
 
 def hipcc():
@@ -34,9 +37,10 @@ def hipcc():
 
 def units():
     """(source, object, extra flags) of every translation unit of the library"""
-    out = [(src, CSRC / (src.rsplit(".", 1)[0] + ".o"), []) for src in SOURCES + HOOKS_SOURCES]
+    out = [(src, CSRC / (src.rsplit(".", 1)[0] + ".o"), SOURCE_FLAGS.get(src, [])) for src in SOURCES + HOOKS_SOURCES]
     for k in range(N_PAIR_VARIANTS):
-        out += [(src, CSRC / (src.rsplit(".", 1)[0] + f".pv{k}.o"), [f"-DEPH_PAIR_VARIANT={k}"]) for src in PAIR_SOURCES]
+        out += [(src, CSRC / (src.rsplit(".", 1)[0] + f".pv{k}.o"), [f"-DEPH_PAIR_VARIANT={k}", *SOURCE_FLAGS.get(src, [])])
+                for src in PAIR_SOURCES]
     return out
 
 

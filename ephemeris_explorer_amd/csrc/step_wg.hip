@@ -55,6 +55,17 @@
 #undef EPH_WG_ABLATE
 #define EPH_WG_ABLATE 0
 #endif
+// the entry of k_lm_step_wg (profiles/step_entry.md). EPH_WG_ENTRY_ARGS: 1 = the hot scalars come from the leading, preloaded
+// kernel arguments, 0 = from the by-value block behind them as before. EPH_WG_HIST_AT: where the tail wave of the 16-body form issues
+// its history loads -- 0 at its entry, 1 behind its first tile loads, 2 behind barrier B_0.
+#if !EPH_EXPERIMENTS || !defined(EPH_WG_ENTRY_ARGS)
+#undef EPH_WG_ENTRY_ARGS
+#define EPH_WG_ENTRY_ARGS 1
+#endif
+#if !EPH_EXPERIMENTS || !defined(EPH_WG_HIST_AT)
+#undef EPH_WG_HIST_AT
+#define EPH_WG_HIST_AT 1
+#endif
 #define WG_LOOP_BARRIER() do { if constexpr (!(EPH_WG_ABLATE & 2)) __syncthreads(); } while (0)
 
 // The SIX-WAVE 8-body workgroup (round 5; `DUO` in the templates below, wb code 9 in the launcher): four pair waves x two bodies, a
@@ -69,6 +80,23 @@ namespace eph {
 namespace EPH_PV_NS {
 
 constexpr int kWgBodies = 16;
+
+// -DEPH_EXPERIMENTS=1 -DEPH_WG_STAMPS=1 (tuning build; the product carries none): lane 0 of every wave of workgroup 7 of k_lm_step_wg
+// stores the shader clock (s_memtime) at 0 its entry, 1 its first tile data arrived (the wave waits for them there), 2 its arrival at
+// barrier B_0, 3 behind B_0, 4 behind the tile loop, 5 behind the barrier that hands the acceleration over, 6 its end; the 16-body
+// form only. eph_wg_stamps (order 0) copies the last launch's out: scripts/step_entry_stamps.py, profiles/step_entry.md.
+#if !EPH_EXPERIMENTS || !defined(EPH_WG_STAMPS)
+#undef EPH_WG_STAMPS
+#define EPH_WG_STAMPS 0
+#endif
+#if EPH_WG_STAMPS
+__device__ unsigned long long g_wg_stamps[12][8];
+#define WG_STAMP(k) do { if (blockIdx.x == 7 && (threadIdx.x & 63) == 0) g_wg_stamps[threadIdx.x >> 6][k] = __builtin_amdgcn_s_memtime(); } while (0)
+#define WG_STAMP_DATA(k) do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); WG_STAMP(k); } while (0)
+#else
+#define WG_STAMP(k) do {} while (0)
+#define WG_STAMP_DATA(k) do {} while (0)
+#endif
 constexpr int kDuoThreads = 64 * 6;                  // the duo form: waves 0-3 pair (two bodies each), 4 chain, 5 tail
 constexpr int kDuoTailWave = 5;
 constexpr int kWgChainWave = 4;                      // the chain wave (wave 4: lands on SIMD 0)
@@ -398,8 +426,13 @@ __device__ __forceinline__ void wg_pair_block(const double (&xi)[NB], const doub
 // 15 / 15 / 15 / 3 -- ranks 0 and 1 carry the five bodies of the group (NB = 5), rank 2, which only ever has the THIRD tile of a
 // three-tile phase, the first four (NB = 4); the fifth bodies of the three groups (local bodies 5, 10, 15) against that tile are ONE
 // block of wave 8 on SIMD 0 (NB = 3, BS = 5, rank 2: the same loop), written to the rows the rank-2 waves would have written.
-template <int NB, int BS = 1, typename PosPtr>
-__device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int b0, int rank, double *C, int lane, int tiles, int tdiag, int wbuf) {
+// `hook`: called once behind the wave's first tile loads -- the step kernel's tail wave issues its history loads there, so that they
+// queue behind the loads everybody waits for at B_0 and not in front of them (EPH_WG_HIST_AT, tuning builds: 0 at the kernel's entry
+// as before, 2 behind B_0; 32.9 / 33.4 / 32.8 us per step for 1 / 0 / 2 at one phase of the code, profiles/step_entry.md)
+struct WgNoHook { __device__ __forceinline__ void operator()() const {} };
+template <int NB, int BS = 1, typename PosPtr, typename Hook = WgNoHook>
+__device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int b0, int rank, double *C, int lane, int tiles, int tdiag, int wbuf,
+                                                  Hook &&hook = Hook{}) {
     double xi[NB], yi[NB], zi[NB];
     wg_load_own<NB, BS>(pos, n, i0 + b0, xi, yi, zi);
     auto tile_of = [&](int P) { return P < 2 ? (rank == 0 ? P : tiles) : phase_start(P) + rank; };   // >= tiles: none
@@ -414,8 +447,13 @@ __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int
             wg_pair_block<NB, 1, BS>(xi, yi, zi, src, t == tdiag, dst, b0, lane);
         };
         Body4 pj = load_src(pos, n, tiles, lane, tile_of(0)), pjn = load_src(pos, n, tiles, lane, tile_of(1));
+        if constexpr (EPH_WG_HIST_AT == 1) hook();
+        WG_STAMP_DATA(1);
         produce(tile_of(0), pj);
+        WG_STAMP(2);
         __syncthreads();
+        WG_STAMP(3);
+        if constexpr (EPH_WG_HIST_AT == 2) hook();
         for (int P = 1; P < NP; ++P) {
             pj = pjn;
             pjn = load_src(pos, n, tiles, lane, tile_of(P + 1));
@@ -430,7 +468,12 @@ __device__ __forceinline__ void wg_pair_wave_deal(PosPtr pos, int n, int i0, int
         for (int q = 0; q < 3 * NB; ++q) held[q] = 0.0;
         int tprev = tile_of(2);                         // nothing held in the interval of the first c: zeros to its own buffer
         Body4 pj, pjn = load_src(pos, n, tiles, lane, tile_of(2));
+        if constexpr (EPH_WG_HIST_AT == 1) hook();
+        WG_STAMP_DATA(1);
+        WG_STAMP(2);
         __syncthreads();
+        WG_STAMP(3);
+        if constexpr (EPH_WG_HIST_AT == 2) hook();
         for (int I = 1; I < NI; ++I) {
             const int t = I < 2 ? tiles : tile_of(I);
             if (I >= 2) {
@@ -500,8 +543,11 @@ __device__ __forceinline__ void wg_pair_wave_solo(PosPtr pos, int n, int i0, dou
     Body4 s[3], sn[3];
     load_phase(0, s);
     load_phase(1, sn);
+    WG_STAMP_DATA(1);
     produce(0, s);
+    WG_STAMP(2);
     __syncthreads();
+    WG_STAMP(3);
     for (int P = 1; P < NI; ++P) {                      // (P = NP, when the last phase has a third tile: its writes alone)
 #pragma unroll
         for (int k = 0; k < 3; ++k) s[k] = sn[k];
@@ -608,9 +654,10 @@ __device__ __forceinline__ double wg_force_split(PosPtr pos, int n, int i0, doub
 // wave carrying all of them and this wave only meeting the barriers -- two waves beside the chain's adds instead of three -- measured
 // 31.41-31.56 against 31.18-31.36 us per step: scripts/experiments/wg_solo6.patch.)
 constexpr int kWgShedFirst = 5, kWgShedStride = 5, kWgShedBodies = 3;
-template <typename PosPtr>
-__device__ __forceinline__ void wg_tail_wave_phases(PosPtr pos, int n, int i0, double *C, int lane, int tiles, int tdiag, int wbuf) {
-    wg_pair_wave_deal<kWgShedBodies, kWgShedStride>(pos, n, i0, kWgShedFirst, 2, C, lane, tiles, tdiag, wbuf);
+template <typename PosPtr, typename Hook = WgNoHook>
+__device__ __forceinline__ void wg_tail_wave_phases(PosPtr pos, int n, int i0, double *C, int lane, int tiles, int tdiag, int wbuf,
+                                                    Hook &&hook = Hook{}) {
+    wg_pair_wave_deal<kWgShedBodies, kWgShedStride>(pos, n, i0, kWgShedFirst, 2, C, lane, tiles, tdiag, wbuf, hook);
 }
 
 // ---- wg_force<WB, DUO>: the force of a workgroup ------------------------------------------------------------------------------------
@@ -653,7 +700,9 @@ __device__ __forceinline__ double wg_force(PosPtr pos, int n, int i0, double ini
     // opens with the load of its own first two chunks; inside a phase tile t + 1 is prefetched while tile t is summed.
     // Behind barrier B_P the complete tiles are c of phase P - 1 and a, b of phase P (phase_start above).
     const int NP = interval_count(tiles);
+    WG_STAMP(2);
     __syncthreads();                              // B_0: tile 0 ready
+    WG_STAMP(3);
     for (int P = 0; P < NP; ++P) {
         const int t0 = chain_first(P), nt = min(chain_first(P + 1), tiles) - t0;
         // three whole tiles of other workgroups' bodies (all but a handful of phases): written out, the prefetch registers
@@ -768,47 +817,78 @@ __global__ void __launch_bounds__(kWgThreads) k_accel_wg(int n, int npad, const 
 // (amdgpu_waves_per_eu(3, 3): for the twelve-wave forms it restates what __launch_bounds__(768) already implies -- three waves per
 // SIMD, 168 VGPRs -- and changes nothing in their code; for the six-wave DUO form it is a choice (its 1.5 waves per SIMD would
 // allow 256 VGPRs): that form was measured WITH it (17.7 against 18.6 us at 2048 bodies, round 5) and ships as measured.)
+//
+// THE PHASE OF THE CODE. The step time depends on where the kernel's code lies modulo 32 bytes: s_nop (4 bytes each) at the entry of
+// the otherwise unchanged kernel move <12, 16> of order 0 between 29.6-29.9 us per step (an odd number) and 32.1-33.6 (an even one)
+// at N = 4096, period 8 s_nop = 32 bytes; the six-wave form at 2048 bodies between 17.3 and 17.8. Nearly every instruction of the
+// tile loops is 8 bytes long, and the instruction fetch evidently pays for the ones that straddle its 32-byte windows. So an edit
+// that changes the length of the entry by an odd number of dwords -- removing the kernarg loads did -- costs 3 us unless the phase is
+// put back: kWgEntryPad is the number of s_nop behind the entry. One value serves every form, both L and all seven evaluation orders
+// (each level or faster than before at 4096 / 2048 / 1024 bodies: profiles/step_entry.md). Whoever changes the length of the code in
+// front of the role switch re-takes the scan (scripts/build_exp.sh NAME -DEPH_EXPERIMENTS=1 -DEPH_WG_PAD=k, k = 0 .. 7).
+constexpr int kWgEntryPad = 5;
+//
+// THE ARGUMENTS. pos_cur, n, lo, hi, npad and cur are leading plain arguments and arrive in scalar registers (kernarg preload, a
+// compile flag of this file: build.py), the whole LmArgs follows by value and is read where a role needs the rest: the tail wave
+// alone. No wave waits for the kernarg segment in front of the role switch; every pair role's first memory instructions are the loads
+// of its own bodies and its first source tiles.
 template <int L, int WB = kWgBodies, bool DUO = false>
 __global__ void __launch_bounds__(DUO ? kDuoThreads : kWgThreads) __attribute__((amdgpu_waves_per_eu(3, 3)))
-k_lm_step_wg(const LmArgs a) {
+k_lm_step_wg(const Body4 *pos_cur_, int n_, int lo_, int hi_, int npad_, int cur_, const LmArgs a) {
     constexpr int kRows = 3 * WB;
+    if constexpr (WB == kWgBodies && !DUO) WG_STAMP(0);
+    const Body4 *const pos_cur = EPH_WG_ENTRY_ARGS ? pos_cur_ : a.pos_cur;
+    const int n = EPH_WG_ENTRY_ARGS ? n_ : a.n, lo = EPH_WG_ENTRY_ARGS ? lo_ : a.lo, hi = EPH_WG_ENTRY_ARGS ? hi_ : a.hi;
+    const int npad = EPH_WG_ENTRY_ARGS ? npad_ : a.npad, cur = EPH_WG_ENTRY_ARGS ? cur_ : a.cur;
     __shared__ __attribute__((aligned(16))) double C[wg_lds_doubles(WB, DUO)];
     const int tid = threadIdx.x, lane = tid & 63;
     const bool chain_wave = (tid >> 6) == kWgChainWave;
     // the wave that does the integrator's work around the force; wave-uniform by construction, and told so (a scalar
     // branch keeps the history registers out of the other roles' live ranges)
     const bool tail_wave = __builtin_amdgcn_readfirstlane(tid >> 6) == (DUO ? kDuoTailWave : kWgTailWave);
-    const int i0 = a.lo + blockIdx.x * WB;
+    const int i0 = lo + blockIdx.x * WB;
     const int cb = lane / 3, cc = lane % 3;
     const int my_i = i0 + cb;
-    const bool owner = tail_wave && lane < kRows && my_i < a.hi;
-    const size_t lvl = (size_t)3 * a.npad;
-    const size_t off = (size_t)cc * a.npad + (owner ? my_i : 0);
+    const bool owner = tail_wave && lane < kRows && my_i < hi;
+    const size_t lvl = (size_t)3 * npad;
+    const size_t off = (size_t)cc * npad + (owner ? my_i : 0);
     // the tail wave's whole life is this branch, so its history registers are live across this code only (through
     // wg_force's role switch the allocator would keep them alive in every role and spill)
+    // the code behind the entry at its measured 32-byte phase (kWgEntryPad above); the tuning builds' EPH_WG_PAD overrides it
+#if EPH_EXPERIMENTS && defined(EPH_WG_PAD)
+    asm volatile(".rept %0\n s_nop 0\n .endr" ::"n"(EPH_WG_PAD));
+#else
+    asm volatile(".rept %0\n s_nop 0\n .endr" ::"n"(kWgEntryPad));
+#endif
     if (tail_wave) {
         double yv[L], av[L];   // yv[j] / av[j]: level (new - j); av[0] is filled after the force
+        auto load_history = [&]() {
 #pragma unroll
-        for (int j = 0; j < L; ++j) {
-            const int slot = (a.cur + j) % L;
-            yv[j] = a.Y[slot * lvl + off];
-            av[j] = j > 0 ? a.A[slot * lvl + off] : 0.0;
-        }
+            for (int j = 0; j < L; ++j) {
+                const int slot = (cur + j) % L;
+                yv[j] = a.Y[slot * lvl + off];
+                av[j] = j > 0 ? a.A[slot * lvl + off] : 0.0;
+            }
+        };
+        constexpr bool kPhaseTail = WB == kWgBodies && !DUO;
+        if constexpr (!kPhaseTail || EPH_WG_HIST_AT == 0) load_history();
         // (Forming everything that does not need the new acceleration here, ahead of the barriers, was built and measured:
         // 37.55 vs 37.2 us per step at N = 4096 -- the early arithmetic takes issue slots from the pair wave and the chain wave
         // of this SIMD when they are the critical path, and the tail's work was not on it.)
-        const int tiles = (a.n + kTile - 1) / kTile;
+        const int tiles = (n + kTile - 1) / kTile;
         if constexpr (wg_tile_split(WB) && !DUO) {
             for (int t = 0; t <= tiles; ++t) __syncthreads();                             // one barrier per tile there
         } else if constexpr (WB == kWgBodies && !DUO) {
-            wg_tail_wave_phases(a.pos_cur, a.n, i0, C, lane, tiles, i0 / kTile, 3 * WB * kRow);
+            wg_tail_wave_phases(pos_cur, n, i0, C, lane, tiles, i0 / kTile, 3 * WB * kRow, load_history);
         } else {
             wg_idle_wave(tiles);
         }
+        if constexpr (kPhaseTail) WG_STAMP(4);
         __syncthreads();                              // the chain wave's result is in LDS
+        if constexpr (kPhaseTail) WG_STAMP(5);
         if (owner) {
             const double anew = C[lane];
-            a.A[(size_t)a.cur * lvl + off] = anew;
+            a.A[(size_t)cur * lvl + off] = anew;
             {
                 double prev[L];
 #pragma unroll
@@ -820,15 +900,18 @@ k_lm_step_wg(const LmArgs a) {
             if (a.do_predict) {
                 av[0] = anew;
                 const double ynext = lm_predict<L>(yv, av, a.wa, a.wb, a.hh);
-                const int nslot = (a.cur + L - 1) % L;
+                const int nslot = (cur + L - 1) % L;
                 a.Y[(size_t)nslot * lvl + off] = ynext;
                 reinterpret_cast<double *>(a.pos_next + my_i)[cc] = ynext;
             }
         }
+        if constexpr (kPhaseTail) WG_STAMP(6);
     } else {
-        const double anew = wg_force<WB, DUO>(a.pos_cur, a.n, i0, 0.0, C, tid);
+        const double anew = wg_force<WB, DUO>(pos_cur, n, i0, 0.0, C, tid);
+        if constexpr (WB == kWgBodies && !DUO) WG_STAMP(4);
         if (chain_wave && lane < kRows) C[lane] = anew;    // every tile buffer is dead after the loop's last barrier
         __syncthreads();
+        if constexpr (WB == kWgBodies && !DUO) WG_STAMP(5);
     }
 }
 
@@ -844,21 +927,29 @@ int accel_wg(hipStream_t s, int wb, int n, int npad, const Body4 *pos, const dou
 int lm_step_wg(hipStream_t s, int wb, const LmArgs &a) {
     if (wb == 9) {                                          // the six-wave 8-body form (dispatch.cpp: 1024 < targets <= 2048; EPH_WG_BODIES=9)
         const dim3 grid((a.hi - a.lo + 7) / 8), block(kDuoThreads);
-        if (a.L == 12) hipLaunchKernelGGL((k_lm_step_wg<12, 8, true>), grid, block, 0, s, a);
-        else if (a.L == 13) hipLaunchKernelGGL((k_lm_step_wg<13, 8, true>), grid, block, 0, s, a);
+        if (a.L == 12) hipLaunchKernelGGL((k_lm_step_wg<12, 8, true>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
+        else if (a.L == 13) hipLaunchKernelGGL((k_lm_step_wg<13, 8, true>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
         else return EPH_ERR_UNSUPPORTED;
         return launched("k_lm_step_wg (six waves)");
     }
     const dim3 grid((a.hi - a.lo + wb - 1) / wb), block(kWgThreads);
-    if (a.L == 12 && wb == 8) hipLaunchKernelGGL((k_lm_step_wg<12, 8>), grid, block, 0, s, a);
-    else if (a.L == 13 && wb == 8) hipLaunchKernelGGL((k_lm_step_wg<13, 8>), grid, block, 0, s, a);
-    else if (a.L == 12 && wb == 4) hipLaunchKernelGGL((k_lm_step_wg<12, 4>), grid, block, 0, s, a);
-    else if (a.L == 13 && wb == 4) hipLaunchKernelGGL((k_lm_step_wg<13, 4>), grid, block, 0, s, a);
-    else if (a.L == 12) hipLaunchKernelGGL((k_lm_step_wg<12, 16>), grid, block, 0, s, a);
-    else if (a.L == 13) hipLaunchKernelGGL((k_lm_step_wg<13, 16>), grid, block, 0, s, a);
+    if (a.L == 12 && wb == 8) hipLaunchKernelGGL((k_lm_step_wg<12, 8>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
+    else if (a.L == 13 && wb == 8) hipLaunchKernelGGL((k_lm_step_wg<13, 8>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
+    else if (a.L == 12 && wb == 4) hipLaunchKernelGGL((k_lm_step_wg<12, 4>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
+    else if (a.L == 13 && wb == 4) hipLaunchKernelGGL((k_lm_step_wg<13, 4>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
+    else if (a.L == 12) hipLaunchKernelGGL((k_lm_step_wg<12, 16>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
+    else if (a.L == 13) hipLaunchKernelGGL((k_lm_step_wg<13, 16>), grid, block, 0, s, a.pos_cur, a.n, a.lo, a.hi, a.npad, a.cur, a);
     else return EPH_ERR_UNSUPPORTED;
     return launched("k_lm_step_wg");
 }
 
 }  // namespace EPH_PV_NS
 }  // namespace eph
+
+#if EPH_WG_STAMPS && EPH_PAIR_VARIANT == 0
+// the stamps of the last k_lm_step_wg<L, 16> launch (order 0): [wave][point], 12 x 8 shader-clock values
+extern "C" __attribute__((visibility("default"))) int eph_wg_stamps(unsigned long long *out) {
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(eph::pv0::g_wg_stamps), sizeof(unsigned long long) * 12 * 8) == hipSuccess ? 0 : 1;
+}
+#endif

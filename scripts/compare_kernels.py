@@ -108,7 +108,8 @@ def tree_kernels(tree, tmp, pair=()):
         unit = src if k is None else f"{src} pv{k}"
         out = Path(tmp) / (unit.replace(".hip", "").replace(" ", ".") + ".s")
         order = [] if k is None else [f"-DEPH_PAIR_VARIANT={k}"]
-        subprocess.run([b["hipcc"](), *b["FLAGS"], *order, "--offload-device-only", "-S", "-x", "hip", str(b["CSRC"] / src), "-o", str(out)],
+        subprocess.run([b["hipcc"](), *b["FLAGS"], *order, *b.get("SOURCE_FLAGS", {}).get(src, []), "--offload-device-only", "-S", "-x", "hip",
+                        str(b["CSRC"] / src), "-o", str(out)],
                        check=True, stderr=subprocess.DEVNULL)
         return {name: (unit, *v) for name, v in kernels(out).items()}
     found = {}
