@@ -331,7 +331,8 @@ def test_workgroup_kernel_at_every_tile_count(gpu):
     tiles first, then pairs of tiles, six LDS buffers) is exercised here at the tile counts it never sees by default -- 2, 3,
     4, 5, 7, 17 tiles, ragged last tiles -- by forcing it (EPH_FORCE=wg, read once per process: hence the subprocess),
     at the size-dependent workgroup choice and with each workgroup size forced at EVERY n, accelerations and a few fused
-    steps against the oracle."""
+    steps against the oracle. (These sizes say nothing about the wave form that owns them by default: its tile walk, its
+    bodies per wave and its fallback branch are held by tests/test_gpu_wave_form.py.)"""
     import os
     import subprocess
     import sys
