@@ -7,12 +7,14 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "libephemeris_amd.so"
-# the product's objects + debug_api.o + debug_kernels.o: the eph_debug_* test hooks (csrc/eph_debug.h), for tests/ only -- the product never loads it
+# the product's objects + debug_api.o + debug_kernels.o + pair_debug.pv<k>.o: the eph_debug_* test hooks (csrc/eph_debug.h), for tests/ only -- the product never loads it
 HOOKS_LIB = HERE / "libephemeris_amd_testhooks.so"
 HOOKS_SOURCES = ["debug_api.cpp", "debug_kernels.hip"]
 N_PAIR_VARIANTS = 7      # csrc/pair_term.h: the evaluation orders of the unpinned point-mass term, all in the one library
 # compiled once per evaluation order (-DEPH_PAIR_VARIANT=k, every symbol in namespace eph::pv<k>; csrc/pair_ns.h)
-PAIR_SOURCES = ["step_wg.hip", "step_wave.hip", "step_small.hip", "step_double_small.hip", "step_srkn_small.hip", "fast.hip", "craft_sweep.hip"]
+PAIR_SOURCES = ["step_wg.hip", "step_wave.hip", "step_small.hip", "step_double_small.hip", "step_srkn_small.hip", "fast.hip", "craft_sweep.hip",
+                "pair_table.hip"]
+PAIR_HOOKS_SOURCES = ["pair_debug.hip"]     # the hooks' per-order half: compiled like PAIR_SOURCES, linked like HOOKS_SOURCES
 # compiled once
 SOURCES = ["solout.hip", "double_step.hip", "craft.hip", "craft_events.hip", "ephemeris_table.hip", "evaluators.hip", "craft_eval.hip", "craft_restart.hip", "craft_gather.hip", "craft_plot.hip", "craft_markers.hip", "craft_separation.hip", "peer.hip", "dispatch.cpp", "mem.cpp", "coeffs.cpp", "nbody.cpp", "propagator.cpp", "shard.cpp", "api.cpp"]
 EXPORTS = CSRC / "exports.map"      # linker version script: only eph_* is a dynamic symbol
@@ -40,7 +42,7 @@ def units():
     out = [(src, CSRC / (src.rsplit(".", 1)[0] + ".o"), SOURCE_FLAGS.get(src, [])) for src in SOURCES + HOOKS_SOURCES]
     for k in range(N_PAIR_VARIANTS):
         out += [(src, CSRC / (src.rsplit(".", 1)[0] + f".pv{k}.o"), [f"-DEPH_PAIR_VARIANT={k}", *SOURCE_FLAGS.get(src, [])])
-                for src in PAIR_SOURCES]
+                for src in PAIR_SOURCES + PAIR_HOOKS_SOURCES]
     return out
 
 
@@ -48,7 +50,7 @@ def needs_build(lib=LIB):
     if not lib.exists():
         return True
     t = lib.stat().st_mtime
-    return any((CSRC / f).stat().st_mtime > t for f in SOURCES + HOOKS_SOURCES + PAIR_SOURCES + HEADERS) or Path(__file__).stat().st_mtime > t
+    return any((CSRC / f).stat().st_mtime > t for f in SOURCES + HOOKS_SOURCES + PAIR_SOURCES + PAIR_HOOKS_SOURCES + HEADERS) or Path(__file__).stat().st_mtime > t
 
 
 def build(force=False, verbose=False, lib=LIB, extra_flags=(), obj_dir=None, jobs=None):
@@ -83,7 +85,9 @@ def build(force=False, verbose=False, lib=LIB, extra_flags=(), obj_dir=None, job
     todo.sort(key=lambda j: -(CSRC / j[0]).stat().st_size)
     with ThreadPoolExecutor(jobs or max(2, (os.cpu_count() or 4))) as ex:
         list(ex.map(compile_one, todo))
-    hook_objs = [o for o in objs if Path(o).name in {h.rsplit(".", 1)[0] + ".o" for h in HOOKS_SOURCES}]
+    hook_names = {h.rsplit(".", 1)[0] + ".o" for h in HOOKS_SOURCES}
+    hook_names |= {h.rsplit(".", 1)[0] + f".pv{k}.o" for h in PAIR_HOOKS_SOURCES for k in range(N_PAIR_VARIANTS)}
+    hook_objs = [o for o in objs if Path(o).name in hook_names]
     link = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", f"-Wl,--version-script={EXPORTS}"]
     if hooks is not None:                              # the product: the boundary only; the hooks in a library of their own
         subprocess.check_call([*link, "-o", str(lib), *[o for o in objs if o not in hook_objs]])

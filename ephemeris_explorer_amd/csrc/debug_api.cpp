@@ -7,6 +7,22 @@
 
 using namespace eph;
 
+// the per-order halves of the hooks (pair_debug.hip) and, for eph_debug_table_variants, the product's table (pair_table.hip)
+namespace eph {
+#define EPH_DECLARE_TABLES(k) namespace pv##k { const PairKernels *pair_table(); const PairDebugKernels *pair_debug_table(); }
+EPH_PAIR_ORDERS(EPH_DECLARE_TABLES)
+#undef EPH_DECLARE_TABLES
+}
+// order pv's hooks, as dispatch.cpp's table(pv) for the product's launchers: none for an order that does not exist, or when a slot
+// holds another order's table
+static const PairDebugKernels *debug_table(int pv) {
+#define EPH_TABLE_SLOT(k) pv##k::pair_debug_table(),
+    static const PairDebugKernels *const t[kPairVariants] = {EPH_PAIR_ORDERS(EPH_TABLE_SLOT)};
+#undef EPH_TABLE_SLOT
+    static const bool sound = slots_hold_their_orders(t);
+    return sound && pv >= 0 && pv < kPairVariants ? t[pv] : nullptr;
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -15,11 +31,13 @@ int32_t eph_debug_inv_r3(int64_t n, const double *n2, double *fast, double *ieee
     if (n < 0 || (n > 0 && (!n2 || !fast || !ieee))) return EPH_ERR_BAD_ARGUMENT;
     int st = check_device();
     if (st) return st;
+    const PairDebugKernels *t = debug_table(default_pair_variant());
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
     if (n == 0) return EPH_OK;
     DevBuf<double> a, b, c;
     if ((st = a.alloc(n)) || (st = b.alloc(n)) || (st = c.alloc(n))) return st;
     EPH_HIP(hipMemcpy(a.p, n2, sizeof(double) * n, hipMemcpyHostToDevice));
-    if ((st = launch_debug_inv_r3(default_pair_variant(), nullptr, n, a.p, b.p, c.p))) return st;
+    if ((st = t->debug_inv_r3(nullptr, n, a.p, b.p, c.p))) return st;
     EPH_HIP(hipMemcpy(fast, b.p, sizeof(double) * n, hipMemcpyDeviceToHost));
     EPH_HIP(hipMemcpy(ieee, c.p, sizeof(double) * n, hipMemcpyDeviceToHost));
     return EPH_OK;
@@ -32,12 +50,14 @@ int32_t eph_debug_quot(int64_t n, const double *x, const double *a, double *fast
     if (n < 0 || (n > 0 && (!x || !a || !fast || !ieee))) return EPH_ERR_BAD_ARGUMENT;
     int st = check_device();
     if (st) return st;
+    const PairDebugKernels *t = debug_table(default_pair_variant());
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
     if (n == 0) return EPH_OK;
     DevBuf<double> dx, da, b, c;
     if ((st = dx.alloc(n)) || (st = da.alloc(n)) || (st = b.alloc(n)) || (st = c.alloc(n))) return st;
     EPH_HIP(hipMemcpy(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice));
     EPH_HIP(hipMemcpy(da.p, a, sizeof(double) * n, hipMemcpyHostToDevice));
-    if ((st = launch_debug_quot(default_pair_variant(), nullptr, n, dx.p, da.p, b.p, c.p))) return st;
+    if ((st = t->debug_quot(nullptr, n, dx.p, da.p, b.p, c.p))) return st;
     EPH_HIP(hipMemcpy(fast, b.p, sizeof(double) * n, hipMemcpyDeviceToHost));
     EPH_HIP(hipMemcpy(ieee, c.p, sizeof(double) * n, hipMemcpyDeviceToHost));
     return EPH_OK;
@@ -49,10 +69,12 @@ int32_t eph_debug_inv_r3_sweep(uint64_t seed, int64_t n, uint64_t *mismatches, u
     if (n < 0 || !mismatches || !example_bits) return EPH_ERR_BAD_ARGUMENT;
     int st = check_device();
     if (st) return st;
+    const PairDebugKernels *t = debug_table(default_pair_variant());
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
     DevBuf<unsigned long long> out;
     if ((st = out.alloc(2))) return st;
     EPH_HIP(hipMemset(out.p, 0, 2 * sizeof(unsigned long long)));
-    if ((st = launch_debug_inv_r3_sweep(default_pair_variant(), nullptr, seed, n, out.p))) return st;
+    if ((st = t->debug_inv_r3_sweep(nullptr, seed, n, out.p))) return st;
     unsigned long long h[2];
     EPH_HIP(hipMemcpy(h, out.p, sizeof(h), hipMemcpyDeviceToHost));
     *mismatches = h[0];
@@ -63,7 +85,8 @@ int32_t eph_debug_inv_r3_sweep(uint64_t seed, int64_t n, uint64_t *mismatches, u
 
 int32_t eph_debug_wg_cycles(int64_t *out8) {
     if (!out8) return EPH_ERR_BAD_ARGUMENT;
-    return debug_wg_cycles(default_pair_variant(), (long long *)out8);
+    const PairDebugKernels *t = debug_table(default_pair_variant());
+    return t ? t->debug_wg_cycles((long long *)out8) : EPH_ERR_BAD_ARGUMENT;
 }
 
 int32_t eph_debug_div(int64_t n, const double *a, const double *b, double *fast, double *ieee) { return debug_div_device(n, a, b, fast, ieee); }
@@ -78,6 +101,15 @@ int32_t eph_debug_fast_partition(int32_t npad, int32_t path, int32_t *S, int32_t
     const bool approx = path == EPH_PATH_FAST_RSQ, f32 = path == EPH_PATH_F32_PAIRS;
     *S = fast_slices(npad, approx);
     *slice_len = fast_slice_len(npad, *S, fast_unroll(), approx, f32);
+    return EPH_OK;
+}
+
+// host only: what each slot of the two per-order tables says of itself
+int32_t eph_debug_table_variants(int32_t *product, int32_t *debug) {
+    if (!product || !debug) return EPH_ERR_BAD_ARGUMENT;
+#define EPH_TABLE_SLOT(k) product[k] = pv##k::pair_table()->variant, debug[k] = pv##k::pair_debug_table()->variant;
+    EPH_PAIR_ORDERS(EPH_TABLE_SLOT)
+#undef EPH_TABLE_SLOT
     return EPH_OK;
 }
 

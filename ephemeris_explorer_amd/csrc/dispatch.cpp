@@ -1,7 +1,8 @@
 // dispatch.cpp -- which kernel form runs a launch, and whose: the kernels that contain the point-mass term exist once per
-// evaluation order of that term (namespaces eph::pv0 .. pv6, pair_ns.h); every handle carries the order it was created under,
-// and the launch_* functions below route to that order's table after choosing the form (one wave per block / workgroup-
-// specialised / single workgroup; bodies per wave or workgroup) from the number of TARGET bodies of the launch.
+// evaluation order of that term (namespaces eph::pv0 .. pv6, pair_ns.h; the orders are listed once, EPH_PAIR_ORDERS); every handle
+// carries the order it was created under, and the launch_* functions below route to that order's table (pair_table.hip) after
+// choosing the form (one wave per block / workgroup-specialised / single workgroup; bodies per wave or workgroup) from the number
+// of TARGET bodies of the launch. The test hooks route through a table of their own (pair_debug.hip, debug_api.cpp).
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -11,34 +12,17 @@
 
 namespace eph {
 
-namespace pv0 { const PairKernels *pair_table(); }
-namespace pv1 { const PairKernels *pair_table(); }
-namespace pv2 { const PairKernels *pair_table(); }
-namespace pv3 { const PairKernels *pair_table(); }
-namespace pv4 { const PairKernels *pair_table(); }
-namespace pv5 { const PairKernels *pair_table(); }
-namespace pv6 { const PairKernels *pair_table(); }
+#define EPH_DECLARE_TABLE(k) namespace pv##k { const PairKernels *pair_table(); }      // pair_table.hip, once per order
+EPH_PAIR_ORDERS(EPH_DECLARE_TABLE)
+#undef EPH_DECLARE_TABLE
 
+// order pv's launchers; none for an order that does not exist, or when a slot holds another order's table
 static const PairKernels *table(int pv) {
-    static const PairKernels *const t[kPairVariants] = {pv0::pair_table(), pv1::pair_table(), pv2::pair_table(), pv3::pair_table(),
-                                                        pv4::pair_table(), pv5::pair_table(), pv6::pair_table()};
-    return pv >= 0 && pv < kPairVariants ? t[pv] : nullptr;
-}
-
-// (the SRKN single-workgroup kernels export their launchers through a table of their own: PairKernels lives in step_wave.hip)
-namespace pv0 { const SrknSmallKernels *srkn_small_table(); }
-namespace pv1 { const SrknSmallKernels *srkn_small_table(); }
-namespace pv2 { const SrknSmallKernels *srkn_small_table(); }
-namespace pv3 { const SrknSmallKernels *srkn_small_table(); }
-namespace pv4 { const SrknSmallKernels *srkn_small_table(); }
-namespace pv5 { const SrknSmallKernels *srkn_small_table(); }
-namespace pv6 { const SrknSmallKernels *srkn_small_table(); }
-
-static const SrknSmallKernels *srkn_table(int pv) {
-    static const SrknSmallKernels *const t[kPairVariants] = {pv0::srkn_small_table(), pv1::srkn_small_table(), pv2::srkn_small_table(),
-                                                             pv3::srkn_small_table(), pv4::srkn_small_table(), pv5::srkn_small_table(),
-                                                             pv6::srkn_small_table()};
-    return pv >= 0 && pv < kPairVariants ? t[pv] : nullptr;
+#define EPH_TABLE_SLOT(k) pv##k::pair_table(),
+    static const PairKernels *const t[kPairVariants] = {EPH_PAIR_ORDERS(EPH_TABLE_SLOT)};
+#undef EPH_TABLE_SLOT
+    static const bool sound = slots_hold_their_orders(t);
+    return sound && pv >= 0 && pv < kPairVariants ? t[pv] : nullptr;
 }
 
 static std::atomic<int> g_default_pv{-1};
@@ -46,7 +30,8 @@ int default_pair_variant() {
     int v = g_default_pv.load(std::memory_order_relaxed);
     if (v < 0) {                                       // first use: the environment's choice, else order 0
         const char *e = getenv("EPH_PAIR_VARIANT");
-        v = e && *e >= '0' && *e <= '6' && !e[1] ? *e - '0' : 0;
+        static_assert(kPairVariants <= 10, "EPH_PAIR_VARIANT is read as one digit");
+        v = e && *e >= '0' && *e < '0' + kPairVariants && !e[1] ? *e - '0' : 0;
         g_default_pv.store(v, std::memory_order_relaxed);
     }
     return v;
@@ -135,14 +120,14 @@ int launch_lm_double_small(int pv, hipStream_t s, const LmDoubleArgs &d, int64_t
     return t->lm_double_small(s, d, nsteps);
 }
 int launch_srkn_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
-    const SrknSmallKernels *t = srkn_table(pv);
+    const PairKernels *t = table(pv);
     if (!t) return EPH_ERR_BAD_ARGUMENT;
     if (a.n <= 0 || nsteps <= 0) return EPH_OK;
     if (a.n > kGangMaxN || a.stages < 1 || a.stages > 32) return EPH_ERR_UNSUPPORTED;
     return t->srkn_small(s, a, nsteps);
 }
 int launch_srkn_double_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
-    const SrknSmallKernels *t = srkn_table(pv);
+    const PairKernels *t = table(pv);
     if (!t) return EPH_ERR_BAD_ARGUMENT;
     if (a.n <= 0 || nsteps <= 0) return EPH_OK;
     if (a.n > kGangMaxN || a.stages < 1 || a.stages > 32 || !a.YE || !a.VE) return EPH_ERR_UNSUPPORTED;
@@ -199,24 +184,6 @@ int launch_lm_step_fast(int pv, hipStream_t s, const LmArgs &a, double *partial,
 int launch_craft(int pv, hipStream_t s, const CraftArgs &a, const CraftLaunch &how) {
     const PairKernels *t = table(pv);
     return t ? t->craft_launch(s, a, how) : EPH_ERR_BAD_ARGUMENT;
-}
-int launch_debug_inv_r3(int pv, hipStream_t s, int64_t n, const double *n2, double *fast, double *ieee) {
-    const PairKernels *t = table(pv);
-    if (!t) return EPH_ERR_BAD_ARGUMENT;
-    return n <= 0 ? EPH_OK : t->debug_inv_r3(s, n, n2, fast, ieee);
-}
-int launch_debug_inv_r3_sweep(int pv, hipStream_t s, uint64_t seed, int64_t n, unsigned long long *out2) {
-    const PairKernels *t = table(pv);
-    return t ? t->debug_inv_r3_sweep(s, seed, n, out2) : EPH_ERR_BAD_ARGUMENT;
-}
-int launch_debug_quot(int pv, hipStream_t s, int64_t n, const double *x, const double *a, double *fast, double *ieee) {
-    const PairKernels *t = table(pv);
-    if (!t) return EPH_ERR_BAD_ARGUMENT;
-    return n <= 0 ? EPH_OK : t->debug_quot(s, n, x, a, fast, ieee);
-}
-int debug_wg_cycles(int pv, long long *out) {
-    const PairKernels *t = table(pv);
-    return t ? t->debug_wg_cycles(out) : EPH_ERR_BAD_ARGUMENT;
 }
 
 }  // namespace eph

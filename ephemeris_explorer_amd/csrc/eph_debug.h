@@ -1,6 +1,8 @@
 /* eph_debug.h -- test and tuning hooks. NOT part of the drop-in boundary (include/ephemeris_amd.h): no trait of the reference
- * corresponds to them. Their extern "C" entry points are compiled in debug_api.cpp (device halves: debug_kernels.hip), which is linked into
- *   - libephemeris_amd_testhooks.so (the product's objects + debug_api.o + debug_kernels.o; tests/hooks.py loads it), and
+ * corresponds to them. Their extern "C" entry points are compiled in debug_api.cpp (device halves: debug_kernels.hip and, once per
+ * evaluation order of the point-mass term, pair_debug.hip), which is linked into
+ *   - libephemeris_amd_testhooks.so (the product's objects + debug_api.o + debug_kernels.o + pair_debug.pv<k>.o; tests/hooks.py
+ *     loads it), and
  *   - tuning builds (scripts/build_exp.sh NAME -DEPH_EXPERIMENTS=1 ...),
  * never into libephemeris_amd.so. */
 #pragma once
@@ -38,15 +40,29 @@ int32_t eph_debug_fail_alloc(int32_t nth);
  * uses in THIS process for a system padded to npad bodies -- S slices of slice_len consecutive sources, EPH_FAST_SLICES and
  * EPH_FAST_UNROLL honoured. A host function: no device is touched. */
 int32_t eph_debug_fast_partition(int32_t npad, int32_t path, int32_t *S, int32_t *slice_len);
+/* Test hook: product[k] / debug[k] (7 ints each, one per evaluation order) = the order that slot k of the product's launcher table
+ * (csrc/pair_table.hip) and of the hooks' (csrc/pair_debug.hip) was compiled for: k in every slot. A host function: no device is
+ * touched. */
+int32_t eph_debug_table_variants(int32_t *product, int32_t *debug);
 
 #ifdef __cplusplus
 }
 #endif
 
 #ifdef __cplusplus
+#include <hip/hip_runtime.h>
 namespace eph {                 /* the device halves that live beside their kernels (debug_kernels.hip) */
 int debug_div_device(int64_t n, const double *a, const double *b, double *fast, double *ieee);
 int debug_rsq_device(int64_t n, const double *x, double *rsq, double *h);
 int debug_pow_device(int64_t n, const double *x, double y, double *out);
+/* one evaluation order's hook launchers, filled in pair_debug.hip: 1/(x*sqrt(x)) and a/(x*sqrt(x)) through the in-range sequences
+ * and through the compiler's IEEE expansions; tuning builds (-DEPH_EXPERIMENTS): the single-workgroup kernel's cycle accounting */
+struct PairDebugKernels {
+    int (*debug_inv_r3)(hipStream_t, int64_t, const double *, double *, double *);
+    int (*debug_inv_r3_sweep)(hipStream_t, uint64_t, int64_t, unsigned long long *);
+    int (*debug_quot)(hipStream_t, int64_t, const double *, const double *, double *, double *);
+    int (*debug_wg_cycles)(long long *);
+    int variant;                /* the order they were compiled for: debug_api.cpp holds slot k to order k */
+};
 }
 #endif

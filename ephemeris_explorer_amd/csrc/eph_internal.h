@@ -115,6 +115,17 @@ struct LmArgs {                // fused linear-multistep step (step_wg.hip, step
 // says whose. A handle fixes it at creation (eph_set_pair_variant / EPH_PAIR_VARIANT); dispatch.cpp chooses the kernel form
 // (wave / workgroup / single workgroup, bodies per wave or workgroup) and routes to that order's table.
 constexpr int kPairVariants = 7;
+#define EPH_PAIR_ORDERS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)      // the orders, listed once: the declarations and tables per order
+#define EPH_PAIR_ORDER_COUNT(k) +1
+static_assert(0 EPH_PAIR_ORDERS(EPH_PAIR_ORDER_COUNT) == kPairVariants, "EPH_PAIR_ORDERS lists every evaluation order once");
+#undef EPH_PAIR_ORDER_COUNT
+// slot k of a per-order table array holds order k's table (PairKernels below; the hooks' PairDebugKernels, eph_debug.h)
+template <class Table>
+bool slots_hold_their_orders(const Table *const (&t)[kPairVariants]) {
+    for (int k = 0; k < kPairVariants; ++k)
+        if (t[k]->variant != k) return false;
+    return true;
+}
 int default_pair_variant();                 // what new handles take: eph_set_pair_variant, else EPH_PAIR_VARIANT, else 0
 int set_default_pair_variant(int pv);       // EPH_ERR_BAD_ARGUMENT outside 0..6
 // a[b] = acc_init[b] (or 0) + sum over the other bodies in the reference order; SoA [3][npad] output
@@ -146,10 +157,6 @@ struct SrknSmallArgs {
     double hb[32], ha[32];     // h * B[s], h * A[s]: the bound of SrknCoeffs
     SampleArgs samp;           // plain kernel only
 };
-struct SrknSmallKernels {      // one evaluation order's launchers, filled in step_srkn_small.hip
-    int (*srkn_small)(hipStream_t, const SrknSmallArgs &, int64_t);
-    int (*srkn_double_small)(hipStream_t, const SrknSmallArgs &, int64_t);
-};
 int launch_srkn_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
 int launch_srkn_double_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
 // opt-in fast path: slice-parallel partial sums combined in slice order (NOT the reference's summation order)
@@ -170,12 +177,7 @@ int launch_lm_step_fast(int pv, hipStream_t s, const LmArgs &a, double *partial,
 struct CraftArgs;
 struct CraftLaunch { bool wave_form, queue, occ2; long long resident_waves; };
 int launch_craft(int pv, hipStream_t s, const CraftArgs &a, const CraftLaunch &how);
-// test hooks: 1/(x*sqrt(x)) and a/(x*sqrt(x)) through the in-range sequences and through the compiler's IEEE expansions
-int launch_debug_inv_r3(int pv, hipStream_t s, int64_t n, const double *n2, double *fast, double *ieee);
-int launch_debug_inv_r3_sweep(int pv, hipStream_t s, uint64_t seed, int64_t n, unsigned long long *out2);   // rounds n up to 2^20
-int launch_debug_quot(int pv, hipStream_t s, int64_t n, const double *x, const double *a, double *fast, double *ieee);
-int debug_wg_cycles(int pv, long long *out);   // tuning builds (-DEPH_EXPERIMENTS): cycle accounting of the workgroup / small kernels
-struct PairKernels {                        // one evaluation order's launchers (pair_launchers.h), filled in step_wave.hip
+struct PairKernels {                        // one evaluation order's launchers (pair_launchers.h), filled in pair_table.hip
     int (*accel_wave)(hipStream_t, int, int, int, const Body4 *, const double *, double *, int, int, const KickDrift &);
     int (*accel_wg)(hipStream_t, int, int, int, const Body4 *, const double *, double *, int, int, const KickDrift &);
     int (*lm_step_wave)(hipStream_t, int, const LmArgs &);
@@ -184,13 +186,11 @@ struct PairKernels {                        // one evaluation order's launchers 
     int (*lm_small)(hipStream_t, const LmArgs &, int64_t);
     int (*lm_small_many)(hipStream_t, const LmArgs *, int, int, int64_t);
     int (*lm_double_small)(hipStream_t, const LmDoubleArgs &, int64_t);
+    int (*srkn_small)(hipStream_t, const SrknSmallArgs &, int64_t);
+    int (*srkn_double_small)(hipStream_t, const SrknSmallArgs &, int64_t);
     int (*lm_step_fast)(hipStream_t, const LmArgs &, double *, int, int, bool, float *, int, int, int, unsigned *);
     int (*craft_launch)(hipStream_t, const CraftArgs &, const CraftLaunch &);
-    int (*debug_inv_r3)(hipStream_t, int64_t, const double *, double *, double *);
-    int (*debug_inv_r3_sweep)(hipStream_t, uint64_t, int64_t, unsigned long long *);
-    int (*debug_quot)(hipStream_t, int64_t, const double *, const double *, double *, double *);
-    int (*debug_wg_cycles)(long long *);
-    int variant;
+    int variant;                            // the order these launchers were compiled for: dispatch.cpp holds slot k to order k
 };
 // ---- launchers of the kernels without a point-mass term (solout.hip) --------------------------------------------------------------
 int launch_pack(hipStream_t s, int n, int npad, const double *Yslot, const double *mu, Body4 *pos);

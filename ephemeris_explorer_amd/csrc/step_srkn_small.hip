@@ -132,19 +132,15 @@ __global__ void __launch_bounds__(kSmallThreads) k_srkn_double_small(const SrknS
     srkn_small_steps<SrknDouble>(U, Lw, sP, a, nsteps);
 }
 
-static int srkn_small(hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
+int srkn_small(hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
     if (a.n > kSmallMaxN) return EPH_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_srkn_small, dim3(1), dim3(kSmallThreads), 0, s, a, (long long)nsteps);
     return launched("k_srkn_small");
 }
-static int srkn_double_small(hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
+int srkn_double_small(hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
     if (a.n > kSmallMaxN) return EPH_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_srkn_double_small, dim3(1), dim3(kSmallThreads), 0, s, a, (long long)nsteps);
     return launched("k_srkn_double_small");
-}
-const SrknSmallKernels *srkn_small_table() {
-    static const SrknSmallKernels t{srkn_small, srkn_double_small};
-    return &t;
 }
 
 }  // namespace EPH_PV_NS

@@ -7,8 +7,10 @@ when a kernel changes file; nothing else should). For a refactor that moves kern
     compare_kernels.py [-v] A.s B.s
     compare_kernels.py [-v] TREE_A TREE_B   # compiles SOURCES + HOOKS_SOURCES (*.hip) of each tree's build.py with its FLAGS
     compare_kernels.py [-v] --pair step_wg.hip [--pair ...] TREE_A TREE_B
-                                            # instead: these units of PAIR_SOURCES, once per evaluation order
-                                            # (-DEPH_PAIR_VARIANT=k, k < N_PAIR_VARIANTS); `--pair all`: every unit of PAIR_SOURCES
+                                            # instead: these per-order units (PAIR_SOURCES + PAIR_HOOKS_SOURCES; a tree whose
+                                            # build.py has no PAIR_HOOKS_SOURCES has none of the latter), once per evaluation
+                                            # order (-DEPH_PAIR_VARIANT=k, k < N_PAIR_VARIANTS); `--pair all`: every such unit.
+                                            # A unit named with --pair that one tree does not have counts as empty there
 
 Three verdicts per kernel:
     same       descriptor block and instruction text identical
@@ -92,13 +94,18 @@ def explain(a, b):
             print(f"        {'*' if pinned(op) else ' '} {op:<28} {ca[op]:>5} -> {cb[op]:<5}")
 
 
+def pair_units(tree):
+    """the per-order units of a source tree"""
+    b = runpy.run_path(str(Path(tree) / "ephemeris_explorer_amd" / "build.py"), run_name="build")
+    return b["PAIR_SOURCES"] + b.get("PAIR_HOOKS_SOURCES", [])
+
+
 def tree_kernels(tree, tmp, pair=()):
     """{kernel symbol: (unit, descriptor, text)} of the compiled-once .hip units of a source tree, or, with `pair`, of those
     per-order units in every evaluation order (their kernels live in one namespace per order, so the symbols stay apart)"""
     b = runpy.run_path(str(Path(tree) / "ephemeris_explorer_amd" / "build.py"), run_name="build")
     if pair:
-        srcs = b["PAIR_SOURCES"] if "all" in pair else list(pair)
-        assert set(srcs) <= set(b["PAIR_SOURCES"]), f"--pair takes units of PAIR_SOURCES: {b['PAIR_SOURCES']}"
+        srcs = [s for s in pair_units(tree) if "all" in pair or s in pair]
         jobs = [(s, k) for s in srcs for k in range(b["N_PAIR_VARIANTS"])]
     else:
         jobs = [(s, None) for s in b["SOURCES"] + b["HOOKS_SOURCES"] if s.endswith(".hip")]
@@ -127,6 +134,8 @@ def demangle(names):
 
 def main(a, b, verbose=False, pair=()):
     if Path(a).is_dir():
+        known = set(pair_units(a)) | set(pair_units(b)) | {"all"}
+        assert set(pair) <= known, f"--pair takes per-order units of either tree: {sorted(known)}"
         with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
             ka, kb = tree_kernels(a, ta, pair), tree_kernels(b, tb, pair)
     else:

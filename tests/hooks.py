@@ -1,6 +1,6 @@
 """The eph_debug_* test and tuning hooks (csrc/eph_debug.h). They are NOT in the product library: `load()` opens
-libephemeris_amd_testhooks.so (the product's objects + debug_api.o + debug_kernels.o, built by ephemeris_explorer_amd.build) or, for the scripts that
-read a tuning build's accounting, the library named by `path`. TEST INFRASTRUCTURE ONLY."""
+libephemeris_amd_testhooks.so (the product's objects + debug_api.o + debug_kernels.o + pair_debug.pv<k>.o, built by
+ephemeris_explorer_amd.build) or, for the scripts that read a tuning build's accounting, the library named by `path`. TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 from pathlib import Path
 
@@ -35,6 +35,7 @@ class Hooks:
         L.eph_debug_wg_cycles.argtypes = [C.POINTER(C.c_int64)]
         L.eph_debug_fail_alloc.argtypes = [C.c_int32]
         L.eph_debug_fast_partition.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.eph_debug_table_variants.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.eph_status_string.restype = C.c_char_p
         L.eph_status_string.argtypes = [C.c_int32]
         self.L = L
@@ -107,6 +108,13 @@ class Hooks:
         S, sl = C.c_int32(), C.c_int32()
         self._check(self.L.eph_debug_fast_partition(int(npad), int(path), C.byref(S), C.byref(sl)), "eph_debug_fast_partition")
         return S.value, sl.value
+
+    def table_variants(self):
+        """(product, debug): the evaluation order each slot of the product's launcher table and of the hooks' says it was compiled
+        for. Host only."""
+        product, debug = (C.c_int32 * 7)(), (C.c_int32 * 7)()
+        self._check(self.L.eph_debug_table_variants(product, debug), "eph_debug_table_variants")
+        return list(product), list(debug)
 
 
 _cache = {}

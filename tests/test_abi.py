@@ -171,14 +171,15 @@ def test_cpp_operator_surface_compiles_and_links(product_lib, tmp_path):
 
 
 def test_debug_hooks_are_not_in_the_product(product_lib):
-    """csrc/eph_debug.h: the nine eph_debug_* hooks are exported by the test-hooks library (the product's objects + debug_api.o + debug_kernels.o)
-    and by tuning builds, never by libephemeris_amd.so; the product exports the header's functions and no other eph_* name."""
+    """csrc/eph_debug.h: the ten eph_debug_* hooks are exported by the test-hooks library (the product's objects + debug_api.o +
+    debug_kernels.o + pair_debug.pv<k>.o, k = 0..6) and by tuning builds, never by libephemeris_amd.so; the product exports the
+    header's functions and no other eph_* name, and the per-order hook kernels (csrc/pair_debug.hip) are in no symbol of it."""
     hooks_lib = product_lib.LIB_PATH.with_name("libephemeris_amd_testhooks.so")
     assert hooks_lib.exists(), "ephemeris_explorer_amd.build builds it beside the product"
     text = (ROOT / "ephemeris_explorer_amd" / "csrc" / "eph_debug.h").read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     debug = sorted(set(re.findall(r"\b(eph_debug_[a-z0-9_]+)\s*\(", text)))
-    assert len(debug) == 9
+    assert len(debug) == 10
     assert not any(n.startswith("eph_debug") for n in header_functions())
 
     def exported(path):
@@ -191,6 +192,23 @@ def test_debug_hooks_are_not_in_the_product(product_lib):
     leaked = [ln for ln in out.splitlines() if " T " in ln and " T eph_" not in ln and "__device_stub__" not in ln]
     assert not leaked, leaked[:5]
     assert product_lib._lib().eph_abi_version() == 3
+    # the full symbol tables (the kernels' host stubs and handles are local symbols, not stripped)
+    defined = lambda path: subprocess.check_output(["nm", "--defined-only", str(path)]).decode().split()
+    assert not [s for s in defined(product_lib.LIB_PATH) if "k_debug_inv_r3" in s or "k_debug_quot" in s]
+    in_hooks = defined(hooks_lib)
+    for k in range(7):
+        for kernel in ("k_debug_inv_r3", "k_debug_inv_r3_sweep", "k_debug_quot"):
+            mangled = f"3pv{k}{len(kernel)}{kernel}E"                   # eph::pv<k>::<kernel>(
+            assert any(mangled in s for s in in_hooks), (k, kernel)
+
+
+def test_every_table_slot_holds_its_own_order(product_lib):
+    """slot k of the product's launcher table (csrc/pair_table.hip through dispatch.cpp) and of the hooks' (csrc/pair_debug.hip
+    through debug_api.cpp) was compiled for evaluation order k. A host function of the hooks library: no device is touched."""
+    import sys
+    sys.path.insert(0, str(ROOT / "tests"))
+    import hooks
+    assert hooks.load().table_variants() == (list(range(7)), list(range(7)))
 
 
 def test_integration_shims_use_only_declared_names():

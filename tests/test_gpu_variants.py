@@ -183,6 +183,41 @@ def test_handles_of_different_orders_coexist(gpu):
         orc.set_pair_variant(0, native=True)
 
 
+def test_inv_r3_hook_follows_the_process_order(gpu, hooks):
+    """eph_debug_inv_r3 runs the kernel of the order eph_set_pair_variant chose (csrc/pair_debug.hip through debug_api.cpp's table):
+    in every order, 64 operands over biased exponents 722 .. 1323 -- the two ends of the guarded range of orders 0-3 (723, 1322), one
+    value just outside each end, the ends of the narrower range of orders 4-6 (890, 1155) with their outer neighbours, random
+    exponents and mantissas in between. Inside the ORDER'S OWN guarded range (csrc/pair_term.h kRangeBase / kRangeSpan: biased
+    exponents [723, 1323) in orders 0-3, [890, 1156) in orders 4-6) `fast` is `ieee` bit for bit, outside it `fast` is NaN: a hook
+    that ran another order's kernel would show the other family's NaN pattern, or another order's bits in `ieee`."""
+    import numpy as np
+    rng = np.random.default_rng(20261021)
+    expo = np.concatenate([[722, 723, 1322, 1323, 889, 890, 1155, 1156], rng.integers(724, 1322, 56)]).astype(np.uint64)
+    mant = rng.integers(0, 1 << 52, 64, dtype=np.uint64)
+    mant[:8:2] = 0                                         # the lowest value of a binade at each lower end ...
+    mant[1:8:2] = (1 << 52) - 1                            # ... and the highest at each upper end
+    x = ((expo << np.uint64(52)) | mant).view(np.float64)
+    ieee_of = {}
+    try:
+        for k in range(7):
+            hooks.set_pair_variant(k)
+            fast, ieee = hooks.debug_inv_r3(x)
+            lo, hi = (890, 1156) if k >= 4 else (723, 1323)
+            inside = (expo >= lo) & (expo < hi)
+            assert inside.sum() >= 2 and (~inside).sum() >= 2
+            assert _same(fast[inside], ieee[inside]), k
+            assert np.isnan(fast[~inside]).all(), k
+            assert np.isfinite(ieee).all(), k
+            ieee_of[k] = ieee
+    finally:
+        hooks.set_pair_variant(0)
+    # 1/(x sqrt x) in orders 0, 4, 5, 6; three other expressions in orders 1, 2, 3 (inv_r3_ieee)
+    for k in (4, 5, 6):
+        assert _same(ieee_of[k], ieee_of[0]), k
+    for k in (1, 2, 3):
+        assert not _same(ieee_of[k], ieee_of[0]), k
+
+
 def test_seeded_quotient_on_hard_cases(gpu, hooks):
     """a / p, p = x sqrt(x), through r = RN(1/p) and Markstein's step against the device's IEEE division: numerators whose
     quotient lies k 2^-106 / p' from a rounding boundary (k = 1, 2, 3, 5), and random ones"""
