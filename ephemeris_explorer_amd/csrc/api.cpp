@@ -244,18 +244,19 @@ int32_t eph_rccl_unique_id(void *out128) {
     return rccl_unique_id(out128);
     EPH_GUARD_END
 }
+// what both shard entry points do first: the handle, the <Double> refusal (before any communicator is made), the handle's device current
+static int shard_preamble(eph_nbody *h) {
+    if (!h || !h->p) return EPH_ERR_BAD_ARGUMENT;
+    if (const int st = h->p->shard_refusal()) return st;
+    return hipSetDevice(h->p->device()) == hipSuccess ? EPH_OK : EPH_ERR_HIP;
+}
 int32_t eph_nbody_shard(eph_nbody *h, int32_t rank, int32_t world, const void *rccl_unique_id, eph_exchange_fn fn,
                         void *ctx) {
     EPH_GUARD_BEGIN
-    if (!h || !h->p) return EPH_ERR_BAD_ARGUMENT;
-    if (h->p->compensated()) {                          // before any communicator is made
-        set_last_error_text("a <Double> handle is not sharded: the error parts of the state have no exchange");
-        return EPH_ERR_UNSUPPORTED;
-    }
-    if (hipSetDevice(h->p->device()) != hipSuccess) return EPH_ERR_HIP;
-    std::shared_ptr<Exchange> x;
-    int st = Exchange::create(rank, world, rccl_unique_id, fn, ctx, &x);
+    int st = shard_preamble(h);
     if (st) return st;
+    std::shared_ptr<Exchange> x;
+    if ((st = Exchange::create(rank, world, rccl_unique_id, fn, ctx, &x))) return st;
     return h->p->set_shard(std::move(x));
     EPH_GUARD_END
 }
@@ -314,15 +315,11 @@ int32_t eph_peer_destroy(eph_peer *p) {
 }
 int32_t eph_nbody_shard_peer(eph_nbody *h, eph_peer *p) {
     EPH_GUARD_BEGIN
-    if (!h || !h->p || !p || !p->t) return EPH_ERR_BAD_ARGUMENT;
-    if (h->p->compensated()) {
-        set_last_error_text("a <Double> handle is not sharded: the error parts of the state have no exchange");
-        return EPH_ERR_UNSUPPORTED;
-    }
-    if (hipSetDevice(h->p->device()) != hipSuccess) return EPH_ERR_HIP;
-    std::shared_ptr<Exchange> x;
-    int st = Exchange::create_peer(p->t, &x);
+    if (!p || !p->t) return EPH_ERR_BAD_ARGUMENT;
+    int st = shard_preamble(h);
     if (st) return st;
+    std::shared_ptr<Exchange> x;
+    if ((st = Exchange::create_peer(p->t, &x))) return st;
     return h->p->set_shard(std::move(x));
     EPH_GUARD_END
 }

@@ -172,9 +172,34 @@ private:
 };
 int rccl_unique_id(void *out128);
 
+// The scalar bookkeeping of an NBodyIntegration: what a clone takes from its source in ONE assignment (a member added here travels;
+// one added to the class itself -- timing, sampling, the gang's members, anything per stream -- does not).
+struct NBodyBook {
+    int device_ = 0;
+    int n_ = 0, npad_ = 0, L_ = 1;
+    int lo_ = 0, hi_ = 0, slice_ = 0;         // owned targets [lo_, hi_); slice_ = npad_ / world when sharded
+    std::shared_ptr<Exchange> xch_;           // (a clone of a sharded handle shares the ranks)
+    bool is_multistep_ = false;
+    bool compensated_ = false;                // a `<Double>` handle
+    Elm2Coeffs lm_{};
+    SrknCoeffs rk_{};
+    int substeps_ = 1;
+    double h_ = 0, h_sub_ = 0;
+    double time_ = 0, bound_ = 0;
+    uint32_t starter_i_ = 0, lm_i_ = 0;       // SRKN.i (inner RK steps), ELM2.i
+    uint64_t evals_ = 0;
+    int cur_ = 0, pp_ = 0;
+    int path_ = 0;
+    int pv_ = 0;                              // evaluation order of the point-mass term, fixed at creation (dispatch.cpp)
+    // the last fused step of a batch left the NEXT step's predicted positions in P_[pp_ ^ 1] and in the ring slot the next step
+    // takes (the oldest level's, dead by then): the next batch starts with its force evaluation instead of a predictor launch
+    bool predicted_ = false;
+    int failed_ = EPH_OK;                     // sticky: a gang launch failed with this handle's bookkeeping already advanced
+};
+
 // Integration<NBodyProblem<DVec3>, M>: problem + integrator   (integration/src/lib.rs:394-503,
 // ephemeris/src/propagators/nbody.rs:41,93-121)
-class NBodyIntegration {
+class NBodyIntegration : private NBodyBook {
 public:
     ~NBodyIntegration();
     static int create(int n, const double *pos, const double *vel, const double *mu, double t0, double h,
@@ -209,6 +234,7 @@ public:
     void set_sampling(const SampleArgs &s) { samp_ = s; }   // consumed by the next advance() batch
     // target-partition the system over the ranks of `x`: this rank keeps bodies [lo, hi) current
     int set_shard(std::shared_ptr<Exchange> x);
+    int shard_refusal() const;                // EPH_ERR_UNSUPPORTED with its text for a `<Double>` handle (before an exchange is made)
     bool sharded() const { return (bool)xch_; }
     int exchange_error() const { return xch_ ? xch_->poll_error() : EPH_OK; }   // EPH_ERR_COMM once a peer wait timed out
     int shard_lo() const { return lo_; }
@@ -239,6 +265,7 @@ public:
 
 private:
     NBodyIntegration() = default;
+    int open_device();                        // the handle's stream, its two events and its buffers (create and clone)
     int alloc_buffers();
     int startup_macro_step();                 // one LinearMultistepIntegrator::advance in the start-up regime
     int srkn_step(double h, double *y_slot);  // FixedRungeKuttaIntegrator::advance (SRKN)
@@ -246,16 +273,21 @@ private:
     bool srkn_small_ready() const { return !is_multistep_ && n_ >= 1 && n_ <= kGangMaxN && !sharded() && (path_ == 0 || path_ == 2); }
     int lm_batch(int64_t k);                  // k steady-state ELM2::advance
     int lm_batch_double(int64_t k);           // the same on a `<Double>` handle
+    template <typename Queue>
+    int batch_frame(int64_t k, Queue &&queue);   // what the three batches share around their launches (nbody.cpp)
     void fill_lm_args(LmArgs &a) const;       // the fields of a batch's launch arguments that both set
+    void point_lm_args(LmArgs &a) const;      // the level a step starts from: ring slot and the two packed position buffers
+    void next_level(LmArgs &a);               // one step on: the ring turns, the position buffers swap
     int srkn_stage_double(double hb, double ha, double *y_slot, double *ye_slot, bool eval);
     double *YEslot(int s) { return YE_.p + (size_t)s * 3 * npad_; }
     double *Yslot(int s) { return Y_.p + (size_t)s * 3 * npad_; }
     double *Aslot(int s) { return A_.p + (size_t)s * 3 * npad_; }
 
     int gather_packed(Body4 *buf);            // all-gather the ranks' slices of a packed position buffer
-    int gather_stage();                       // same for the AoS staging buffer (get_state / get_acc)
+    int gather_stage();                       // same for the AoS staging buffer (read_back)
+    // up to two SoA [3][npad] device arrays to host AoS [n][3] (a null host pointer: not asked for); n_ > 0 and one of them asked for
+    int read_back(const double *a_dev, double *a, const double *b_dev, double *b);
 
-    int device_ = 0;
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     // enable_timing: every batch of steps is bracketed by a pair of events that is read LATER (kernel_ms(), or when 1024 pairs
@@ -263,43 +295,46 @@ private:
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending_, ev_free_;
     int resolve_timing();
     struct TimingGuard;                       // one such interval, opened and closed by a batch (nbody.cpp)
-    // the last fused step of a batch left the NEXT step's predicted positions in P_[pp_ ^ 1] and in the ring slot the next step
-    // takes (the oldest level's, dead by then): the next batch starts with its force evaluation instead of a predictor launch
-    bool predicted_ = false;
-    int n_ = 0, npad_ = 0, L_ = 1;
-    int lo_ = 0, hi_ = 0, slice_ = 0;         // owned targets [lo_, hi_); slice_ = npad_ / world when sharded
-    std::shared_ptr<Exchange> xch_;
-    bool is_multistep_ = false;
-    Elm2Coeffs lm_{};
-    SrknCoeffs rk_{};
-    int substeps_ = 1;
-    double h_ = 0, h_sub_ = 0;
-    double time_ = 0, bound_ = 0;
-    uint32_t starter_i_ = 0, lm_i_ = 0;   // SRKN.i (inner RK steps), ELM2.i
-    uint64_t evals_ = 0;
-    int cur_ = 0, pp_ = 0;
-    int path_ = 0;
     bool timing_ = false;
     double kernel_ms_ = 0;
     uint64_t kernel_launches_ = 0;
     SampleArgs samp_{};
+
+    // ---- The handle's device buffers, stated once ---------------------------------------------------------------------------------
+    // for_each_buffer names every DevBuf member with its element count and its kind; alloc_buffers and the copy half of clone are
+    // walks over it. A NEW BUFFER IS ADDED HERE AND TO THAT LIST AND NOWHERE ELSE. The error parts exist on a `<Double>` handle alone:
+    // those of the y ring (same slots as Y_) and of the current velocity; the accelerations have none. The SRKN working position is
+    // the ring slot under construction (slot 0 of an SRKN method), so its error part is that slot of YE_.
     DevBuf<Body4> P_[2];
-    DevBuf<double> Y_, A_, V_, ASR_, mu_, stage_;
-    // `<Double>` handles only (allocated, zeroed and cloned on them alone): the error parts of the y ring (same slots as Y_) and of
-    // the current velocity. The accelerations have none. The SRKN working position is the ring slot under construction (slot 0 of an
-    // SRKN method), so its error part is that slot of YE_.
-    bool compensated_ = false;
-    DevBuf<double> YE_, VE_;
-    DevBuf<double> fast_partial_;             // EPH_PATH_FAST scratch: [S][3][npad] partial sums
-    DevBuf<float> posf_;                      // EPH_PATH_F32_PAIRS scratch: the level's positions and mu as 4 floats per body
+    DevBuf<double> Y_, A_, V_, ASR_, mu_, stage_, YE_, VE_;
+    DevBuf<double> fast_partial_;             // the fast paths' [S][3][npad] partial sums and arrival tickets
+    DevBuf<float> posf_;                      // EPH_PATH_F32_PAIRS: the level's positions and mu as 4 floats per body
+    DevBuf<LmArgs> gang_args_;                // advance_many: the argument array of the gang this handle leads
+    // state: allocated at creation, zeroed, copied by clone | scratch: allocated at creation, contents nobody's | lazy: allocated where
+    // it is first used (lm_batch, advance_many), neither zeroed nor copied
+    enum class Buf { state, scratch, lazy };
+    template <typename F>   // f(accessor: handle -> its member, element count on g, kind), in allocation order, until a status other than EPH_OK
+    static int for_each_buffer(const NBodyIntegration &g, F &&f) {
+        const size_t bodies = (size_t)g.npad_, vec = 3 * bodies, ring = (size_t)g.L_ * vec;
+#define EPH_NBODY_BUF(member) [](NBodyIntegration &x) -> auto & { return x.member; }
+        int st;
+        (void)((st = f(EPH_NBODY_BUF(P_[0]), bodies, Buf::state)) || (st = f(EPH_NBODY_BUF(P_[1]), bodies, Buf::state)) ||
+               (st = f(EPH_NBODY_BUF(Y_), ring, Buf::state)) || (st = f(EPH_NBODY_BUF(A_), ring, Buf::state)) ||
+               (st = f(EPH_NBODY_BUF(V_), vec, Buf::state)) || (st = f(EPH_NBODY_BUF(ASR_), vec, Buf::state)) ||
+               (st = f(EPH_NBODY_BUF(mu_), bodies, Buf::state)) || (st = f(EPH_NBODY_BUF(stage_), vec, Buf::scratch)) ||
+               (g.compensated_ && ((st = f(EPH_NBODY_BUF(YE_), ring, Buf::state)) || (st = f(EPH_NBODY_BUF(VE_), vec, Buf::state)))) ||
+               (st = f(EPH_NBODY_BUF(fast_partial_), fast_partial_doubles(g.npad_), Buf::lazy)) ||
+               (st = f(EPH_NBODY_BUF(posf_), 4 * bodies, Buf::lazy)) ||
+               (st = f(EPH_NBODY_BUF(gang_args_), (size_t)0, Buf::lazy)));                 // (one LmArgs per system of the gang)
+#undef EPH_NBODY_BUF
+        return st;
+    }
+
     int64_t deferred_time_steps_ = 0;         // advance_many: `time = time + h` replays still owed (run after the gang's launch)
     std::vector<LmArgs> *collect_ = nullptr;  // advance_many: lm_batch hands its launch arguments over instead of launching
-    DevBuf<LmArgs> gang_args_;                // advance_many: the argument array of the gang this handle leads
     hipEvent_t gang_ev_ = nullptr, gang_copy_ev_ = nullptr;
     LmArgs *gang_host_ = nullptr;             // pinned source of the gang's argument copy (so advance_many need not wait for it)
     size_t gang_host_count_ = 0;
-    int pv_ = 0;                              // evaluation order of the point-mass term, fixed at creation (dispatch.cpp)
-    int failed_ = EPH_OK;                     // sticky: a gang launch failed with this handle's bookkeeping already advanced
 };
 
 // Polynomial<DVec3> (SmallVec<[DVec3; 8]>)   ephemeris/src/trajectory.rs:337-396

@@ -37,29 +37,20 @@ NBodyIntegration::~NBodyIntegration() {
 int NBodyIntegration::alloc_buffers() {
     npad_ = ((n_ + 63) / 64) * 64;
     if (npad_ < 64) npad_ = 64;
-    int st;
-    for (int k = 0; k < 2; ++k)
-        if ((st = P_[k].alloc(npad_))) return st;
-    if ((st = Y_.alloc((size_t)L_ * 3 * npad_))) return st;
-    if ((st = A_.alloc((size_t)L_ * 3 * npad_))) return st;
-    if ((st = V_.alloc((size_t)3 * npad_))) return st;
-    if ((st = ASR_.alloc((size_t)3 * npad_))) return st;
-    if ((st = mu_.alloc(npad_))) return st;
-    if ((st = stage_.alloc((size_t)3 * npad_))) return st;
-    EPH_HIP(hipMemsetAsync(P_[0].p, 0, sizeof(Body4) * npad_, stream_));
-    EPH_HIP(hipMemsetAsync(P_[1].p, 0, sizeof(Body4) * npad_, stream_));
-    EPH_HIP(hipMemsetAsync(Y_.p, 0, sizeof(double) * Y_.count, stream_));
-    EPH_HIP(hipMemsetAsync(A_.p, 0, sizeof(double) * A_.count, stream_));
-    EPH_HIP(hipMemsetAsync(V_.p, 0, sizeof(double) * V_.count, stream_));
-    EPH_HIP(hipMemsetAsync(ASR_.p, 0, sizeof(double) * ASR_.count, stream_));
-    EPH_HIP(hipMemsetAsync(mu_.p, 0, sizeof(double) * mu_.count, stream_));
-    if (compensated_) {                                   // Double::new(x): error +0.0
-        if ((st = YE_.alloc((size_t)L_ * 3 * npad_))) return st;
-        if ((st = VE_.alloc((size_t)3 * npad_))) return st;
-        EPH_HIP(hipMemsetAsync(YE_.p, 0, sizeof(double) * YE_.count, stream_));
-        EPH_HIP(hipMemsetAsync(VE_.p, 0, sizeof(double) * VE_.count, stream_));
-    }
-    return EPH_OK;
+    return for_each_buffer(*this, [&](auto buf, size_t count, Buf kind) -> int {
+        if (kind == Buf::lazy) return EPH_OK;
+        auto &b = buf(*this);
+        if (const int st = b.alloc(count)) return st;
+        if (kind == Buf::state) EPH_HIP(hipMemsetAsync(b.p, 0, sizeof(*b.p) * b.count, stream_));   // (Double::new(x): error +0.0)
+        return EPH_OK;
+    });
+}
+
+int NBodyIntegration::open_device() {
+    EPH_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    EPH_HIP(hipEventCreate(&ev0_));
+    EPH_HIP(hipEventCreate(&ev1_));
+    return alloc_buffers();
 }
 
 int NBodyIntegration::create(int n, const double *pos, const double *vel, const double *mu, double t0, double h,
@@ -93,10 +84,7 @@ int NBodyIntegration::create(int n, const double *pos, const double *vel, const 
     o->bound_ = INFINITY;   // nbody.rs:111
     o->pv_ = default_pair_variant();
     EPH_HIP(hipGetDevice(&o->device_));
-    EPH_HIP(hipStreamCreateWithFlags(&o->stream_, hipStreamNonBlocking));
-    EPH_HIP(hipEventCreate(&o->ev0_));
-    EPH_HIP(hipEventCreate(&o->ev1_));
-    if ((st = o->alloc_buffers())) return st;
+    if ((st = o->open_device())) return st;
     o->lo_ = 0;
     o->hi_ = n;
     if (n > 0) {
@@ -119,33 +107,19 @@ int NBodyIntegration::clone(std::unique_ptr<NBodyIntegration> *out) {
     EPH_HIP(hipSetDevice(device_));
     EPH_HIP(hipStreamSynchronize(stream_));
     std::unique_ptr<NBodyIntegration> o(new NBodyIntegration());
-    o->device_ = device_;
-    o->n_ = n_; o->L_ = L_;
-    o->is_multistep_ = is_multistep_; o->lm_ = lm_; o->rk_ = rk_; o->substeps_ = substeps_;
-    o->h_ = h_; o->h_sub_ = h_sub_; o->time_ = time_; o->bound_ = bound_; o->pv_ = pv_;
-    o->starter_i_ = starter_i_; o->lm_i_ = lm_i_; o->evals_ = evals_;
-    o->cur_ = cur_; o->pp_ = pp_; o->path_ = path_; o->predicted_ = predicted_;
-    o->compensated_ = compensated_;
-    o->failed_ = failed_;                                  // (a handle a gang launch left behind its bookkeeping stays marked in its copies)
-    o->lo_ = lo_; o->hi_ = hi_; o->slice_ = slice_; o->xch_ = xch_;   // a clone of a sharded handle shares the ranks
-    EPH_HIP(hipStreamCreateWithFlags(&o->stream_, hipStreamNonBlocking));
-    EPH_HIP(hipEventCreate(&o->ev0_));
-    EPH_HIP(hipEventCreate(&o->ev1_));
-    int st = o->alloc_buffers();
+    // the bookkeeping in one assignment: a failed handle stays marked in its copies, a sharded one's clone shares the ranks
+    static_cast<NBodyBook &>(*o) = *this;
+    int st = o->open_device();
     if (st) return st;
-    hipStream_t s = o->stream_;
-    for (int k = 0; k < 2; ++k)
-        EPH_HIP(hipMemcpyAsync(o->P_[k].p, P_[k].p, sizeof(Body4) * npad_, hipMemcpyDeviceToDevice, s));
-    EPH_HIP(hipMemcpyAsync(o->Y_.p, Y_.p, sizeof(double) * Y_.count, hipMemcpyDeviceToDevice, s));
-    EPH_HIP(hipMemcpyAsync(o->A_.p, A_.p, sizeof(double) * A_.count, hipMemcpyDeviceToDevice, s));
-    EPH_HIP(hipMemcpyAsync(o->V_.p, V_.p, sizeof(double) * V_.count, hipMemcpyDeviceToDevice, s));
-    EPH_HIP(hipMemcpyAsync(o->ASR_.p, ASR_.p, sizeof(double) * ASR_.count, hipMemcpyDeviceToDevice, s));
-    EPH_HIP(hipMemcpyAsync(o->mu_.p, mu_.p, sizeof(double) * mu_.count, hipMemcpyDeviceToDevice, s));
-    if (compensated_) {                                    // the error parts travel with the clone: it continues bit-identically
-        EPH_HIP(hipMemcpyAsync(o->YE_.p, YE_.p, sizeof(double) * YE_.count, hipMemcpyDeviceToDevice, s));
-        EPH_HIP(hipMemcpyAsync(o->VE_.p, VE_.p, sizeof(double) * VE_.count, hipMemcpyDeviceToDevice, s));
-    }
-    EPH_HIP(hipStreamSynchronize(s));
+    // the state buffers (on a <Double> handle the error parts among them: the clone continues bit-identically)
+    st = for_each_buffer(*this, [&](auto buf, size_t, Buf kind) -> int {
+        if (kind != Buf::state) return EPH_OK;
+        auto &from = buf(*this), &to = buf(*o);
+        EPH_HIP(hipMemcpyAsync(to.p, from.p, sizeof(*from.p) * from.count, hipMemcpyDeviceToDevice, o->stream_));
+        return EPH_OK;
+    });
+    if (st) return st;
+    EPH_HIP(hipStreamSynchronize(o->stream_));
     *out = std::move(o);
     return EPH_OK;
 }
@@ -153,12 +127,14 @@ int NBodyIntegration::clone(std::unique_ptr<NBodyIntegration> *out) {
 // Target partition: rank r owns bodies [r*slice, (r+1)*slice) with slice = npad/world. From here on
 // only the owned bodies' history, velocities and accelerations are kept current on this rank; the packed
 // positions of ALL bodies are, through one all-gather after every kernel that publishes positions.
+int NBodyIntegration::shard_refusal() const {
+    if (!compensated_) return EPH_OK;
+    set_last_error_text("a <Double> handle is not sharded: the error parts of the state have no exchange");
+    return EPH_ERR_UNSUPPORTED;
+}
 int NBodyIntegration::set_shard(std::shared_ptr<Exchange> x) {
     if (!x || xch_) return EPH_ERR_BAD_ARGUMENT;          // a handle is sharded once, while every body is current
-    if (compensated_) {
-        set_last_error_text("a <Double> handle is not sharded: the error parts of the state have no exchange");
-        return EPH_ERR_UNSUPPORTED;
-    }
+    if (const int st = shard_refusal()) return st;
     if (n_ <= kSmallN) return EPH_ERR_UNSUPPORTED;        // one-workgroup systems: replicas only
     if (npad_ % (x->world() * kTile) != 0) {
         set_last_error_text("sharding needs the padded body count to be a multiple of 64 * world");
@@ -329,6 +305,33 @@ void NBodyIntegration::fill_lm_args(LmArgs &a) const {
     a.hc = h_ * lm_.inv_cowell_d;        // h * Ratio::from_recip(Self::BETA_D)
     a.kind = force_kind();
 }
+void NBodyIntegration::point_lm_args(LmArgs &a) const {
+    a.cur = cur_;
+    a.pos_cur = P_[pp_].p;
+    a.pos_next = P_[pp_ ^ 1].p;
+}
+void NBodyIntegration::next_level(LmArgs &a) {
+    pp_ ^= 1;
+    cur_ = (cur_ + L_ - 1) % L_;
+    point_lm_args(a);
+}
+
+// The frame of a batch of k steps, stated once for lm_batch, lm_batch_double and srkn_batch: a timed interval around the launches that
+// queue(launches) makes (it returns a status and says how many they were), then the k-fold `problem.time = problem.time + h` -- AFTER
+// the launches are queued, so that it runs under the kernel (steps_certain) -- which a gang's batch leaves to advance_many.
+template <typename Queue>
+int NBodyIntegration::batch_frame(int64_t k, Queue &&queue) {
+    int st;
+    TimingGuard timing{*this};
+    if ((st = timing.open())) return st;
+    uint64_t launches = 0;
+    if ((st = queue(launches))) return st;
+    if (timing_) kernel_launches_ += launches;
+    if ((st = timing.close())) return st;
+    if (collect_) deferred_time_steps_ += k;              // advance_many replays them once the gang is launched
+    else for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;
+    return EPH_OK;
+}
 
 // k x ELM2::advance on Double. At most 32 bodies (and not path 1): ONE launch of the single-workgroup kernel. Otherwise, per step,
 // the predictor of the next level, the force-only launch on its values, Cowell's velocity -- the last two element-wise pieces of
@@ -345,35 +348,29 @@ int NBodyIntegration::lm_batch_double(int64_t k) {
         return EPH_ERR_UNSUPPORTED;
     }
     const bool persistent = n_ <= kGangMaxN && path_ != 1;
-    int st;
-    TimingGuard timing{*this};
-    if ((st = timing.open())) return st;
-    a.cur = cur_;
-    a.pos_cur = P_[pp_].p;
-    a.pos_next = P_[pp_ ^ 1].p;
-    if (persistent) {
-        if ((st = launch_lm_double_small(pv_, stream_, d, k))) return st;
-        cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
-        if (timing_) kernel_launches_ += 1;
-    } else {
+    const int st = batch_frame(k, [&](uint64_t &launches) -> int {
+        int st;
+        point_lm_args(a);
+        if (persistent) {
+            if ((st = launch_lm_double_small(pv_, stream_, d, k))) return st;
+            cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
+            launches = 1;
+            return EPH_OK;
+        }
         a.do_predict = 1;
         d.do_cowell = 0;
         if ((st = launch_lm_double_step(stream_, d))) return st;       // the first step's predictor alone
         for (int64_t s = 1; s <= k; ++s) {
-            pp_ ^= 1;
-            cur_ = (cur_ + L_ - 1) % L_;
+            next_level(a);
             if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(cur_), force_kind(), 0, n_))) return st;
-            a.cur = cur_;
-            a.pos_cur = P_[pp_].p;
-            a.pos_next = P_[pp_ ^ 1].p;
             a.do_predict = s < k;
             d.do_cowell = 1;
             if ((st = launch_lm_double_step(stream_, d))) return st;
         }
-        if (timing_) kernel_launches_ += (uint64_t)k;
-    }
-    if ((st = timing.close())) return st;
-    for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;               // problem.time = problem.time + h, per step
+        launches = (uint64_t)k;
+        return EPH_OK;
+    });
+    if (st) return st;
     lm_i_ += (uint32_t)k;
     evals_ += (uint64_t)k;
     return EPH_OK;
@@ -406,17 +403,16 @@ int NBodyIntegration::lm_batch(int64_t k) {
     const bool persistent = n_ <= kSmallN && path_ != 1 && path_ != 3 && !fast;
     if (path_ == 2 && n_ > kSmallN) return EPH_ERR_UNSUPPORTED;
     if (collect_ && !persistent) return EPH_ERR_UNSUPPORTED;           // (advance_many checks gang_ready first)
-    TimingGuard timing{*this};
-    if ((st = timing.open())) return st;
-    a.cur = cur_;
-    a.pos_cur = P_[pp_].p;
-    a.pos_next = P_[pp_ ^ 1].p;
-    if (persistent) {
-        if (collect_) collect_->push_back(a);                           // launched by advance_many with the gang's others
-        else if ((st = launch_lm_persistent(pv_, stream_, a, k))) return st;
-        cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
-        if (timing_) kernel_launches_ += 1;
-    } else {
+    st = batch_frame(k, [&](uint64_t &launches) -> int {
+        int st;
+        point_lm_args(a);
+        if (persistent) {
+            if (collect_) collect_->push_back(a);                           // launched by advance_many with the gang's others
+            else if ((st = launch_lm_persistent(pv_, stream_, a, k))) return st;
+            cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
+            launches = 1;
+            return EPH_OK;
+        }
         // a handle that can neither take the single-workgroup kernels nor exchange positions leaves the prediction of the step
         // after the batch behind (host.h predicted_): one launch and one launch boundary less per call
         const bool leave_prediction = n_ > kSmallN && !sharded();
@@ -426,11 +422,7 @@ int NBodyIntegration::lm_batch(int64_t k) {
         }
         predicted_ = false;
         for (int64_t s = 1; s <= k; ++s) {
-            pp_ ^= 1;
-            cur_ = (cur_ + L_ - 1) % L_;
-            a.cur = cur_;
-            a.pos_cur = P_[pp_].p;
-            a.pos_next = P_[pp_ ^ 1].p;
+            next_level(a);
             a.do_predict = s < k || leave_prediction;
             a.step = (uint32_t)s;
             if (f32_sharded) {
@@ -449,11 +441,10 @@ int NBodyIntegration::lm_batch(int64_t k) {
             if (s < k && (st = gather_packed(a.pos_next))) return st;
         }
         predicted_ = leave_prediction;
-        if (timing_) kernel_launches_ += (uint64_t)k;
-    }
-    if ((st = timing.close())) return st;
-    if (collect_) deferred_time_steps_ += k;              // advance_many replays them once the gang is launched
-    else for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;   // problem.time = problem.time + h, per step (the launch is already queued)
+        launches = (uint64_t)k;
+        return EPH_OK;
+    });
+    if (st) return st;
     lm_i_ += (uint32_t)k;
     evals_ += (uint64_t)k;
     return EPH_OK;
@@ -471,14 +462,12 @@ int NBodyIntegration::srkn_batch(int64_t k) {
     a.YE = compensated_ ? YEslot(0) : nullptr; a.VE = compensated_ ? VE_.p : nullptr;
     for (int s = 0; s < rk_.stages; ++s) { a.hb[s] = h_ * rk_.B[s]; a.ha[s] = h_ * rk_.A[s]; }
     a.samp = samp_;
-    int st;
-    TimingGuard timing{*this};
-    if ((st = timing.open())) return st;
-    if ((st = compensated_ ? launch_srkn_double_small(pv_, stream_, a, k) : launch_srkn_small(pv_, stream_, a, k))) return st;
-    if (timing_) kernel_launches_ += 1;
-    if ((st = timing.close())) return st;
-    // the bookkeeping of k calls of srkn_step (the launch is already queued)
-    for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;
+    const int st = batch_frame(k, [&](uint64_t &launches) -> int {
+        launches = 1;
+        return compensated_ ? launch_srkn_double_small(pv_, stream_, a, k) : launch_srkn_small(pv_, stream_, a, k);
+    });
+    if (st) return st;
+    // the rest of the bookkeeping of k calls of srkn_step
     const uint64_t per_step = (uint64_t)(rk_.fsal ? rk_.stages - 1 : rk_.stages);
     evals_ += (uint64_t)k * per_step + (rk_.fsal && starter_i_ == 0 ? 1 : 0);
     starter_i_ += (uint32_t)k;
@@ -492,52 +481,39 @@ int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
     int st = EPH_OK;
     const SampleArgs samp = samp_;
     while (done < n_steps) {
-        if (srkn_small_ready() && !(done > 0 && samp.period)) {
-            // at most 32 bodies: the steps that can be taken, in one launch (the kernel's sampling countdown starts at this
-            // advance()'s first step, so a sampled call that comes round again -- more than 2^30 steps -- finishes below)
-            int after = EPH_OK;
-            int64_t want = n_steps - done;
-            if (want > (int64_t)1 << 30) want = (int64_t)1 << 30;
-            const int64_t k = steps_available(want, &after);
-            if (k > 0) {
-                if ((st = srkn_batch(k))) break;
-                done += k;
-            }
-            if (k < want) { st = after; break; }
-        } else if (!is_multistep_) {
+        // An SRKN method at no more than 32 bodies takes its steps in one launch. The kernel's sampling countdown starts at this
+        // advance()'s first step, so a sampled call that comes round again -- more than 2^30 steps -- finishes step by step.
+        const bool srkn_small = srkn_small_ready() && !(done > 0 && samp.period);
+        if (!is_multistep_ && !srkn_small) {
             if ((st = srkn_step(h_, Yslot(0)))) break;
             done++;
             if ((st = launch_sample(stream_, n_, npad_, Yslot(0), samp, (uint32_t)done))) break;
-        } else if (!started()) {
+        } else if (is_multistep_ && !started()) {
             if ((st = startup_macro_step())) break;
             done++;
             if ((st = launch_sample(stream_, n_, npad_, Yslot(cur_), samp, (uint32_t)done))) break;
         } else {
+            // the batching regimes: the steps that can be taken, below 2^31 at a time (the single-workgroup kernels take a 32-bit
+            // step index for sampling)
             int after = EPH_OK;
-            // the persistent kernel takes a 32-bit step index for sampling; keep batches below 2^31
-            int64_t want = n_steps - done;
-            if (want > (int64_t)1 << 30) want = (int64_t)1 << 30;
+            const int64_t want = std::min<int64_t>(n_steps - done, (int64_t)1 << 30);
             const int64_t k = steps_available(want, &after);
-            if (k > 0) {
-                // sampling phases are relative to the start of this advance(): shift them past the steps
-                // already taken in the other regimes by running the batch with a step offset of `done`
-                if (done > 0 && samp.period) {
-                    // rare (start-up and steady state in one call): finish one step at a time
-                    SampleArgs none{};
-                    samp_ = none;
-                    for (int64_t s = 0; s < k && !st; ++s) {
-                        st = lm_batch(1);
-                        if (!st) {
-                            done++;
-                            st = launch_sample(stream_, n_, npad_, Yslot(cur_), samp, (uint32_t)done);
-                        }
+            if (k > 0 && is_multistep_ && done > 0 && samp.period) {
+                // Sampling phases are relative to the start of this advance(). Start-up and steady state in one sampled call
+                // (rare): finish one step at a time, sampling between the batches
+                samp_ = SampleArgs{};
+                for (int64_t s = 0; s < k && !st; ++s) {
+                    st = lm_batch(1);
+                    if (!st) {
+                        done++;
+                        st = launch_sample(stream_, n_, npad_, Yslot(cur_), samp, (uint32_t)done);
                     }
-                    samp_ = samp;
-                    if (st) break;
-                } else {
-                    if ((st = lm_batch(k))) break;
-                    done += k;
                 }
+                samp_ = samp;
+                if (st) break;
+            } else if (k > 0) {
+                if ((st = srkn_small ? srkn_batch(k) : lm_batch(k))) break;
+                done += k;
             }
             if (k < want) { st = after; break; }
         }
@@ -640,42 +616,44 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
     return EPH_OK;                                                      // not synchronised: like eph_nbody_advance, the call only queues
 }
 
-int NBodyIntegration::get_state(double *pos, double *vel, double *t, uint32_t *sc) {
-    EPH_HIP(hipSetDevice(device_));
+// The read-back of get_state and get_acc. One device: the transposition kernels write straight into a pinned, device-mapped staging
+// buffer of this call's own (a second handle's read-back does not wait for ours) -- one synchronisation, no copy-engine submissions
+// (the reference's Integration reads the state after every step: 115-119 -> 63 us per step at N = 4096 with this,
+// scripts/time_boundary.py). Sharded: every rank contributes its bodies to stage_, array by array.
+int NBodyIntegration::read_back(const double *a_dev, double *a, const double *b_dev, double *b) {
+    const double *const dev[2] = {a_dev, b_dev};
+    double *const host[2] = {a, b};
+    const size_t nd = 3 * (size_t)n_;
     int st;
-    if (!xch_ && n_ > 0 && (pos || vel)) {
-        // one device: the two transposition kernels write straight into the pinned, device-mapped staging buffer -- one
-        // synchronisation, no copy-engine submissions (the reference's Integration reads the state after every step: 115-119 -> 63 us
-        // per step at N = 4096 with this, scripts/time_boundary.py)
-        const size_t nd = (size_t)n_;
-        PinnedStage stage(sizeof(double) * 6 * nd);       // this call's own buffer: a second handle's read-back does not wait for ours
+    if (!xch_) {
+        PinnedStage stage(sizeof(double) * nd * ((a ? 1 : 0) + (b ? 1 : 0)));
         if (stage.status()) return stage.status();
         StreamIdleOnExit idle(stream_);
-        double *h = static_cast<double *>(stage.host()), *d = static_cast<double *>(stage.dev());
-        if (pos && (st = launch_soa_to_aos(stream_, n_, npad_, Yslot(is_multistep_ ? cur_ : 0), d))) return st;
-        if (vel && (st = launch_soa_to_aos(stream_, n_, npad_, V_.p, d + 3 * nd))) return st;
+        double *d = static_cast<double *>(stage.dev());
+        for (int i = 0; i < 2; ++i)
+            if (host[i]) { if ((st = launch_soa_to_aos(stream_, n_, npad_, dev[i], d))) return st; d += nd; }
         EPH_HIP(hipStreamSynchronize(stream_));
         idle.disarm();
-        if (pos) std::memcpy(pos, h, sizeof(double) * 3 * nd);
-        if (vel) std::memcpy(vel, h + 3 * nd, sizeof(double) * 3 * nd);
-        if (t) *t = time_;
-        if (sc) *sc = step_count();
+        const double *h = static_cast<const double *>(stage.host());
+        for (int i = 0; i < 2; ++i)
+            if (host[i]) { std::memcpy(host[i], h, sizeof(double) * nd); h += nd; }
         return EPH_OK;
     }
-    if (pos && n_ > 0) {
-        if ((st = launch_soa_to_aos(stream_, n_, npad_, Yslot(is_multistep_ ? cur_ : 0), stage_.p))) return st;
-        if ((st = gather_stage())) return st;               // sharded: every rank contributes its bodies
-        EPH_HIP(hipMemcpyAsync(pos, stage_.p, sizeof(double) * 3 * n_, hipMemcpyDeviceToHost, stream_));
-        EPH_HIP(hipStreamSynchronize(stream_));
-        if (xch_ && (st = xch_->poll_error())) return st;    // a peer that never delivered: the gathered rows are not data
-    }
-    if (vel && n_ > 0) {
-        if ((st = launch_soa_to_aos(stream_, n_, npad_, V_.p, stage_.p))) return st;
+    for (int i = 0; i < 2; ++i) {
+        if (!host[i]) continue;
+        if ((st = launch_soa_to_aos(stream_, n_, npad_, dev[i], stage_.p))) return st;
         if ((st = gather_stage())) return st;
-        EPH_HIP(hipMemcpyAsync(vel, stage_.p, sizeof(double) * 3 * n_, hipMemcpyDeviceToHost, stream_));
+        EPH_HIP(hipMemcpyAsync(host[i], stage_.p, sizeof(double) * nd, hipMemcpyDeviceToHost, stream_));
         EPH_HIP(hipStreamSynchronize(stream_));
-        if (xch_ && (st = xch_->poll_error())) return st;
+        if ((st = xch_->poll_error())) return st;          // a peer that never delivered: the gathered rows are not data
     }
+    return EPH_OK;
+}
+
+int NBodyIntegration::get_state(double *pos, double *vel, double *t, uint32_t *sc) {
+    EPH_HIP(hipSetDevice(device_));
+    if (n_ > 0 && (pos || vel))
+        if (const int st = read_back(Yslot(is_multistep_ ? cur_ : 0), pos, V_.p, vel)) return st;
     if (t) *t = time_;
     if (sc) *sc = step_count();
     return EPH_OK;
@@ -684,23 +662,7 @@ int NBodyIntegration::get_state(double *pos, double *vel, double *t, uint32_t *s
 int NBodyIntegration::get_acc(double *acc) {
     EPH_HIP(hipSetDevice(device_));
     if (!acc) return EPH_ERR_BAD_ARGUMENT;
-    if (n_ == 0) return EPH_OK;
-    int st;
-    if (!xch_) {                                          // as get_state: through the pinned, device-mapped staging buffer
-        PinnedStage stage(sizeof(double) * 3 * (size_t)n_);
-        if (stage.status()) return stage.status();
-        StreamIdleOnExit idle(stream_);
-        if ((st = launch_soa_to_aos(stream_, n_, npad_, is_multistep_ ? Aslot(cur_) : ASR_.p, static_cast<double *>(stage.dev())))) return st;
-        EPH_HIP(hipStreamSynchronize(stream_));
-        idle.disarm();
-        std::memcpy(acc, stage.host(), sizeof(double) * 3 * (size_t)n_);
-        return EPH_OK;
-    }
-    if ((st = launch_soa_to_aos(stream_, n_, npad_, is_multistep_ ? Aslot(cur_) : ASR_.p, stage_.p))) return st;
-    if ((st = gather_stage())) return st;
-    EPH_HIP(hipMemcpyAsync(acc, stage_.p, sizeof(double) * 3 * n_, hipMemcpyDeviceToHost, stream_));
-    EPH_HIP(hipStreamSynchronize(stream_));
-    return xch_ ? xch_->poll_error() : EPH_OK;
+    return n_ == 0 ? (int)EPH_OK : read_back(is_multistep_ ? Aslot(cur_) : ASR_.p, acc, nullptr, nullptr);
 }
 
 // seam 1: SecondOrderODE::eval for NewtonianGravity, host buffers in and out.

@@ -39,6 +39,18 @@ double accumulate(double start, double delta, uint64_t times) {
 inline double dir_offset(int d, double to, double duration) { return d > 0 ? to + duration : to - duration; }
 inline double dir_distance(int d, double from, double to) { return d > 0 ? to - from : from - to; }
 constexpr uint64_t kSampleBudget = 4u << 20;   // samples in the device logs (96 MB)
+// rows q, q + 1, ... of a fit's output (24 coefficients and ncoef each; body-major, nwin[b] windows of body b) as Polynomials, each
+// handed to push(spline of its body, polynomial) in the order the windows were fitted
+template <typename Push>
+void push_rows(Solution &so, const std::vector<uint32_t> &nwin, const double *co, const int32_t *nc, size_t &q, Push &&push) {
+    for (size_t b = 0; b < nwin.size(); ++b)
+        for (uint32_t w = 0; w < nwin[b]; ++w, ++q) {
+            Polynomial poly;
+            poly.ncoef = nc[q];
+            std::copy(co + q * kDiv * 3, co + (q + 1) * kDiv * 3, &poly.c[0][0]);
+            push(so.splines[b], poly);
+        }
+}
 }  // namespace
 
 Solution NBodyPropagator::new_solution() const {   // Solout::new_solution  nbody.rs:454-469
@@ -121,19 +133,19 @@ int NBodyPropagator::clone(std::unique_ptr<NBodyPropagator> *out) {
     p->log_off_ = log_off_;
     p->log_cap_ = log_cap_;
     const size_t n = interp_.size();
-    if ((st = p->log_.alloc(log_.count)) || (st = p->d_period_.alloc(n)) || (st = p->d_phase_.alloc(n)) ||
+    hipStream_t s = integ_->stream();
+    if ((st = copy_buf(log_, p->log_, s)) || (st = copy_buf(d_period_, p->d_period_, s)) || (st = p->d_phase_.alloc(n)) ||
         (st = p->d_offset_.alloc(n)))
         return st;
-    EPH_HIP(hipMemcpy(p->log_.p, log_.p, sizeof(double) * log_.count, hipMemcpyDeviceToDevice));
-    EPH_HIP(hipMemcpy(p->d_period_.p, d_period_.p, sizeof(uint32_t) * d_period_.count, hipMemcpyDeviceToDevice));
-    if (pend_count_) {                                // device-resident polynomials travel with the clone
+    if (pend_count_) {                                // device-resident polynomials travel with the clone: the windows, not the capacity
         if ((st = p->pend_co_.alloc(pend_count_ * kDiv * 3)) || (st = p->pend_nc_.alloc(pend_count_))) return st;
-        EPH_HIP(hipStreamSynchronize(integ_->stream()));
-        EPH_HIP(hipMemcpy(p->pend_co_.p, pend_co_.p, sizeof(double) * pend_count_ * kDiv * 3, hipMemcpyDeviceToDevice));
-        EPH_HIP(hipMemcpy(p->pend_nc_.p, pend_nc_.p, sizeof(int32_t) * pend_count_, hipMemcpyDeviceToDevice));
+        EPH_HIP(hipStreamSynchronize(s));
+        EPH_HIP(hipMemcpyAsync(p->pend_co_.p, pend_co_.p, sizeof(double) * pend_count_ * kDiv * 3, hipMemcpyDeviceToDevice, s));
+        EPH_HIP(hipMemcpyAsync(p->pend_nc_.p, pend_nc_.p, sizeof(int32_t) * pend_count_, hipMemcpyDeviceToDevice, s));
         p->pend_count_ = p->pend_cap_ = pend_count_;
         p->pend_batches_ = pend_batches_;
     }
+    EPH_HIP(hipStreamSynchronize(s));
     *out = std::move(p);
     return EPH_OK;
 }
@@ -187,17 +199,11 @@ int NBodyPropagator::materialize() {
     EPH_HIP(hipStreamSynchronize(s));
     size_t q = 0;
     for (const std::vector<uint32_t> &nwin : pend_batches_)
-        for (size_t b = 0; b < nwin.size(); ++b) {
-            UniformSpline &traj = solution_.splines[b];
-            for (uint32_t w = 0; w < nwin[b]; ++w, ++q) {
-                Polynomial poly;
-                poly.ncoef = nc[q];
-                std::copy(co.begin() + q * kDiv * 3, co.begin() + (q + 1) * kDiv * 3, &poly.c[0][0]);
-                // push_at_bound: the start of a backward spline already moved when the window was fitted
-                if (direction_ > 0) traj.polynomials.push_back(poly); else traj.polynomials.push_front(poly);
-                traj.ghost -= 1;
-            }
-        }
+        push_rows(solution_, nwin, co.data(), nc.data(), q, [&](UniformSpline &traj, const Polynomial &poly) {
+            // push_at_bound, into the deque directly: the start of a backward spline already moved when the window was fitted
+            if (direction_ > 0) traj.polynomials.push_back(poly); else traj.polynomials.push_front(poly);
+            traj.ghost -= 1;
+        });
     pend_count_ = 0;
     pend_batches_.clear();
     return EPH_OK;
@@ -330,35 +336,32 @@ int NBodyPropagator::fit_and_push(int64_t done, hipStream_t s) {
     }
     const int64_t W = (int64_t)first.size();
     if (W == 0) return EPH_OK;
-    // Sharded system (eph_prop_shard): this rank samples and fits only the bodies it owns -- the windows of
-    // bodies [lo, hi) are the contiguous range [qlo, qhi) of the window list -- and the fitted polynomials
-    // are all-gathered (equal slices of world x wmax windows, 25 doubles each: 24 coefficients + ncoef) so
-    // that every rank holds the whole Vec<UniformSpline>. The window bookkeeping above is identical on
-    // every rank, so all ranks agree on the ranges.
-    const bool sharded = ig.sharded();
-    const int world = ig.shard_world(), rank = ig.shard_rank(), slice = ig.shard_slice();
-    std::vector<int64_t> qstart(n + 1, 0);
-    for (int b = 0; b < n; ++b) qstart[b + 1] = qstart[b] + nwin[b];
-    auto body_lo = [&](int r) { return std::min<int64_t>((int64_t)r * slice, n); };
-    const int64_t qlo = sharded ? qstart[body_lo(rank)] : 0, qhi = sharded ? qstart[body_lo(rank + 1)] : W;
-    int64_t wmax = 0;
-    for (int r = 0; r < world && sharded; ++r) wmax = std::max(wmax, qstart[body_lo(r + 1)] - qstart[body_lo(r)]);
     int st;
-    if (!sharded) {
+    // what both halves below queue on `s` (each reserves its own scratch first; it is grow-only and lives with the propagator, so a
+    // steady run allocates nothing per batch): the window list, and the carry -- the samples that open the next windows move to the
+    // front of their log regions
+    auto upload_windows = [&]() -> int {
+        EPH_HIP(hipMemcpyAsync(d_first_.p, first.data(), sizeof(uint64_t) * W, hipMemcpyHostToDevice, s));
+        EPH_HIP(hipMemcpyAsync(d_deg_.p, deg.data(), sizeof(uint8_t) * W, hipMemcpyHostToDevice, s));
+        return EPH_OK;
+    };
+    auto carry = [&]() -> int {
+        EPH_HIP(hipMemcpyAsync(d_src_.p, carry_src.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+        EPH_HIP(hipMemcpyAsync(d_cnt_.p, carry_cnt.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+        EPH_HIP(hipMemcpyAsync(d_region_.p, log_off_.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+        return launch_carry(s, n, d_region_.p, d_src_.p, d_cnt_.p, log_.p);
+    };
+    if (!ig.sharded()) {
         // Unsharded: fit straight into the device-resident pending list; only the bounds move on the host
         // (UniformSpline::push_front's `start -= interval`, one f64 subtraction per window like the reference).
         if ((st = d_first_.reserve(W)) || (st = d_deg_.reserve(W)) || (st = d_src_.reserve(n)) || (st = d_cnt_.reserve(n)) ||
             (st = d_region_.reserve(n)) || (st = reserve_pending((size_t)W, s)))
             return st;
-        EPH_HIP(hipMemcpyAsync(d_first_.p, first.data(), sizeof(uint64_t) * W, hipMemcpyHostToDevice, s));
-        EPH_HIP(hipMemcpyAsync(d_deg_.p, deg.data(), sizeof(uint8_t) * W, hipMemcpyHostToDevice, s));
+        if ((st = upload_windows())) return st;
         if ((st = launch_lsq_fit(s, W, d_first_.p, d_deg_.p, direction_ < 0, log_.p, pend_co_.p + pend_count_ * kDiv * 3,
                                  pend_nc_.p + pend_count_)))
             return st;
-        EPH_HIP(hipMemcpyAsync(d_src_.p, carry_src.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-        EPH_HIP(hipMemcpyAsync(d_cnt_.p, carry_cnt.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-        EPH_HIP(hipMemcpyAsync(d_region_.p, log_off_.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
-        if ((st = launch_carry(s, n, d_region_.p, d_src_.p, d_cnt_.p, log_.p))) return st;
+        if ((st = carry())) return st;
         EPH_HIP(hipStreamSynchronize(s));            // the host vectors above go out of scope
         for (int b = 0; b < n; ++b) {
             UniformSpline &traj = solution_.splines[b];
@@ -370,65 +373,58 @@ int NBodyPropagator::fit_and_push(int64_t done, hipStream_t s) {
         pend_batches_.push_back(std::move(nwin));
         return EPH_OK;
     }
-    // scratch is grow-only and lives with the propagator: a steady run allocates nothing per batch
+    // Sharded system (eph_prop_shard): this rank samples and fits only the bodies it owns -- the windows of
+    // bodies [lo, hi) are the contiguous range [qlo, qhi) of the window list -- and the fitted polynomials
+    // are all-gathered (equal slices of world x wmax windows, 25 doubles each: 24 coefficients + ncoef) so
+    // that every rank holds the whole Vec<UniformSpline>. The window bookkeeping above is identical on
+    // every rank, so all ranks agree on the ranges.
+    const int world = ig.shard_world(), rank = ig.shard_rank(), slice = ig.shard_slice();
+    std::vector<int64_t> qstart(n + 1, 0);
+    for (int b = 0; b < n; ++b) qstart[b + 1] = qstart[b] + nwin[b];
+    auto body_lo = [&](int r) { return std::min<int64_t>((int64_t)r * slice, n); };
+    const int64_t qlo = qstart[body_lo(rank)], qhi = qstart[body_lo(rank + 1)];
+    int64_t wmax = 0;
+    for (int r = 0; r < world; ++r) wmax = std::max(wmax, qstart[body_lo(r + 1)] - qstart[body_lo(r)]);
+    const size_t rec = (size_t)kDiv * 3 + 1;                      // doubles per window in the exchange buffer
+    const size_t slice_d = (size_t)std::max<int64_t>(wmax, 1) * rec;
     if ((st = d_first_.reserve(W)) || (st = d_deg_.reserve(W)) || (st = d_co_.reserve((size_t)W * kDiv * 3)) ||
         (st = d_nc_.reserve(W)) || (st = d_src_.reserve(n)) || (st = d_cnt_.reserve(n)) || (st = d_region_.reserve(n)))
         return st;
-    EPH_HIP(hipMemcpyAsync(d_first_.p, first.data(), sizeof(uint64_t) * W, hipMemcpyHostToDevice, s));
-    EPH_HIP(hipMemcpyAsync(d_deg_.p, deg.data(), sizeof(uint8_t) * W, hipMemcpyHostToDevice, s));
+    if ((st = upload_windows())) return st;
     if (qhi > qlo &&
         (st = launch_lsq_fit(s, qhi - qlo, d_first_.p + qlo, d_deg_.p + qlo, direction_ < 0, log_.p,
                              d_co_.p + qlo * kDiv * 3, d_nc_.p + qlo)))
         return st;
-    std::vector<double> co((size_t)W * kDiv * 3), all;
+    // device-side: pack this rank's windows into its slice of the exchange buffer, all-gather in place,
+    // one copy of the whole buffer to the host (which owns the Vec<UniformSpline>)
+    if ((st = d_all_.reserve(slice_d * world))) return st;
+    if ((st = launch_pack_records(s, qhi - qlo, d_co_.p + qlo * kDiv * 3, d_nc_.p + qlo,
+                                  d_all_.p + (size_t)rank * slice_d)))
+        return st;
+    if ((st = ig.gather_buffer(d_all_.p, sizeof(double) * slice_d))) return st;
+    std::vector<double> co((size_t)W * kDiv * 3), all(slice_d * world);
     std::vector<int32_t> nc(W);
-    const size_t rec = (size_t)kDiv * 3 + 1;                      // doubles per window in the exchange buffer
-    const size_t slice_d = (size_t)std::max<int64_t>(wmax, 1) * rec;
-    if (sharded) {
-        // device-side: pack this rank's windows into its slice of the exchange buffer, all-gather in place,
-        // one copy of the whole buffer to the host (which owns the Vec<UniformSpline>)
-        if ((st = d_all_.reserve(slice_d * world))) return st;
-        if ((st = launch_pack_records(s, qhi - qlo, d_co_.p + qlo * kDiv * 3, d_nc_.p + qlo,
-                                      d_all_.p + (size_t)rank * slice_d)))
-            return st;
-        if ((st = ig.gather_buffer(d_all_.p, sizeof(double) * slice_d))) return st;
-        all.resize(slice_d * world);
-        EPH_HIP(hipMemcpyAsync(all.data(), d_all_.p, sizeof(double) * all.size(), hipMemcpyDeviceToHost, s));
-    } else {
-        EPH_HIP(hipMemcpyAsync(co.data(), d_co_.p, sizeof(double) * co.size(), hipMemcpyDeviceToHost, s));
-        EPH_HIP(hipMemcpyAsync(nc.data(), d_nc_.p, sizeof(int32_t) * W, hipMemcpyDeviceToHost, s));
-    }
-    EPH_HIP(hipMemcpyAsync(d_src_.p, carry_src.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-    EPH_HIP(hipMemcpyAsync(d_cnt_.p, carry_cnt.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-    EPH_HIP(hipMemcpyAsync(d_region_.p, log_off_.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
-    if ((st = launch_carry(s, n, d_region_.p, d_src_.p, d_cnt_.p, log_.p))) return st;
+    EPH_HIP(hipMemcpyAsync(all.data(), d_all_.p, sizeof(double) * all.size(), hipMemcpyDeviceToHost, s));
+    if ((st = carry())) return st;
     EPH_HIP(hipStreamSynchronize(s));
-    if (sharded) {
-        // a peer that never delivered its records (peer.hip: bounded wait): nothing gathered may be unpacked
-        if ((st = integ_->exchange_error())) return st;
-        for (int r = 0; r < world; ++r) {
-            const int64_t a0 = qstart[body_lo(r)], a1 = qstart[body_lo(r + 1)];
-            for (int64_t q = a0; q < a1; ++q) {
-                const double *src = all.data() + (size_t)r * slice_d + (size_t)(q - a0) * rec;
-                std::copy(src, src + kDiv * 3, co.begin() + q * kDiv * 3);
-                nc[q] = (int32_t)src[kDiv * 3];
-                if (!(src[kDiv * 3] >= 0.0 && src[kDiv * 3] <= (double)kDiv)) {       // not a record a rank packed
-                    set_last_error_text("sharded propagator: a gathered polynomial record carries ncoef outside [0, 8]");
-                    return EPH_ERR_COMM;
-                }
+    // a peer that never delivered its records (peer.hip: bounded wait): nothing gathered may be unpacked
+    if ((st = integ_->exchange_error())) return st;
+    for (int r = 0; r < world; ++r) {
+        const int64_t a0 = qstart[body_lo(r)], a1 = qstart[body_lo(r + 1)];
+        for (int64_t q = a0; q < a1; ++q) {
+            const double *src = all.data() + (size_t)r * slice_d + (size_t)(q - a0) * rec;
+            std::copy(src, src + kDiv * 3, co.begin() + q * kDiv * 3);
+            nc[q] = (int32_t)src[kDiv * 3];
+            if (!(src[kDiv * 3] >= 0.0 && src[kDiv * 3] <= (double)kDiv)) {       // not a record a rank packed
+                set_last_error_text("sharded propagator: a gathered polynomial record carries ncoef outside [0, 8]");
+                return EPH_ERR_COMM;
             }
         }
     }
-    int64_t q = 0;
-    for (int b = 0; b < n; ++b) {
-        UniformSpline &traj = solution_.splines[b];
-        for (uint32_t w = 0; w < nwin[b]; ++w, ++q) {
-            Polynomial poly;
-            poly.ncoef = nc[q];
-            std::copy(co.begin() + q * kDiv * 3, co.begin() + (q + 1) * kDiv * 3, &poly.c[0][0]);
-            if (direction_ > 0) traj.push_back(poly); else traj.push_front(poly);   // push_at_bound
-        }
-    }
+    size_t q = 0;
+    push_rows(solution_, nwin, co.data(), nc.data(), q, [&](UniformSpline &traj, const Polynomial &poly) {
+        if (direction_ > 0) traj.push_back(poly); else traj.push_front(poly);   // push_at_bound: UniformSpline::push_front moves the start
+    });
     return EPH_OK;
 }
 

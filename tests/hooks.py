@@ -117,6 +117,21 @@ class Hooks:
         return list(product), list(debug)
 
 
+def failing_allocations(ea, H, call, on_failure):
+    """call() -> (status, *out, text) with the k-th allocation failing, k = 1, 2, ...: every failure is ERR_OUT_OF_MEMORY with the injected
+    text and a countdown that has disarmed itself, then on_failure(k, *out) -> (failures before the first success, that success's *out)"""
+    for k in range(1, 200):
+        assert H.fail_alloc(k) == 0
+        st, out, text = call()
+        left = H.fail_alloc(0)
+        if st == ea.OK:
+            return k - 1, out
+        assert st == ea.ERR_OUT_OF_MEMORY and "injected allocation failure" in text, (k, st, out, text)
+        assert left == 0, f"k = {k}: the countdown is still armed"
+        on_failure(k, out)
+    raise AssertionError("no success by k = 199")
+
+
 _cache = {}
 
 

@@ -25,6 +25,7 @@ import pytest
 import event_scenes as evs
 from conftest import ROOT
 from craft_cases import bits, same
+from hooks import failing_allocations
 from oracle import orc
 from test_gpu_craft_events import DRAINED, SCENES, compare_events, compare_sweep, oracle_results
 from test_gpu_live_ephemeris import DAY, _compare, _fleet, _live, _ship, pieces  # noqa: F401  (pieces: the fixture)
@@ -569,21 +570,6 @@ ALLOCATIONS = {"commit-rule": 35,      # gather (no body order set): 20 of the s
                "clone-rule": 34,       # every buffer of the source but `summary`: 33 copied, the queue fresh
                "create-rule": 23,      # 20 of the state, 3 of the deal
                "events-rule": 11}      # soi, 4 per-craft event arrays, 6 event slabs
-
-
-def failing_allocations(ea, H, call, on_failure):
-    """call() -> (status, *out, text) with the k-th allocation failing, k = 1, 2, ...: every failure is ERR_OUT_OF_MEMORY with the injected
-    text and a countdown that has disarmed itself, then on_failure(k, *out) -> (failures before the first success, that success's *out)"""
-    for k in range(1, 200):
-        assert H.fail_alloc(k) == 0
-        st, out, text = call()
-        left = H.fail_alloc(0)
-        if st == ea.OK:
-            return k - 1, out
-        assert st == ea.ERR_OUT_OF_MEMORY and "injected allocation failure" in text, (k, st, out, text)
-        assert left == 0, f"k = {k}: the countdown is still armed"
-        on_failure(k, out)
-    raise AssertionError("no success by k = 199")
 
 
 def unchanged(batches, before, what):
