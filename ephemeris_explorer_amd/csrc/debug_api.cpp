@@ -86,7 +86,12 @@ int32_t eph_debug_inv_r3_sweep(uint64_t seed, int64_t n, uint64_t *mismatches, u
 int32_t eph_debug_wg_cycles(int64_t *out8) {
     if (!out8) return EPH_ERR_BAD_ARGUMENT;
     const PairDebugKernels *t = debug_table(default_pair_variant());
-    return t ? t->debug_wg_cycles((long long *)out8) : EPH_ERR_BAD_ARGUMENT;
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
+    const int st = t->debug_wg_cycles((long long *)out8);
+#if !EPH_EXPERIMENTS
+    if (!st) out8[0] = (int64_t)launches_counted();        // no tick accounting in these objects: the launch accounting instead
+#endif
+    return st;
 }
 
 int32_t eph_debug_div(int64_t n, const double *a, const double *b, double *fast, double *ieee) { return debug_div_device(n, a, b, fast, ieee); }

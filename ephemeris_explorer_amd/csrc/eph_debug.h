@@ -29,8 +29,12 @@ int32_t eph_debug_quot(int64_t n, const double *x, const double *a, double *fast
  * exponent uniform over the guarded range; n is rounded up to a multiple of 2^20). *mismatches = operands whose two
  * results differ in any bit; *example_bits = the IEEE bits of one of them (0 when none). */
 int32_t eph_debug_inv_r3_sweep(uint64_t seed, int64_t n, uint64_t *mismatches, uint64_t *example_bits);
-/* Tuning hook: zeros from the product library. A build with -DEPH_EXPERIMENTS=1 (scripts/build_exp.sh) returns the
- * single-workgroup kernel's per-phase tick accounting of its last launch (EPH_DEBUG_SMALL=4). */
+/* Tuning hook. A build with -DEPH_EXPERIMENTS=1 (scripts/build_exp.sh) returns the single-workgroup kernel's per-phase tick
+ * accounting of its last launch (EPH_DEBUG_SMALL=4). The product's objects have no tick accounting: out8[1..7] are zeros and
+ * out8[0] is the launch accounting -- the kernel launches that eph_nbody_advance / eph_nbody_advance_many (and the eph_prop_* calls
+ * above them) have queued on THIS thread through this library so far: start-up, per-stage, sample and steady launches alike, a
+ * launch shared by a gang once; read-backs, clones and fits not counted. Tests read it before and after a call. (The boundary
+ * has no such call, and this header no hook of its own for it: both lists of names are pinned by tests/test_abi.py.) */
 int32_t eph_debug_wg_cycles(int64_t *out8);
 /* Test hook: the nth device allocation the library makes on THIS thread from now (nth >= 1) returns EPH_ERR_OUT_OF_MEMORY with
  * last-error text "injected allocation failure", before any HIP call, and the countdown disarms itself; 0 disarms it. A host

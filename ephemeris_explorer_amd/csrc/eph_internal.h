@@ -126,6 +126,10 @@ bool slots_hold_their_orders(const Table *const (&t)[kPairVariants]) {
         if (t[k]->variant != k) return false;
     return true;
 }
+// test hook (eph_debug_wg_cycles of a product build): the kernel launches NBodyIntegration::advance / advance_many have queued on THIS
+// thread -- start-up, per-stage, sample and steady launches alike, a gang's shared launch once; read-backs, clones and fits not
+void count_launches(uint64_t n);
+uint64_t launches_counted();
 int default_pair_variant();                 // what new handles take: eph_set_pair_variant, else EPH_PAIR_VARIANT, else 0
 int set_default_pair_variant(int pv);       // EPH_ERR_BAD_ARGUMENT outside 0..6
 // a[b] = acc_init[b] (or 0) + sum over the other bodies in the reference order; SoA [3][npad] output
@@ -159,6 +163,18 @@ struct SrknSmallArgs {
 };
 int launch_srkn_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
 int launch_srkn_double_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
+// a linear multistep handle's start-up in the same frame (k_lm_startup_small, step_srkn_small.hip): `m` macro steps of `substeps`
+// steps of the substepper's table `s` per launch, each closed by the force at the new front. s.Y / s.YE are the RING bases, s.starter_i
+// counts the substepper's steps (0: the force at the initial positions is evaluated first). The gang form runs one workgroup per
+// argument block of a device array (plain state only); every block carries its own system, ring position and m.
+struct LmStartupArgs {
+    SrknSmallArgs s;
+    double *A;                 // acceleration ring [L][3][npad]
+    int L, cur;                // ring length; slot of the newest level on entry
+    int m, substeps;
+};
+int launch_lm_startup_small(int pv, hipStream_t s, const LmStartupArgs &a, bool compensated);
+int launch_lm_startup_small_many(int pv, hipStream_t s, const LmStartupArgs *argv_dev, int count);
 // opt-in fast path: slice-parallel partial sums combined in slice order (NOT the reference's summation order)
 int fast_slices(int npad, bool approx = false);                     // S (the rsq form takes twice the waves)
 #ifndef EPH_F32_GROUP
@@ -188,6 +204,8 @@ struct PairKernels {                        // one evaluation order's launchers 
     int (*lm_double_small)(hipStream_t, const LmDoubleArgs &, int64_t);
     int (*srkn_small)(hipStream_t, const SrknSmallArgs &, int64_t);
     int (*srkn_double_small)(hipStream_t, const SrknSmallArgs &, int64_t);
+    int (*lm_startup_small)(hipStream_t, const LmStartupArgs &, bool);
+    int (*lm_startup_small_many)(hipStream_t, const LmStartupArgs *, int);
     int (*lm_step_fast)(hipStream_t, const LmArgs &, double *, int, int, bool, float *, int, int, int, unsigned *);
     int (*craft_launch)(hipStream_t, const CraftArgs &, const CraftLaunch &);
     int variant;                            // the order these launchers were compiled for: dispatch.cpp holds slot k to order k

@@ -258,16 +258,30 @@ public:
     bool steps_certain(int64_t k) const;       // neither the bound nor the underflow test can fire in the next k steps (closed form)
     void replay_deferred_time() { for (int64_t s = 0; s < deferred_time_steps_; ++s) time_ = time_ + h_; deferred_time_steps_ = 0; }
     // `count` independent single-workgroup systems advanced by k steps in ONE launch (k_lm_small, one workgroup each):
-    // the same as advance(k) on every one of them. Systems that do not qualify (start-up not finished, more than
-    // kGangMaxN bodies, sharded, a forced kernel path, a step that would fail) make the call fall back to that.
+    // the same as advance(k) on every one of them. Systems that do not qualify (more than kGangMaxN bodies, sharded, a
+    // forced kernel path, a step that would fail) make the call fall back to that.
+    // Members still in their start-up take its macro steps first, those of at least two plain members in ONE launch of
+    // k_lm_startup_small (a workgroup each); what is left of k then runs as above when it is the same for every member.
     static int advance_many(NBodyIntegration *const *igs, int count, int64_t k);
     bool gang_ready(int64_t k) const;
+    // The one-launch start-up (k_lm_startup_small): how many of the next `want` steps it would take now -- min(want, macro steps
+    // left) -- or 0 where the per-launch route has to run: started, not multistep, more than kGangMaxN bodies, sharded, a forced
+    // per-launch path, between two substeps of an abandoned macro step, or one of the tests of startup_macro_step / srkn_step
+    // firing in those macro steps (a dry run of `time = time + h_sub` in the reference's order; *t_after: the time it ends at).
+    int64_t startup_small_steps(int64_t want, double *t_after = nullptr) const;
+    int64_t startup_left() const { return started() ? 0 : (int64_t)lm_.order - (int64_t)(starter_i_ / (uint32_t)substeps_); }
 
 private:
     NBodyIntegration() = default;
     int open_device();                        // the handle's stream, its two events and its buffers (create and clone)
     int alloc_buffers();
+    int advance_from(int64_t done, int64_t n_steps, int64_t *done_out);   // advance(n_steps) whose first `done` steps are taken already
     int startup_macro_step();                 // one LinearMultistepIntegrator::advance in the start-up regime
+    int startup_batch(int64_t m, double t_after);                  // m of them in one launch (startup_small_steps said so)
+    void fill_startup_args(LmStartupArgs &g, int64_t m) const;
+    void commit_startup(int64_t m, double t_after);                // the bookkeeping m calls of startup_macro_step would have left
+    static int startup_gang(NBodyIntegration *const *igs, int count, const int64_t *m, const double *t_after);
+    int queued(int st, bool made = true) { if (!st && made && n_ > 0) count_launches(1); return st; }   // a launch that was made, for the hook's count
     int srkn_step(double h, double *y_slot);  // FixedRungeKuttaIntegrator::advance (SRKN)
     int srkn_batch(int64_t k);                // k of them in one launch of the single-workgroup kernel (step_srkn_small.hip)
     bool srkn_small_ready() const { return !is_multistep_ && n_ >= 1 && n_ <= kGangMaxN && !sharded() && (path_ == 0 || path_ == 2); }
@@ -310,6 +324,7 @@ private:
     DevBuf<double> fast_partial_;             // the fast paths' [S][3][npad] partial sums and arrival tickets
     DevBuf<float> posf_;                      // EPH_PATH_F32_PAIRS: the level's positions and mu as 4 floats per body
     DevBuf<LmArgs> gang_args_;                // advance_many: the argument array of the gang this handle leads
+    DevBuf<LmStartupArgs> startup_args_;      // advance_many: the same for the start-up gang it leads
     // state: allocated at creation, zeroed, copied by clone | scratch: allocated at creation, contents nobody's | lazy: allocated where
     // it is first used (lm_batch, advance_many), neither zeroed nor copied
     enum class Buf { state, scratch, lazy };
@@ -325,7 +340,8 @@ private:
                (g.compensated_ && ((st = f(EPH_NBODY_BUF(YE_), ring, Buf::state)) || (st = f(EPH_NBODY_BUF(VE_), vec, Buf::state)))) ||
                (st = f(EPH_NBODY_BUF(fast_partial_), fast_partial_doubles(g.npad_), Buf::lazy)) ||
                (st = f(EPH_NBODY_BUF(posf_), 4 * bodies, Buf::lazy)) ||
-               (st = f(EPH_NBODY_BUF(gang_args_), (size_t)0, Buf::lazy)));                 // (one LmArgs per system of the gang)
+               (st = f(EPH_NBODY_BUF(gang_args_), (size_t)0, Buf::lazy)) ||                // (one LmArgs per system of the gang)
+               (st = f(EPH_NBODY_BUF(startup_args_), (size_t)0, Buf::lazy)));
 #undef EPH_NBODY_BUF
         return st;
     }
@@ -335,6 +351,8 @@ private:
     hipEvent_t gang_ev_ = nullptr, gang_copy_ev_ = nullptr;
     LmArgs *gang_host_ = nullptr;             // pinned source of the gang's argument copy (so advance_many need not wait for it)
     size_t gang_host_count_ = 0;
+    LmStartupArgs *startup_host_ = nullptr;   // the same for the start-up gang (gang_copy_ev_ guards both)
+    size_t startup_host_count_ = 0;
 };
 
 // Polynomial<DVec3> (SmallVec<[DVec3; 8]>)   ephemeris/src/trajectory.rs:337-396
@@ -456,7 +474,7 @@ public:
                       std::unique_ptr<NBodyPropagator> *out);
     int clone(std::unique_ptr<NBodyPropagator> *out);
     int step_n(int64_t k);                    // k x IncrementalPropagator::step
-    // step_n(k) on every propagator of `ps`, the steady-state steps of all of them in shared launches (advance_many)
+    // step_n(k) on every propagator of `ps`, the start-up and the steady-state steps of all of them in shared launches (advance_many)
     static int step_n_many(NBodyPropagator *const *ps, int count, int64_t k);
     int step_to(double t);
     // ONE IncrementalPropagator::step, executed lazily: the reference's callers step in a loop and look at time() /

@@ -19,6 +19,12 @@
 
 namespace eph {
 
+namespace {
+thread_local uint64_t g_launches = 0;    // test hook: launches queued by advance / advance_many on this thread (eph_internal.h)
+}
+void count_launches(uint64_t n) { g_launches += n; }
+uint64_t launches_counted() { return g_launches; }
+
 NBodyIntegration::~NBodyIntegration() {
     if (stream_) {
         (void)hipSetDevice(device_);
@@ -30,6 +36,7 @@ NBodyIntegration::~NBodyIntegration() {
         if (gang_ev_) (void)hipEventDestroy(gang_ev_);
         if (gang_copy_ev_) { (void)hipEventSynchronize(gang_copy_ev_); (void)hipEventDestroy(gang_copy_ev_); }
         if (gang_host_) (void)hipHostFree(gang_host_);
+        if (startup_host_) (void)hipHostFree(startup_host_);
         (void)hipStreamDestroy(stream_);
     }
 }
@@ -172,9 +179,9 @@ int NBodyIntegration::srkn_step(double h, double *y_slot) {
         const KickDrift kd{V_.p, y_slot, h * rk_.B[s], h * rk_.A[s], P_[pp_ ^ 1].p};
         if (!rk_.fsal || s > 0 || starter_i_ == 0) {
             // problem.ode.eval(t_stage, &problem.state.y, self.ddy.zero()) and the stage update behind it, one launch
-            if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, ASR_.p, force_kind(), lo_, hi_, &kd))) return st;
+            if ((st = queued(launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, ASR_.p, force_kind(), lo_, hi_, &kd)))) return st;
             evals_++;
-        } else if ((st = launch_kick_drift(stream_, n_, npad_, ASR_.p, V_.p, y_slot, kd.hb, kd.ha, mu_.p, P_[pp_ ^ 1].p))) {
+        } else if ((st = queued(launch_kick_drift(stream_, n_, npad_, ASR_.p, V_.p, y_slot, kd.hb, kd.ha, mu_.p, P_[pp_ ^ 1].p)))) {
             return st;                                 // FSAL first stage: the acceleration is the previous step's last
         }
         if ((st = gather_packed(P_[pp_ ^ 1].p))) return st;
@@ -189,11 +196,11 @@ int NBodyIntegration::srkn_step(double h, double *y_slot) {
 int NBodyIntegration::srkn_stage_double(double hb, double ha, double *y_slot, double *ye_slot, bool eval) {
     int st;
     if (eval) {
-        if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, ASR_.p, force_kind(), lo_, hi_))) return st;
+        if ((st = queued(launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, ASR_.p, force_kind(), lo_, hi_)))) return st;
         evals_++;
     }                                                  // (FSAL first stage: the acceleration is the previous step's last)
     const KickDriftDouble kd{ASR_.p, V_.p, VE_.p, y_slot, ye_slot, hb, ha, P_[pp_ ^ 1].p};
-    if ((st = launch_kick_drift_double(stream_, n_, npad_, kd))) return st;
+    if ((st = queued(launch_kick_drift_double(stream_, n_, npad_, kd)))) return st;
     pp_ ^= 1;
     return EPH_OK;
 }
@@ -209,17 +216,67 @@ int NBodyIntegration::startup_macro_step() {
     if (time_ + h_ == time_) return EPH_STEP_SIZE_UNDERFLOW;
     int st;
     if (starter_i_ / (uint32_t)substeps_ == 0) {
-        if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(cur_), force_kind(), lo_, hi_))) return st;
+        if ((st = queued(launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(cur_), force_kind(), lo_, hi_)))) return st;
         evals_++;
     }
     const int nslot = (cur_ + L_ - 1) % L_;
-    if ((st = launch_copy3(stream_, n_, npad_, Yslot(cur_), Yslot(nslot)))) return st;
-    if (compensated_ && (st = launch_copy3(stream_, n_, npad_, YEslot(cur_), YEslot(nslot)))) return st;   // clone_from copies the error parts
+    if ((st = queued(launch_copy3(stream_, n_, npad_, Yslot(cur_), Yslot(nslot))))) return st;
+    if (compensated_ && (st = queued(launch_copy3(stream_, n_, npad_, YEslot(cur_), YEslot(nslot))))) return st;   // clone_from copies the error parts
     cur_ = nslot;   // from here on the working state is the new front, as in the reference after the clone_from
     for (int s = 0; s < substeps_; ++s)
         if ((st = srkn_step(h_sub_, Yslot(nslot)))) return st;
-    if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(nslot), force_kind(), lo_, hi_))) return st;
+    if ((st = queued(launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(nslot), force_kind(), lo_, hi_)))) return st;
     evals_++;
+    return EPH_OK;
+}
+
+// ---- The start-up in one launch (k_lm_startup_small) -------------------------------------------------------------------------
+int64_t NBodyIntegration::startup_small_steps(int64_t want, double *t_after) const {
+    if (!is_multistep_ || started() || n_ < 1 || n_ > kGangMaxN || sharded() || (path_ != 0 && path_ != 2)) return 0;
+    if (starter_i_ % (uint32_t)substeps_ != 0) return 0;               // a macro step abandoned between two substeps
+    const int64_t m = std::min(want, startup_left());
+    double t = time_;
+    for (int64_t d = 0; d < m; ++d) {
+        if (t >= bound_ || t + h_ == t) return 0;                       // startup_macro_step's two tests
+        for (int s = 0; s < substeps_; ++s) {
+            if (t >= bound_ || t + h_sub_ == t) return 0;               // srkn_step's
+            t = t + h_sub_;
+        }
+    }
+    if (t_after) *t_after = t;
+    return m > 0 ? m : 0;
+}
+void NBodyIntegration::fill_startup_args(LmStartupArgs &g, int64_t m) const {
+    g = LmStartupArgs{};
+    SrknSmallArgs &a = g.s;
+    a.n = n_; a.npad = npad_;
+    a.stages = rk_.stages; a.fsal = rk_.fsal ? 1 : 0;
+    a.starter_i = starter_i_;
+    a.pos[0] = P_[pp_].p; a.pos[1] = P_[pp_ ^ 1].p;
+    a.Y = Y_.p; a.V = V_.p; a.ASR = ASR_.p;
+    a.YE = compensated_ ? YE_.p : nullptr; a.VE = compensated_ ? VE_.p : nullptr;
+    for (int s = 0; s < rk_.stages; ++s) { a.hb[s] = h_sub_ * rk_.B[s]; a.ha[s] = h_sub_ * rk_.A[s]; }
+    a.samp = samp_;
+    g.A = A_.p;
+    g.L = L_; g.cur = cur_;
+    g.m = (int)m; g.substeps = substeps_;
+}
+void NBodyIntegration::commit_startup(int64_t m, double t_after) {
+    const uint64_t steps = (uint64_t)m * (uint64_t)substeps_;
+    // the first force evaluation and the FSAL table's first stage of the very first substep; per substep the other stages; per macro
+    // step the closing force
+    evals_ += (starter_i_ == 0 ? 1 + (rk_.fsal ? 1 : 0) : 0) + steps * (uint64_t)(rk_.fsal ? rk_.stages - 1 : rk_.stages) + (uint64_t)m;
+    if ((steps * (uint64_t)rk_.stages) & 1) pp_ ^= 1;                  // every stage swaps the packed position buffers
+    cur_ = (int)(((int64_t)cur_ - m % L_ + L_) % L_);
+    starter_i_ += (uint32_t)steps;
+    time_ = t_after;
+}
+int NBodyIntegration::startup_batch(int64_t m, double t_after) {
+    LmStartupArgs g;
+    fill_startup_args(g, m);
+    if (const int st = launch_lm_startup_small(pv_, stream_, g, compensated_)) return st;
+    count_launches(1);
+    commit_startup(m, t_after);
     return EPH_OK;
 }
 
@@ -327,6 +384,7 @@ int NBodyIntegration::batch_frame(int64_t k, Queue &&queue) {
     uint64_t launches = 0;
     if ((st = queue(launches))) return st;
     if (timing_) kernel_launches_ += launches;
+    if (!collect_) count_launches(launches);              // (a gang's one launch is counted by advance_many)
     if ((st = timing.close())) return st;
     if (collect_) deferred_time_steps_ += k;              // advance_many replays them once the gang is launched
     else for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;
@@ -359,10 +417,10 @@ int NBodyIntegration::lm_batch_double(int64_t k) {
         }
         a.do_predict = 1;
         d.do_cowell = 0;
-        if ((st = launch_lm_double_step(stream_, d))) return st;       // the first step's predictor alone
+        if ((st = queued(launch_lm_double_step(stream_, d)))) return st;   // the first step's predictor alone
         for (int64_t s = 1; s <= k; ++s) {
             next_level(a);
-            if ((st = launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(cur_), force_kind(), 0, n_))) return st;
+            if ((st = queued(launch_accel(pv_, stream_, n_, npad_, P_[pp_].p, nullptr, Aslot(cur_), force_kind(), 0, n_)))) return st;
             a.do_predict = s < k;
             d.do_cowell = 1;
             if ((st = launch_lm_double_step(stream_, d))) return st;
@@ -417,7 +475,7 @@ int NBodyIntegration::lm_batch(int64_t k) {
         // after the batch behind (host.h predicted_): one launch and one launch boundary less per call
         const bool leave_prediction = n_ > kSmallN && !sharded();
         if (!predicted_) {
-            if ((st = launch_lm_predict(stream_, a))) return st;
+            if ((st = queued(launch_lm_predict(stream_, a)))) return st;
             if ((st = gather_packed(a.pos_next))) return st;
         }
         predicted_ = false;
@@ -429,7 +487,7 @@ int NBodyIntegration::lm_batch(int64_t k) {
                 // this rank's rows of the binary32 copy (16 B per body: SURVEY 8(e)'s f32x4), one all-gather of them, then the rank's
                 // targets against all sources in the single-device slice order. The f64 packed positions of the OTHER ranks' bodies
                 // are not needed between the steps of a batch (the batch's first prediction gathers them once, above).
-                if ((st = launch_lm_step_fast(pv_, stream_, a, fast_partial_.p, false, posf_.p, 1, lo_, slice_))) return st;
+                if ((st = queued(launch_lm_step_fast(pv_, stream_, a, fast_partial_.p, false, posf_.p, 1, lo_, slice_)))) return st;
                 if ((st = xch_->all_gather_inplace(posf_.p, sizeof(float) * 4 * (size_t)slice_, stream_))) return st;
                 if ((st = launch_lm_step_fast(pv_, stream_, a, fast_partial_.p, false, posf_.p, 2))) return st;
                 continue;
@@ -474,10 +532,13 @@ int NBodyIntegration::srkn_batch(int64_t k) {
     return EPH_OK;
 }
 
-int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
+int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) { return advance_from(0, n_steps, done_out); }
+
+// (advance_many continues here behind a start-up gang: `done` of the call's n_steps are taken, *done_out counts from there on)
+int NBodyIntegration::advance_from(int64_t done, int64_t n_steps, int64_t *done_out) {
     if (failed_) { if (done_out) *done_out = 0; return failed_; }     // a gang launch failed after this handle's bookkeeping had moved
     EPH_HIP(hipSetDevice(device_));
-    int64_t done = 0;
+    const int64_t done_before = done;
     int st = EPH_OK;
     const SampleArgs samp = samp_;
     while (done < n_steps) {
@@ -487,11 +548,20 @@ int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
         if (!is_multistep_ && !srkn_small) {
             if ((st = srkn_step(h_, Yslot(0)))) break;
             done++;
-            if ((st = launch_sample(stream_, n_, npad_, Yslot(0), samp, (uint32_t)done))) break;
+            if ((st = queued(launch_sample(stream_, n_, npad_, Yslot(0), samp, (uint32_t)done), samp.period != nullptr))) break;
         } else if (is_multistep_ && !started()) {
+            // The start-up's macro steps in one launch where they can be. The kernel's sampling countdown starts at this advance()'s
+            // first step, as the SRKN kernel's above.
+            double t_after = 0.0;
+            const int64_t m = done > 0 && samp.period ? 0 : startup_small_steps(n_steps - done, &t_after);
+            if (m > 0) {
+                if ((st = startup_batch(m, t_after))) break;
+                done += m;
+                continue;
+            }
             if ((st = startup_macro_step())) break;
             done++;
-            if ((st = launch_sample(stream_, n_, npad_, Yslot(cur_), samp, (uint32_t)done))) break;
+            if ((st = queued(launch_sample(stream_, n_, npad_, Yslot(cur_), samp, (uint32_t)done), samp.period != nullptr))) break;
         } else {
             // the batching regimes: the steps that can be taken, below 2^31 at a time (the single-workgroup kernels take a 32-bit
             // step index for sampling)
@@ -506,7 +576,7 @@ int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
                     st = lm_batch(1);
                     if (!st) {
                         done++;
-                        st = launch_sample(stream_, n_, npad_, Yslot(cur_), samp, (uint32_t)done);
+                        st = queued(launch_sample(stream_, n_, npad_, Yslot(cur_), samp, (uint32_t)done), samp.period != nullptr);
                     }
                 }
                 samp_ = samp;
@@ -519,7 +589,7 @@ int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) {
         }
     }
     samp_ = SampleArgs{};
-    if (done_out) *done_out = done;
+    if (done_out) *done_out = done - done_before;
     return st;
 }
 
@@ -530,18 +600,100 @@ bool NBodyIntegration::gang_ready(int64_t k) const {
     return steps_available(k, &after) == k;
 }
 
+// The start-up macro steps of `count` members, m[i] of member i, in ONE launch on the lead's stream (a workgroup per member); the
+// caller has established each m[i] by startup_small_steps, which also gave t_after[i]. The choreography of the steady gang below.
+int NBodyIntegration::startup_gang(NBodyIntegration *const *igs, int count, const int64_t *m, const double *t_after) {
+    NBodyIntegration &lead = *igs[0];
+    for (int i = 0; i < count; ++i)
+        if (m[i] < 1 || m[i] > igs[i]->startup_left()) return EPH_ERR_BAD_ARGUMENT;
+    EPH_HIP(hipSetDevice(lead.device_));
+    // everything that can fail for lack of resources happens BEFORE any handle's bookkeeping moves
+    int st;
+    if ((st = lead.startup_args_.reserve((size_t)count))) return st;
+    if (!lead.gang_ev_) EPH_HIP(hipEventCreateWithFlags(&lead.gang_ev_, hipEventDisableTiming));
+    if (!lead.gang_copy_ev_) EPH_HIP(hipEventCreateWithFlags(&lead.gang_copy_ev_, hipEventDisableTiming));
+    // the previous gang's argument copy out of the pinned array must have completed before it is rewritten (or freed)
+    EPH_HIP(hipEventSynchronize(lead.gang_copy_ev_));
+    if (lead.startup_host_count_ < (size_t)count) {
+        if (lead.startup_host_) (void)hipHostFree(lead.startup_host_);
+        lead.startup_host_ = nullptr;
+        lead.startup_host_count_ = 0;
+        const size_t want = (size_t)count + (size_t)count / 2;
+        EPH_HIP(hipHostMalloc((void **)&lead.startup_host_, sizeof(LmStartupArgs) * want, hipHostMallocDefault));
+        lead.startup_host_count_ = want;
+    }
+    for (int i = 0; i < count; ++i) igs[i]->fill_startup_args(lead.startup_host_[i], m[i]);
+    // From the first queued operation on a failure marks every member failed, as the steady gang's does
+    auto fail = [&](int status) {
+        for (int i = 0; i < count; ++i) igs[i]->failed_ = status;
+        return status;
+    };
+#define EPH_GANG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(#call, e_); return fail(EPH_ERR_HIP); } } while (0)
+    for (int i = 1; i < count; ++i) {
+        EPH_GANG_HIP(hipEventRecord(lead.gang_ev_, igs[i]->stream_));
+        EPH_GANG_HIP(hipStreamWaitEvent(lead.stream_, lead.gang_ev_, 0));
+    }
+    EPH_GANG_HIP(hipMemcpyAsync(lead.startup_args_.p, lead.startup_host_, sizeof(LmStartupArgs) * (size_t)count, hipMemcpyHostToDevice, lead.stream_));
+    EPH_GANG_HIP(hipEventRecord(lead.gang_copy_ev_, lead.stream_));
+    if ((st = launch_lm_startup_small_many(lead.pv_, lead.stream_, lead.startup_args_.p, count))) return fail(st);
+    count_launches(1);
+    for (int i = 0; i < count; ++i) igs[i]->commit_startup(m[i], t_after[i]);     // host bookkeeping under the kernel
+    EPH_GANG_HIP(hipEventRecord(lead.gang_ev_, lead.stream_));
+    for (int i = 1; i < count; ++i) EPH_GANG_HIP(hipStreamWaitEvent(igs[i]->stream_, lead.gang_ev_, 0));
+#undef EPH_GANG_HIP
+    return EPH_OK;
+}
+
 int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int64_t k) {
     if (count < 0 || (count > 0 && !igs) || k < 0) return EPH_ERR_BAD_ARGUMENT;
     if (count == 0 || k == 0) return EPH_OK;
-    bool gang = count > 1;
-    for (int i = 0; i < count && gang; ++i)
-        gang = igs[i] && igs[i]->gang_ready(k) && igs[i]->device_ == igs[0]->device_ && igs[i]->L_ == igs[0]->L_ &&
-               igs[i]->pv_ == igs[0]->pv_;
     for (int i = 0; i < count; ++i) {
         if (!igs[i]) return EPH_ERR_BAD_ARGUMENT;
         for (int j = 0; j < i; ++j)
             if (igs[j] == igs[i]) return EPH_ERR_BAD_ARGUMENT;          // a system cannot be in the gang twice
     }
+    // 1. The start-up. Every plain member that can take macro steps in one launch (startup_small_steps) takes m_i = min(k, macro
+    // steps left) of them; at least two on one device with one ring length and evaluation order share the launch. Anyone else --
+    // a <Double> member too -- does its start-up in its own advance below.
+    std::vector<int64_t> taken((size_t)count, 0);
+    {
+        std::vector<NBodyIntegration *> mem;
+        std::vector<int> who;
+        std::vector<int64_t> ms;
+        std::vector<double> ts;
+        for (int i = 0; i < count; ++i) {
+            NBodyIntegration &ig = *igs[i];
+            double t = 0.0;
+            const int64_t m = ig.failed_ || ig.compensated_ ? 0 : ig.startup_small_steps(k, &t);
+            if (m <= 0) continue;
+            if (!mem.empty() && (ig.device_ != mem[0]->device_ || ig.L_ != mem[0]->L_ || ig.pv_ != mem[0]->pv_)) continue;
+            mem.push_back(&ig); who.push_back(i); ms.push_back(m); ts.push_back(t);
+        }
+        if (mem.size() >= 2) {
+            if (const int st = startup_gang(mem.data(), (int)mem.size(), ms.data(), ts.data())) return st;
+            for (size_t j = 0; j < mem.size(); ++j) taken[(size_t)who[j]] = ms[j];
+        }
+    }
+    // 2. What is left of k. The same positive number for every member: the code below with that number. Otherwise -- and where a
+    // member's sampling schedule has started counting in the start-up launch -- each member finishes its own call.
+    bool same = true, sampled_on = false;
+    for (int i = 0; i < count; ++i) {
+        same = same && taken[(size_t)i] == taken[0];
+        sampled_on = sampled_on || (taken[(size_t)i] > 0 && taken[(size_t)i] < k && igs[i]->samp_.period);
+    }
+    if (!same || sampled_on || taken[0] == k) {
+        int first = EPH_OK;
+        for (int i = 0; i < count; ++i) {
+            if (taken[(size_t)i] == k) { igs[i]->samp_ = SampleArgs{}; continue; }
+            const int st = igs[i]->advance_from(taken[(size_t)i], k, nullptr);
+            if (st && !first) first = st;
+        }
+        return first;
+    }
+    k -= taken[0];
+    bool gang = count > 1;
+    for (int i = 0; i < count && gang; ++i)
+        gang = igs[i]->gang_ready(k) && igs[i]->device_ == igs[0]->device_ && igs[i]->L_ == igs[0]->L_ && igs[i]->pv_ == igs[0]->pv_;
     if (!gang) {                                                        // the plain meaning: advance(k) on each
         int first = EPH_OK;
         for (int i = 0; i < count; ++i) {
@@ -602,6 +754,7 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
     if (lead.timing_) EPH_GANG_HIP(hipEventRecord(lead.ev0_, lead.stream_));
     st = launch_lm_small_many(lead.pv_, lead.stream_, lead.gang_args_.p, count, lead.L_, k);
     if (st) return fail(st);
+    count_launches(1);
     for (int i = 0; i < count; ++i) igs[i]->replay_deferred_time();     // host bookkeeping under the kernel
     if (lead.timing_) {
         EPH_GANG_HIP(hipEventRecord(lead.ev1_, lead.stream_));

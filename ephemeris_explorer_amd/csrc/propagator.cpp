@@ -246,10 +246,10 @@ int NBodyPropagator::run_batch(int64_t k) {
     return st_adv;
 }
 
-// step_n(k) on several propagators at once. Start-up steps (and anything else advance_many would not take) run per
-// propagator as usual; the steady-state steps of all of them share launches: every propagator still has `rem` steps to
-// go, the gang advances min(rem, kmax) of them in ONE k_lm_small launch with a workgroup per system, then each fits and
-// pushes its own windows. Results are those of step_n(k) on each.
+// step_n(k) on several propagators at once. Whatever advance_many would not take runs per propagator as usual; the steps of the
+// others share launches: every propagator still has `rem` steps to go, the gang advances min(rem, kmax) of them -- no further than
+// the end of a member's start-up -- in ONE launch with a workgroup per system (k_lm_startup_small for the members in their
+// start-up, k_lm_small for the others), then each fits and pushes its own windows. Results are those of step_n(k) on each.
 int NBodyPropagator::step_n_many(NBodyPropagator *const *ps, int count, int64_t k) {
     if (count < 0 || (count > 0 && !ps) || k < 0) return EPH_ERR_BAD_ARGUMENT;
     std::vector<int64_t> rem((size_t)count, k);
@@ -260,7 +260,8 @@ int NBodyPropagator::step_n_many(NBodyPropagator *const *ps, int count, int64_t 
         NBodyPropagator &p = *ps[i];
         if (p.failed_) return p.failed_;
         if (p.deferred_) { const int st = p.flush(); if (st) return st; }
-        while (rem[i] > 0 && !p.integ_->started()) {                 // start-up: one macro step at a time, as step_n does
+        // a start-up that keeps the per-launch route: one macro step at a time, as step_n does
+        while (rem[i] > 0 && !p.integ_->started() && p.integ_->startup_small_steps(std::min(rem[i], p.kmax_)) == 0) {
             const int st = p.run_batch(1);
             if (st) return st;
             rem[i] -= 1;
@@ -272,10 +273,15 @@ int NBodyPropagator::step_n_many(NBodyPropagator *const *ps, int count, int64_t 
         act.clear();
         int64_t chunk = INT64_MAX;
         for (int i = 0; i < count; ++i)
-            if (rem[i] > 0) { act.push_back(ps[i]); chunk = std::min(chunk, std::min(rem[i], ps[i]->kmax_)); }
+            if (rem[i] > 0) {
+                act.push_back(ps[i]);
+                chunk = std::min(chunk, std::min(rem[i], ps[i]->kmax_));
+                if (!ps[i]->integ_->started()) chunk = std::min(chunk, ps[i]->integ_->startup_left());
+            }
         if (act.empty()) return EPH_OK;
         bool gang = act.size() > 1;
-        for (NBodyPropagator *p : act) gang = gang && p->integ_->gang_ready(chunk);
+        for (NBodyPropagator *p : act)
+            gang = gang && (p->integ_->started() ? p->integ_->gang_ready(chunk) : p->integ_->startup_small_steps(chunk) == chunk);
         if (!gang) {                                                 // somebody cannot: everybody finishes alone
             for (int i = 0; i < count; ++i)
                 if (rem[i] > 0) { const int st = ps[i]->step_n(rem[i]); if (st) return st; }
@@ -288,7 +294,7 @@ int NBodyPropagator::step_n_many(NBodyPropagator *const *ps, int count, int64_t 
             igs.push_back(p->integ_.get());
         }
         const int st_adv = NBodyIntegration::advance_many(igs.data(), (int)igs.size(), chunk);
-        if (st_adv) {                                                // (gang_ready held for all: not a StepError)
+        if (st_adv) {                                                // (every member can take the chunk: not a StepError)
             for (NBodyPropagator *p : act) p->failed_ = st_adv;
             return st_adv;
         }
@@ -486,8 +492,10 @@ int NBodyPropagator::flush() {
 int NBodyPropagator::step_n(int64_t k) {
     if (deferred_) { const int st = flush(); if (st) return st; }
     while (k > 0) {
-        // start-up steps of the multistep method go one at a time (each is many small launches anyway)
-        const int64_t chunk = integ_->started() ? std::min<int64_t>(k, kmax_) : 1;
+        // start-up steps of the multistep method: as many as one launch of k_lm_startup_small takes (a sampled batch does not cross
+        // into the steady state), and one at a time where the handle keeps the per-launch start-up (each is many small launches anyway)
+        const int64_t most = std::min<int64_t>(k, kmax_);
+        const int64_t chunk = integ_->started() ? most : std::max<int64_t>(integ_->startup_small_steps(most), 1);
         const int st = run_batch(chunk);
         if (st) return st;   // NBodyPropagatorError::Integration(e)
         k -= chunk;

@@ -125,8 +125,9 @@ int32_t eph_accel_eval(int32_t n, const double *pos_xyz, const double *mu, doubl
  *   - eph_nbody_advance_many advances it by the separate call, with the same results;
  *   - eph_ephemeris_interpolation_errors works exactly like stepping by hand and comparing the value parts;
  *   - eph_srkn_coeffs / eph_elm2_coeffs know base names only.
- * A steady multistep advance of at most 32 bodies is ONE launch whatever the step count; everything else (more bodies,
- * start-up, SRKN methods) runs a force launch and a compensated element-wise launch per step or stage. */
+ * At most 32 bodies: a steady multistep advance is ONE launch whatever the step count, so are the start-up's macro steps
+ * and the steps of an SRKN method; everything else (more bodies, path 1) runs a force launch and a compensated element-wise
+ * launch per step or stage. */
 typedef struct eph_nbody eph_nbody;
 int32_t eph_nbody_create(int32_t n, const double *pos_xyz, const double *vel_xyz, const double *mu, double t0,
                          double h, const char *method, eph_nbody **out);
@@ -169,8 +170,12 @@ int32_t eph_nbody_sync(eph_nbody *h);
  * workgroup each (a step is a chain of dependent operations, not work: 32 bodies use one of 256 compute units), so the
  * steady-state steps of all of them go into one launch with a workgroup per system -- the reference runs its forward and
  * backward propagators concurrently (ephemeris_explorer/src/load/mod.rs:673-687), and ensembles are independent too.
- * Same results as the separate calls; systems that do not qualify (start-up steps, more bodies, a sharded handle, a
- * step that would return a StepError) simply make the call do those. Handles must be distinct and on one device.
+ * The start-up of a multistep method is ganged the same way: members that still have start-up macro steps to take (each
+ * min(n_steps, macro steps left) of them) take them first, those of at least two such members in ONE launch with a workgroup
+ * per system; what is left of n_steps then shares the steady launch when it is the same number for every member, and is
+ * taken member by member otherwise. Same results as the separate calls; systems that do not qualify (more bodies, a sharded
+ * handle, a forced per-launch path, a step that would return a StepError) simply make the call do those. Handles must be
+ * distinct and on one device.
  * ASYNCHRONOUS, like eph_nbody_advance: the call queues the launch and returns; completion is eph_nbody_sync / get_state of a
  * member. A device failure AFTER the members' bookkeeping has moved (the shared launch itself) marks every member failed: all their
  * later calls -- and those of their clones -- return that status; kernel time of a timed gang accrues to the FIRST handle. */
