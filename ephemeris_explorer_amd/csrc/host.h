@@ -194,7 +194,18 @@ struct NBodyBook {
     // the last fused step of a batch left the NEXT step's predicted positions in P_[pp_ ^ 1] and in the ring slot the next step
     // takes (the oldest level's, dead by then): the next batch starts with its force evaluation instead of a predictor launch
     bool predicted_ = false;
-    int failed_ = EPH_OK;                     // sticky: a gang launch failed with this handle's bookkeeping already advanced
+    int failed_ = EPH_OK;                     // sticky: a gang launch this handle was a member of failed once something was queued
+};
+
+// The launch arguments of a gang, one T per member, on the handle that leads it: the device array the kernel reads, its pinned twin
+// that the copy is made from (so advance_many need not wait for the copy) and the twin's capacity. The twin is rewritten, grown and
+// freed only behind a wait for the owner's copy event (NBodyIntegration::gang_frame, ~NBodyIntegration).
+template <typename T>
+struct GangArgs {
+    DevBuf<T> dev;
+    T *host = nullptr;
+    size_t host_count = 0;
+    ~GangArgs() { if (host) (void)hipHostFree(host); }
 };
 
 // Integration<NBodyProblem<DVec3>, M>: problem + integrator   (integration/src/lib.rs:394-503,
@@ -256,14 +267,16 @@ public:
     // how many of the next k advance() calls would succeed before BoundReached / StepSizeUnderflow
     int64_t steps_available(int64_t k, int *status_after) const;
     bool steps_certain(int64_t k) const;       // neither the bound nor the underflow test can fire in the next k steps (closed form)
-    void replay_deferred_time() { for (int64_t s = 0; s < deferred_time_steps_; ++s) time_ = time_ + h_; deferred_time_steps_ = 0; }
     // `count` independent single-workgroup systems advanced by k steps in ONE launch (k_lm_small, one workgroup each):
     // the same as advance(k) on every one of them. Systems that do not qualify (more than kGangMaxN bodies, sharded, a
     // forced kernel path, a step that would fail) make the call fall back to that.
     // Members still in their start-up take its macro steps first, those of at least two plain members in ONE launch of
     // k_lm_startup_small (a workgroup each); what is left of k then runs as above when it is the same for every member.
+    // Either launch is one gang_frame: every member fills its block of the lead's argument array, the lead launches, every member
+    // commits its bookkeeping under the kernel (fill_startup_args / commit_startup, fill_gang_args / commit_gang). No member's
+    // advance() runs for a ganged launch.
     static int advance_many(NBodyIntegration *const *igs, int count, int64_t k);
-    bool gang_ready(int64_t k) const;
+    bool gang_ready(int64_t k) const;          // advance(k) on this handle would be ONE launch of k_lm_small that takes all k steps
     // The one-launch start-up (k_lm_startup_small): how many of the next `want` steps it would take now -- min(want, macro steps
     // left) -- or 0 where the per-launch route has to run: started, not multistep, more than kGangMaxN bodies, sharded, a forced
     // per-launch path, between two substeps of an abandoned macro step, or one of the tests of startup_macro_step / srkn_step
@@ -281,17 +294,27 @@ private:
     void fill_startup_args(LmStartupArgs &g, int64_t m) const;
     void commit_startup(int64_t m, double t_after);                // the bookkeeping m calls of startup_macro_step would have left
     static int startup_gang(NBodyIntegration *const *igs, int count, const int64_t *m, const double *t_after);
+    void fill_gang_args(LmArgs &a) const;     // the steady gang's member, for k steps that gang_ready(k) has accepted: its launch arguments,
+    void commit_gang(int64_t k);              // and the bookkeeping advance(k) would have left
+    // one launch for the members igs[0 .. count) on the stream of the lead igs[0], whose argument array `ga` is (nbody.cpp)
+    template <typename Args, typename Fill, typename Launch, typename Commit>
+    static int gang_frame(NBodyIntegration *const *igs, int count, GangArgs<Args> &ga, bool timed, Fill &&fill, Launch &&launch, Commit &&commit);
+    // what the members of one gang launch share with its lead: the device, the ring length, the evaluation order
+    bool shares_launch_with(const NBodyIntegration &lead) const { return device_ == lead.device_ && L_ == lead.L_ && pv_ == lead.pv_; }
     int queued(int st, bool made = true) { if (!st && made && n_ > 0) count_launches(1); return st; }   // a launch that was made, for the hook's count
     int srkn_step(double h, double *y_slot);  // FixedRungeKuttaIntegrator::advance (SRKN)
     int srkn_batch(int64_t k);                // k of them in one launch of the single-workgroup kernel (step_srkn_small.hip)
+    void fill_srkn_args(SrknSmallArgs &a, double h) const;         // that kernel's arguments, and the start-up kernel's share of them, for steps of h
+    uint64_t srkn_step_evals() const { return (uint64_t)(rk_.fsal ? rk_.stages - 1 : rk_.stages); }   // force evaluations per SRKN step behind the first
     bool srkn_small_ready() const { return !is_multistep_ && n_ >= 1 && n_ <= kGangMaxN && !sharded() && (path_ == 0 || path_ == 2); }
     int lm_batch(int64_t k);                  // k steady-state ELM2::advance
     int lm_batch_double(int64_t k);           // the same on a `<Double>` handle
     template <typename Queue>
-    int batch_frame(int64_t k, Queue &&queue);   // what the three batches share around their launches (nbody.cpp)
+    int batch_frame(int64_t k, Queue &&queue);   // what a handle's own three batches share around their launches (nbody.cpp); a gang's: gang_frame
     void fill_lm_args(LmArgs &a) const;       // the fields of a batch's launch arguments that both set
     void point_lm_args(LmArgs &a) const;      // the level a step starts from: ring slot and the two packed position buffers
     void next_level(LmArgs &a);               // one step on: the ring turns, the position buffers swap
+    void turn_ring(int64_t k) { cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_); }   // k steps on in one launch: the newest level's slot
     int srkn_stage_double(double hb, double ha, double *y_slot, double *ye_slot, bool eval);
     double *YEslot(int s) { return YE_.p + (size_t)s * 3 * npad_; }
     double *Yslot(int s) { return Y_.p + (size_t)s * 3 * npad_; }
@@ -323,8 +346,8 @@ private:
     DevBuf<double> Y_, A_, V_, ASR_, mu_, stage_, YE_, VE_;
     DevBuf<double> fast_partial_;             // the fast paths' [S][3][npad] partial sums and arrival tickets
     DevBuf<float> posf_;                      // EPH_PATH_F32_PAIRS: the level's positions and mu as 4 floats per body
-    DevBuf<LmArgs> gang_args_;                // advance_many: the argument array of the gang this handle leads
-    DevBuf<LmStartupArgs> startup_args_;      // advance_many: the same for the start-up gang it leads
+    GangArgs<LmArgs> gang_;                   // advance_many: the argument array of the steady gang this handle leads (its .dev is the buffer)
+    GangArgs<LmStartupArgs> startup_;         // advance_many: the same for the start-up gang it leads
     // state: allocated at creation, zeroed, copied by clone | scratch: allocated at creation, contents nobody's | lazy: allocated where
     // it is first used (lm_batch, advance_many), neither zeroed nor copied
     enum class Buf { state, scratch, lazy };
@@ -340,19 +363,15 @@ private:
                (g.compensated_ && ((st = f(EPH_NBODY_BUF(YE_), ring, Buf::state)) || (st = f(EPH_NBODY_BUF(VE_), vec, Buf::state)))) ||
                (st = f(EPH_NBODY_BUF(fast_partial_), fast_partial_doubles(g.npad_), Buf::lazy)) ||
                (st = f(EPH_NBODY_BUF(posf_), 4 * bodies, Buf::lazy)) ||
-               (st = f(EPH_NBODY_BUF(gang_args_), (size_t)0, Buf::lazy)) ||                // (one LmArgs per system of the gang)
-               (st = f(EPH_NBODY_BUF(startup_args_), (size_t)0, Buf::lazy)));
+               (st = f(EPH_NBODY_BUF(gang_.dev), (size_t)0, Buf::lazy)) ||                 // (one LmArgs per system of the gang)
+               (st = f(EPH_NBODY_BUF(startup_.dev), (size_t)0, Buf::lazy)));
 #undef EPH_NBODY_BUF
         return st;
     }
 
-    int64_t deferred_time_steps_ = 0;         // advance_many: `time = time + h` replays still owed (run after the gang's launch)
-    std::vector<LmArgs> *collect_ = nullptr;  // advance_many: lm_batch hands its launch arguments over instead of launching
+    // gang_frame on the lead: the event that joins the members' streams to the lead's and releases them behind the launch, and the one
+    // behind the argument copy, which guards the pinned twins of gang_ and startup_ both
     hipEvent_t gang_ev_ = nullptr, gang_copy_ev_ = nullptr;
-    LmArgs *gang_host_ = nullptr;             // pinned source of the gang's argument copy (so advance_many need not wait for it)
-    size_t gang_host_count_ = 0;
-    LmStartupArgs *startup_host_ = nullptr;   // the same for the start-up gang (gang_copy_ev_ guards both)
-    size_t startup_host_count_ = 0;
 };
 
 // Polynomial<DVec3> (SmallVec<[DVec3; 8]>)   ephemeris/src/trajectory.rs:337-396

@@ -34,9 +34,8 @@ NBodyIntegration::~NBodyIntegration() {
         for (auto *v : {&ev_pending_, &ev_free_})
             for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
         if (gang_ev_) (void)hipEventDestroy(gang_ev_);
+        // (the pinned arrays of gang_ and startup_ go with the members, behind this wait for the last copy out of them)
         if (gang_copy_ev_) { (void)hipEventSynchronize(gang_copy_ev_); (void)hipEventDestroy(gang_copy_ev_); }
-        if (gang_host_) (void)hipHostFree(gang_host_);
-        if (startup_host_) (void)hipHostFree(startup_host_);
         (void)hipStreamDestroy(stream_);
     }
 }
@@ -246,17 +245,22 @@ int64_t NBodyIntegration::startup_small_steps(int64_t want, double *t_after) con
     if (t_after) *t_after = t;
     return m > 0 ? m : 0;
 }
-void NBodyIntegration::fill_startup_args(LmStartupArgs &g, int64_t m) const {
-    g = LmStartupArgs{};
-    SrknSmallArgs &a = g.s;
+// what a launch of the single-workgroup SRKN stage loop takes from the handle, for steps of size h (the substeps of the start-up, the
+// steps of an SRKN method): Y / YE are the ring's base, which is slot 0 -- the SRKN working position, and where the start-up kernel's
+// ring begins
+void NBodyIntegration::fill_srkn_args(SrknSmallArgs &a, double h) const {
     a.n = n_; a.npad = npad_;
     a.stages = rk_.stages; a.fsal = rk_.fsal ? 1 : 0;
     a.starter_i = starter_i_;
     a.pos[0] = P_[pp_].p; a.pos[1] = P_[pp_ ^ 1].p;
     a.Y = Y_.p; a.V = V_.p; a.ASR = ASR_.p;
     a.YE = compensated_ ? YE_.p : nullptr; a.VE = compensated_ ? VE_.p : nullptr;
-    for (int s = 0; s < rk_.stages; ++s) { a.hb[s] = h_sub_ * rk_.B[s]; a.ha[s] = h_sub_ * rk_.A[s]; }
+    for (int s = 0; s < rk_.stages; ++s) { a.hb[s] = h * rk_.B[s]; a.ha[s] = h * rk_.A[s]; }
     a.samp = samp_;
+}
+void NBodyIntegration::fill_startup_args(LmStartupArgs &g, int64_t m) const {
+    g = LmStartupArgs{};
+    fill_srkn_args(g.s, h_sub_);
     g.A = A_.p;
     g.L = L_; g.cur = cur_;
     g.m = (int)m; g.substeps = substeps_;
@@ -265,9 +269,9 @@ void NBodyIntegration::commit_startup(int64_t m, double t_after) {
     const uint64_t steps = (uint64_t)m * (uint64_t)substeps_;
     // the first force evaluation and the FSAL table's first stage of the very first substep; per substep the other stages; per macro
     // step the closing force
-    evals_ += (starter_i_ == 0 ? 1 + (rk_.fsal ? 1 : 0) : 0) + steps * (uint64_t)(rk_.fsal ? rk_.stages - 1 : rk_.stages) + (uint64_t)m;
+    evals_ += (starter_i_ == 0 ? 1 + (rk_.fsal ? 1 : 0) : 0) + steps * srkn_step_evals() + (uint64_t)m;
     if ((steps * (uint64_t)rk_.stages) & 1) pp_ ^= 1;                  // every stage swaps the packed position buffers
-    cur_ = (int)(((int64_t)cur_ - m % L_ + L_) % L_);
+    turn_ring(m);
     starter_i_ += (uint32_t)steps;
     time_ = t_after;
 }
@@ -335,7 +339,7 @@ struct NBodyIntegration::TimingGuard {
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};   // null: not open (this batch is not timed), or closed
     ~TimingGuard() { if (ev.second) ig.ev_free_.push_back(ev); }
     int open() {
-        if (!ig.timing_ || ig.collect_) return EPH_OK;         // (a gang's launch is timed by advance_many, around the one launch)
+        if (!ig.timing_) return EPH_OK;
         if (ig.ev_pending_.size() >= 1024) (void)ig.resolve_timing();
         if (!ig.ev_free_.empty()) { ev = ig.ev_free_.back(); ig.ev_free_.pop_back(); }
         else { EPH_HIP(hipEventCreate(&ev.first)); EPH_HIP(hipEventCreate(&ev.second)); }
@@ -375,7 +379,8 @@ void NBodyIntegration::next_level(LmArgs &a) {
 
 // The frame of a batch of k steps, stated once for lm_batch, lm_batch_double and srkn_batch: a timed interval around the launches that
 // queue(launches) makes (it returns a status and says how many they were), then the k-fold `problem.time = problem.time + h` -- AFTER
-// the launches are queued, so that it runs under the kernel (steps_certain) -- which a gang's batch leaves to advance_many.
+// the launches are queued, so that it runs under the kernel (steps_certain). A handle's own batches only: a gang's members never come
+// through here (gang_frame below: fill_gang_args / commit_gang).
 template <typename Queue>
 int NBodyIntegration::batch_frame(int64_t k, Queue &&queue) {
     int st;
@@ -384,10 +389,9 @@ int NBodyIntegration::batch_frame(int64_t k, Queue &&queue) {
     uint64_t launches = 0;
     if ((st = queue(launches))) return st;
     if (timing_) kernel_launches_ += launches;
-    if (!collect_) count_launches(launches);              // (a gang's one launch is counted by advance_many)
+    count_launches(launches);
     if ((st = timing.close())) return st;
-    if (collect_) deferred_time_steps_ += k;              // advance_many replays them once the gang is launched
-    else for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;
+    for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;
     return EPH_OK;
 }
 
@@ -400,7 +404,6 @@ int NBodyIntegration::lm_batch_double(int64_t k) {
     fill_lm_args(a);
     a.lo = 0; a.hi = n_;
     d.YE = YE_.p; d.VE = VE_.p;
-    if (collect_) return EPH_ERR_UNSUPPORTED;                          // (gang_ready refuses a <Double> handle first)
     if (path_ == 2 && n_ > kGangMaxN) {
         set_last_error_text("a <Double> handle takes the single-workgroup kernel up to 32 bodies");
         return EPH_ERR_UNSUPPORTED;
@@ -411,7 +414,7 @@ int NBodyIntegration::lm_batch_double(int64_t k) {
         point_lm_args(a);
         if (persistent) {
             if ((st = launch_lm_double_small(pv_, stream_, d, k))) return st;
-            cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
+            turn_ring(k);
             launches = 1;
             return EPH_OK;
         }
@@ -460,14 +463,12 @@ int NBodyIntegration::lm_batch(int64_t k) {
     }
     const bool persistent = n_ <= kSmallN && path_ != 1 && path_ != 3 && !fast;
     if (path_ == 2 && n_ > kSmallN) return EPH_ERR_UNSUPPORTED;
-    if (collect_ && !persistent) return EPH_ERR_UNSUPPORTED;           // (advance_many checks gang_ready first)
     st = batch_frame(k, [&](uint64_t &launches) -> int {
         int st;
         point_lm_args(a);
         if (persistent) {
-            if (collect_) collect_->push_back(a);                           // launched by advance_many with the gang's others
-            else if ((st = launch_lm_persistent(pv_, stream_, a, k))) return st;
-            cur_ = (int)(((int64_t)cur_ - k % L_ + L_) % L_);
+            if ((st = launch_lm_persistent(pv_, stream_, a, k))) return st;
+            turn_ring(k);
             launches = 1;
             return EPH_OK;
         }
@@ -512,22 +513,14 @@ int NBodyIntegration::lm_batch(int64_t k) {
 // neither of srkn_step's two tests fires in these k steps (steps_available)
 int NBodyIntegration::srkn_batch(int64_t k) {
     SrknSmallArgs a{};
-    a.n = n_; a.npad = npad_;
-    a.stages = rk_.stages; a.fsal = rk_.fsal ? 1 : 0;
-    a.starter_i = starter_i_;
-    a.pos[0] = P_[pp_].p; a.pos[1] = P_[pp_ ^ 1].p;
-    a.Y = Yslot(0); a.V = V_.p; a.ASR = ASR_.p;
-    a.YE = compensated_ ? YEslot(0) : nullptr; a.VE = compensated_ ? VE_.p : nullptr;
-    for (int s = 0; s < rk_.stages; ++s) { a.hb[s] = h_ * rk_.B[s]; a.ha[s] = h_ * rk_.A[s]; }
-    a.samp = samp_;
+    fill_srkn_args(a, h_);
     const int st = batch_frame(k, [&](uint64_t &launches) -> int {
         launches = 1;
         return compensated_ ? launch_srkn_double_small(pv_, stream_, a, k) : launch_srkn_small(pv_, stream_, a, k);
     });
     if (st) return st;
     // the rest of the bookkeeping of k calls of srkn_step
-    const uint64_t per_step = (uint64_t)(rk_.fsal ? rk_.stages - 1 : rk_.stages);
-    evals_ += (uint64_t)k * per_step + (rk_.fsal && starter_i_ == 0 ? 1 : 0);
+    evals_ += (uint64_t)k * srkn_step_evals() + (rk_.fsal && starter_i_ == 0 ? 1 : 0);
     starter_i_ += (uint32_t)k;
     return EPH_OK;
 }
@@ -536,7 +529,7 @@ int NBodyIntegration::advance(int64_t n_steps, int64_t *done_out) { return advan
 
 // (advance_many continues here behind a start-up gang: `done` of the call's n_steps are taken, *done_out counts from there on)
 int NBodyIntegration::advance_from(int64_t done, int64_t n_steps, int64_t *done_out) {
-    if (failed_) { if (done_out) *done_out = 0; return failed_; }     // a gang launch failed after this handle's bookkeeping had moved
+    if (failed_) { if (done_out) *done_out = 0; return failed_; }     // a gang launch with this member failed once something was queued (gang_frame)
     EPH_HIP(hipSetDevice(device_));
     const int64_t done_before = done;
     int st = EPH_OK;
@@ -600,48 +593,98 @@ bool NBodyIntegration::gang_ready(int64_t k) const {
     return steps_available(k, &after) == k;
 }
 
-// The start-up macro steps of `count` members, m[i] of member i, in ONE launch on the lead's stream (a workgroup per member); the
-// caller has established each m[i] by startup_small_steps, which also gave t_after[i]. The choreography of the steady gang below.
-int NBodyIntegration::startup_gang(NBodyIntegration *const *igs, int count, const int64_t *m, const double *t_after) {
+// ---- The gangs of advance_many -------------------------------------------------------------------------------------------------
+// One gang launch, stated once for the start-up gang (LmStartupArgs, k_lm_startup_small) and the steady one (LmArgs, k_lm_small): the
+// members igs[0 .. count), all on the device of the lead igs[0], a workgroup each in ONE launch on the lead's stream. `ga` is the
+// lead's argument array of the gang's kind. fill(host[i], i) writes member i's launch arguments and moves nothing; launch(device
+// array) queues the kernel on the lead's stream; commit(i) is member i's host bookkeeping, which runs under the kernel. A `timed`
+// frame whose lead has enable_timing() on brackets the launch with the lead's event pair and waits for it (the steady gang; the
+// start-up gang is not timed: kernel_time counts steady-state kernels). Otherwise not synchronised: like eph_nbody_advance, the
+// call only queues.
+template <typename Args, typename Fill, typename Launch, typename Commit>
+int NBodyIntegration::gang_frame(NBodyIntegration *const *igs, int count, GangArgs<Args> &ga, bool timed, Fill &&fill, Launch &&launch,
+                                 Commit &&commit) {
     NBodyIntegration &lead = *igs[0];
-    for (int i = 0; i < count; ++i)
-        if (m[i] < 1 || m[i] > igs[i]->startup_left()) return EPH_ERR_BAD_ARGUMENT;
     EPH_HIP(hipSetDevice(lead.device_));
-    // everything that can fail for lack of resources happens BEFORE any handle's bookkeeping moves
-    int st;
-    if ((st = lead.startup_args_.reserve((size_t)count))) return st;
+    // everything that can fail for lack of resources happens BEFORE anything is queued and before any handle's bookkeeping moves
+    if (const int st = ga.dev.reserve((size_t)count)) return st;
     if (!lead.gang_ev_) EPH_HIP(hipEventCreateWithFlags(&lead.gang_ev_, hipEventDisableTiming));
     if (!lead.gang_copy_ev_) EPH_HIP(hipEventCreateWithFlags(&lead.gang_copy_ev_, hipEventDisableTiming));
-    // the previous gang's argument copy out of the pinned array must have completed before it is rewritten (or freed)
+    // the previous gang's argument copy out of a pinned array (either kind's) must have completed before one is rewritten or freed
     EPH_HIP(hipEventSynchronize(lead.gang_copy_ev_));
-    if (lead.startup_host_count_ < (size_t)count) {
-        if (lead.startup_host_) (void)hipHostFree(lead.startup_host_);
-        lead.startup_host_ = nullptr;
-        lead.startup_host_count_ = 0;
+    if (ga.host_count < (size_t)count) {
+        if (ga.host) (void)hipHostFree(ga.host);
+        ga.host = nullptr;
+        ga.host_count = 0;
         const size_t want = (size_t)count + (size_t)count / 2;
-        EPH_HIP(hipHostMalloc((void **)&lead.startup_host_, sizeof(LmStartupArgs) * want, hipHostMallocDefault));
-        lead.startup_host_count_ = want;
+        EPH_HIP(hipHostMalloc((void **)&ga.host, sizeof(Args) * want, hipHostMallocDefault));
+        ga.host_count = want;
     }
-    for (int i = 0; i < count; ++i) igs[i]->fill_startup_args(lead.startup_host_[i], m[i]);
-    // From the first queued operation on a failure marks every member failed, as the steady gang's does
+    for (int i = 0; i < count; ++i) fill(ga.host[i], i);
+    // From the first queued operation on, a failure marks every member failed (every later call returns the status) instead of
+    // handing the handles back as if nothing had happened: their streams may be half joined, and behind the launch their bookkeeping
+    // is ahead of a device state nobody vouches for.
     auto fail = [&](int status) {
         for (int i = 0; i < count; ++i) igs[i]->failed_ = status;
         return status;
     };
 #define EPH_GANG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(#call, e_); return fail(EPH_ERR_HIP); } } while (0)
+    // the launch goes on the lead's stream, behind whatever the other members still have in flight on theirs
     for (int i = 1; i < count; ++i) {
         EPH_GANG_HIP(hipEventRecord(lead.gang_ev_, igs[i]->stream_));
         EPH_GANG_HIP(hipStreamWaitEvent(lead.stream_, lead.gang_ev_, 0));
     }
-    EPH_GANG_HIP(hipMemcpyAsync(lead.startup_args_.p, lead.startup_host_, sizeof(LmStartupArgs) * (size_t)count, hipMemcpyHostToDevice, lead.stream_));
+    EPH_GANG_HIP(hipMemcpyAsync(ga.dev.p, ga.host, sizeof(Args) * (size_t)count, hipMemcpyHostToDevice, lead.stream_));
     EPH_GANG_HIP(hipEventRecord(lead.gang_copy_ev_, lead.stream_));
-    if ((st = launch_lm_startup_small_many(lead.pv_, lead.stream_, lead.startup_args_.p, count))) return fail(st);
+    timed = timed && lead.timing_;
+    if (timed) EPH_GANG_HIP(hipEventRecord(lead.ev0_, lead.stream_));
+    if (const int st = launch(ga.dev.p)) return fail(st);
     count_launches(1);
-    for (int i = 0; i < count; ++i) igs[i]->commit_startup(m[i], t_after[i]);     // host bookkeeping under the kernel
+    for (int i = 0; i < count; ++i) commit(i);                          // host bookkeeping under the kernel
+    if (timed) {
+        EPH_GANG_HIP(hipEventRecord(lead.ev1_, lead.stream_));
+        EPH_GANG_HIP(hipEventSynchronize(lead.ev1_));
+        float ms = 0;
+        EPH_GANG_HIP(hipEventElapsedTime(&ms, lead.ev0_, lead.ev1_));
+        lead.kernel_ms_ += ms;
+    }
+    // the members' streams go on behind the launch
     EPH_GANG_HIP(hipEventRecord(lead.gang_ev_, lead.stream_));
     for (int i = 1; i < count; ++i) EPH_GANG_HIP(hipStreamWaitEvent(igs[i]->stream_, lead.gang_ev_, 0));
 #undef EPH_GANG_HIP
     return EPH_OK;
+}
+
+// The start-up macro steps of `count` members, m[i] of member i, in one gang launch; the caller has established each m[i] by
+// startup_small_steps, which also gave t_after[i]
+int NBodyIntegration::startup_gang(NBodyIntegration *const *igs, int count, const int64_t *m, const double *t_after) {
+    for (int i = 0; i < count; ++i)
+        if (m[i] < 1 || m[i] > igs[i]->startup_left()) return EPH_ERR_BAD_ARGUMENT;
+    NBodyIntegration &lead = *igs[0];
+    return gang_frame(igs, count, lead.startup_, false,
+                      [&](LmStartupArgs &g, int i) { igs[i]->fill_startup_args(g, m[i]); },
+                      [&](const LmStartupArgs *args) { return launch_lm_startup_small_many(lead.pv_, lead.stream_, args, count); },
+                      [&](int i) { igs[i]->commit_startup(m[i], t_after[i]); });
+}
+
+// The steady gang's member: what advance(k) comes to on a handle that gang_ready(k) has accepted -- lm_batch's single-workgroup
+// launch in batch_frame -- in two halves, the launch arguments (nothing moves) and the bookkeeping once the launch is queued
+void NBodyIntegration::fill_gang_args(LmArgs &a) const {
+    static const int dbg = [] { const char *e = getenv("EPH_DEBUG_SMALL"); return e ? atoi(e) : 0; }();   // tuning switches of k_lm_small
+    a = LmArgs{};                                                       // (do_predict and step stay 0, as in lm_batch's one launch)
+    fill_lm_args(a);
+    a.lo = lo_; a.hi = hi_;
+    a.samp = samp_;
+    point_lm_args(a);
+    a.wg_flags = dbg;
+}
+void NBodyIntegration::commit_gang(int64_t k) {
+    turn_ring(k);
+    lm_i_ += (uint32_t)k;
+    evals_ += (uint64_t)k;
+    if (timing_) kernel_launches_ += 1;                                 // every timed member counts the shared launch; the lead alone times it
+    samp_ = SampleArgs{};
+    for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;                 // behind the launch, under the kernel (steps_certain)
 }
 
 int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int64_t k) {
@@ -653,8 +696,8 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
             if (igs[j] == igs[i]) return EPH_ERR_BAD_ARGUMENT;          // a system cannot be in the gang twice
     }
     // 1. The start-up. Every plain member that can take macro steps in one launch (startup_small_steps) takes m_i = min(k, macro
-    // steps left) of them; at least two on one device with one ring length and evaluation order share the launch. Anyone else --
-    // a <Double> member too -- does its start-up in its own advance below.
+    // steps left) of them; at least two that can share a launch do. Anyone else -- a <Double> member too -- does its start-up in
+    // its own advance below.
     std::vector<int64_t> taken((size_t)count, 0);
     {
         std::vector<NBodyIntegration *> mem;
@@ -665,8 +708,7 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
             NBodyIntegration &ig = *igs[i];
             double t = 0.0;
             const int64_t m = ig.failed_ || ig.compensated_ ? 0 : ig.startup_small_steps(k, &t);
-            if (m <= 0) continue;
-            if (!mem.empty() && (ig.device_ != mem[0]->device_ || ig.L_ != mem[0]->L_ || ig.pv_ != mem[0]->pv_)) continue;
+            if (m <= 0 || (!mem.empty() && !ig.shares_launch_with(*mem[0]))) continue;
             mem.push_back(&ig); who.push_back(i); ms.push_back(m); ts.push_back(t);
         }
         if (mem.size() >= 2) {
@@ -674,14 +716,15 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
             for (size_t j = 0; j < mem.size(); ++j) taken[(size_t)who[j]] = ms[j];
         }
     }
-    // 2. What is left of k. The same positive number for every member: the code below with that number. Otherwise -- and where a
-    // member's sampling schedule has started counting in the start-up launch -- each member finishes its own call.
-    bool same = true, sampled_on = false;
-    for (int i = 0; i < count; ++i) {
-        same = same && taken[(size_t)i] == taken[0];
-        sampled_on = sampled_on || (taken[(size_t)i] > 0 && taken[(size_t)i] < k && igs[i]->samp_.period);
-    }
-    if (!same || sampled_on || taken[0] == k) {
+    // 2. What is left of k: the steady gang, when it is the same positive number for every member, no member's sampling schedule
+    // has started counting in the start-up launch, and every member is ready for that many steps in a launch shared with the lead.
+    const int64_t left = k - taken[0];
+    bool gang = count > 1 && left > 0;
+    for (int i = 0; i < count && gang; ++i)
+        gang = taken[(size_t)i] == taken[0] && !(taken[(size_t)i] > 0 && igs[i]->samp_.period) && igs[i]->gang_ready(left) &&
+               igs[i]->shares_launch_with(*igs[0]);
+    if (!gang) {
+        // the plain meaning: each member finishes its own call, the first status other than EPH_OK is the call's
         int first = EPH_OK;
         for (int i = 0; i < count; ++i) {
             if (taken[(size_t)i] == k) { igs[i]->samp_ = SampleArgs{}; continue; }
@@ -690,83 +733,13 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
         }
         return first;
     }
-    k -= taken[0];
-    bool gang = count > 1;
-    for (int i = 0; i < count && gang; ++i)
-        gang = igs[i]->gang_ready(k) && igs[i]->device_ == igs[0]->device_ && igs[i]->L_ == igs[0]->L_ && igs[i]->pv_ == igs[0]->pv_;
-    if (!gang) {                                                        // the plain meaning: advance(k) on each
-        int first = EPH_OK;
-        for (int i = 0; i < count; ++i) {
-            const int st = igs[i]->advance(k);
-            if (st && !first) first = st;
-        }
-        return first;
-    }
-    NBodyIntegration &lead = *igs[0];
-    EPH_HIP(hipSetDevice(lead.device_));
     for (int i = 0; i < count; ++i)
         if (igs[i]->failed_) return igs[i]->failed_;
-    // everything that can fail for lack of resources happens BEFORE any handle's bookkeeping moves
-    int st;
-    if ((st = lead.gang_args_.reserve((size_t)count))) return st;
-    if (!lead.gang_ev_) EPH_HIP(hipEventCreateWithFlags(&lead.gang_ev_, hipEventDisableTiming));
-    if (!lead.gang_copy_ev_) EPH_HIP(hipEventCreateWithFlags(&lead.gang_copy_ev_, hipEventDisableTiming));
-    if (lead.gang_host_count_ < (size_t)count) {
-        if (lead.gang_host_) { EPH_HIP(hipEventSynchronize(lead.gang_copy_ev_)); (void)hipHostFree(lead.gang_host_); }
-        lead.gang_host_ = nullptr;
-        lead.gang_host_count_ = 0;
-        const size_t want = (size_t)count + (size_t)count / 2;
-        EPH_HIP(hipHostMalloc((void **)&lead.gang_host_, sizeof(LmArgs) * want, hipHostMallocDefault));
-        lead.gang_host_count_ = want;
-    }
-    // the previous gang's argument copy out of the pinned array must have completed before it is rewritten
-    EPH_HIP(hipEventSynchronize(lead.gang_copy_ev_));
-    std::vector<LmArgs> args;
-    args.reserve((size_t)count);
-    for (int i = 0; i < count; ++i) {
-        NBodyIntegration &ig = *igs[i];
-        ig.collect_ = &args;
-        int64_t done = 0;
-        st = ig.advance(k, &done);                                      // bookkeeping as usual, launch arguments into `args`
-        ig.collect_ = nullptr;
-        if (st || done != k || args.size() != (size_t)i + 1) {
-            // (cannot happen after gang_ready: no launch was made, so handles 0..i are ahead of their device state)
-            for (int j = 0; j <= i; ++j) { igs[j]->replay_deferred_time(); igs[j]->failed_ = st ? st : EPH_ERR_HIP; }
-            return st ? st : EPH_ERR_HIP;
-        }
-    }
-    static const int dbg = [] { const char *e = getenv("EPH_DEBUG_SMALL"); return e ? atoi(e) : 0; }();   // tuning switches of k_lm_small
-    for (int i = 0; i < count; ++i) { lead.gang_host_[i] = args[(size_t)i]; lead.gang_host_[i].wg_flags = dbg; }
-    // From here on a failure leaves every handle's bookkeeping k steps ahead of its device state: the handles are marked
-    // failed (every later call returns the status) instead of being handed back as if nothing had happened.
-    auto fail = [&](int status) {
-        for (int i = 0; i < count; ++i) { igs[i]->replay_deferred_time(); igs[i]->failed_ = status; }
-        return status;
-    };
-#define EPH_GANG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(#call, e_); return fail(EPH_ERR_HIP); } } while (0)
-    // the gang's launch goes on the lead's stream, behind whatever the other handles still have in flight on theirs
-    for (int i = 1; i < count; ++i) {
-        EPH_GANG_HIP(hipEventRecord(lead.gang_ev_, igs[i]->stream_));
-        EPH_GANG_HIP(hipStreamWaitEvent(lead.stream_, lead.gang_ev_, 0));
-    }
-    EPH_GANG_HIP(hipMemcpyAsync(lead.gang_args_.p, lead.gang_host_, sizeof(LmArgs) * (size_t)count, hipMemcpyHostToDevice, lead.stream_));
-    EPH_GANG_HIP(hipEventRecord(lead.gang_copy_ev_, lead.stream_));
-    if (lead.timing_) EPH_GANG_HIP(hipEventRecord(lead.ev0_, lead.stream_));
-    st = launch_lm_small_many(lead.pv_, lead.stream_, lead.gang_args_.p, count, lead.L_, k);
-    if (st) return fail(st);
-    count_launches(1);
-    for (int i = 0; i < count; ++i) igs[i]->replay_deferred_time();     // host bookkeeping under the kernel
-    if (lead.timing_) {
-        EPH_GANG_HIP(hipEventRecord(lead.ev1_, lead.stream_));
-        EPH_GANG_HIP(hipEventSynchronize(lead.ev1_));
-        float ms = 0;
-        EPH_GANG_HIP(hipEventElapsedTime(&ms, lead.ev0_, lead.ev1_));
-        lead.kernel_ms_ += ms;
-    }
-    EPH_GANG_HIP(hipEventRecord(lead.gang_ev_, lead.stream_));
-    for (int i = 1; i < count; ++i) EPH_GANG_HIP(hipStreamWaitEvent(igs[i]->stream_, lead.gang_ev_, 0));
-#undef EPH_GANG_HIP
-    return EPH_OK;                                                      // not synchronised: like eph_nbody_advance, the call only queues
+    NBodyIntegration &lead = *igs[0];
+    return gang_frame(igs, count, lead.gang_, true,
+                      [&](LmArgs &a, int i) { igs[i]->fill_gang_args(a); },
+                      [&](const LmArgs *args) { return launch_lm_small_many(lead.pv_, lead.stream_, args, count, lead.L_, left); },
+                      [&](int i) { igs[i]->commit_gang(left); });
 }
 
 // The read-back of get_state and get_acc. One device: the transposition kernels write straight into a pinned, device-mapped staging

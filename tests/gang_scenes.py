@@ -218,10 +218,10 @@ def expected_gang(members, method, oracle):
 
 class LaunchProbe:
     """Was a ganged call ONE launch for this member? An observable of the existing ABI, as it is today (nothing is exported for
-    it): a member that is not the gang's lead and has enable_timing() on skips its own event pair while its launch arguments are
-    collected (TimingGuard::open under collect_, nbody.cpp) but counts the launch -- kernel_time() keeps its milliseconds EXACTLY
-    and its launch count rises by one. Where advance_many / step_n_many fall back to separate advances the member times its own
-    launch and the milliseconds grow."""
+    it): a member that is not the gang's lead and has enable_timing() on opens no event pair of its own -- the shared launch is
+    timed by the lead alone (gang_frame, nbody.cpp) -- but counts the launch (commit_gang): kernel_time() keeps its milliseconds
+    EXACTLY and its launch count rises by one. Where advance_many / step_n_many fall back to separate advances the member times
+    its own launch and the milliseconds grow."""
 
     def __init__(self, handle):
         self.h = handle

@@ -1,13 +1,14 @@
 """-m gpu: the lifecycle calls of the N-body host side (csrc/nbody.cpp, csrc/propagator.cpp) under a failing allocation, and the
-read-back through its NULL arguments. eph_nbody_create, eph_nbody_clone, the first steady batch of the fast paths, eph_prop_clone and
-eph_prop_step_n are walked with the k-th device allocation failing for k = 1, 2, ... (eph_debug_fail_alloc: a host function returns
+read-back through its NULL arguments. eph_nbody_create, eph_nbody_clone, the first steady batch of the fast paths, eph_prop_clone,
+eph_prop_step_n and the first eph_nbody_advance_many of a steady and of a fresh gang are walked with the k-th device allocation failing for k = 1, 2, ... (eph_debug_fail_alloc: a host function returns
 EPH_ERR_OUT_OF_MEMORY before any HIP call; nothing is provoked on the device). After every failure the objects involved go on bit for
 bit like twins that never saw one. No tolerance anywhere.
 
 Each case is one child process (this file run as a script) on the test-hooks library, under its own timeout; after a child that died
 of a signal or ran into its timeout no further child is started. Every case asserts how many device allocations its call makes
-(ALLOCATIONS, measured on the commit before the handle's buffers were stated once: profiles/nbody_host_frame.md): a buffer dropped
-from, or added to, a walk over the statement of NBodyIntegration's buffers moves a count.
+(ALLOCATIONS, measured on the commit before the handle's buffers were stated once: profiles/nbody_host_frame.md; the two gang cases
+on the commit before the gangs shared one launch frame: profiles/gang_frame.md): a buffer dropped from, or added to, a walk over the
+statement of NBodyIntegration's buffers moves a count.
 
 The sharded read-back is tests/test_gpu_shard.py's."""
 import ctypes as C
@@ -40,6 +41,8 @@ ALLOCATIONS = {"create": 8,            # P_[0], P_[1], Y_, A_, V_, ASR_, mu_, st
                "prop-clone": 14,       # the integration's 8, log_, d_period_, d_phase_, d_offset_, pend_co_, pend_nc_
                "prop-step-fit": 5,     # d_first_, d_deg_, d_src_, d_cnt_, d_region_ (a failed pending list spills and retries: no failure)
                "prop-step-advance": 1, # fast_partial_ (the steady batch's fit reuses the start-up's scratch)
+               "gang-steady": 1,       # the lead's LmArgs array
+               "gang-startup": 1,      # the lead's LmStartupArgs array
                "read-back": 0}
 counted = {}
 
@@ -205,7 +208,32 @@ def prop_step_advance_case(ea, H_):
     counted["prop-step-advance"] = failures
 
 
-# ---- 6. read-back -------------------------------------------------------------------------------------------------------------------
+# ---- 6. eph_nbody_advance_many: the argument array of the gang's lead ---------------------------------------------------------------------
+def gang_case(ea, H_, name, entered, k):
+    """three 3-body handles, member i entered after entered[i] steps alone; their first advance_many(k). A failure leaves every member
+    where it was and none failed for good: the retry succeeds, and the members go on like twins that never saw a failure"""
+    gang, twins = ([integration(ea, 3, steps=s) for s in entered] for _ in range(2))
+    arr = (C.c_void_p * len(gang))(*[g._h for g in gang])
+
+    def failed(f, out):
+        for i, (g, t) in enumerate(zip(gang, twins)):
+            assert same_state(g, t, f"k = {f}: member {i} has not moved") == entered[i]
+    failures, _ = failing_allocations(ea, H_, lambda: (ea._lib().eph_nbody_advance_many(arr, len(gang), k), None, last_error(ea)), failed)
+    ea.advance_many(twins, k)
+    for i, (g, t) in enumerate(zip(gang, twins)):
+        assert same_state(g, t, f"member {i}: the retried call") == entered[i] + k
+    for i, (g, t) in enumerate(zip(gang, twins)):
+        g.advance(3)
+        t.advance(3)
+        same_state(g, t, f"member {i}: three steps alone behind it")
+    ea.advance_many(gang, 5)
+    ea.advance_many(twins, 5)
+    for i, (g, t) in enumerate(zip(gang, twins)):
+        assert same_state(g, t, f"member {i}: the gang's next call") == entered[i] + k + 8
+    counted[name] = failures
+
+
+# ---- 7. read-back -------------------------------------------------------------------------------------------------------------------
 def read_back_case(ea, H_):
     L = ea._lib()
     for n in (3, 64, 65):
@@ -243,6 +271,8 @@ CASES = {"create": lambda ea, H_: (create_case(ea, H_, ""), create_case(ea, H_, 
                                         first_batch_case(ea, H_, ea.PATH_F32_PAIRS, "first-batch-f32")),
          "prop-clone": prop_clone_case,
          "prop-step": lambda ea, H_: (prop_step_fit_case(ea, H_), prop_step_advance_case(ea, H_)),
+         "gang-steady": lambda ea, H_: gang_case(ea, H_, "gang-steady", (STARTUP, STARTUP + 1, STARTUP + 2), 7),
+         "gang-startup": lambda ea, H_: gang_case(ea, H_, "gang-startup", (0, 0, 0), STARTUP),
          "read-back": read_back_case}
 
 

@@ -232,6 +232,25 @@ def test_33_bodies_and_the_timed_handle(gpu):
         assert g.kernel_time()[1] == 1 and g.eval_count() == ss.startup_evals(12) + 5
 
 
+@pytest.mark.parametrize("method", list(ss.METHODS))
+def test_a_timed_gang_across_the_start_up(gpu, method):
+    """three fresh plain members, timing on the lead and on one other, advance_many(L + 5): eph_nbody_kernel_time keeps counting the
+    steady-state kernels only in a gang too. Both gain ONE launch, the steady one; the lead times it, the other member gains no
+    milliseconds of its own (gs.LaunchProbe); every member has the oracle's bits"""
+    L, scene = ss.METHODS[method], SCENES["sun_earth_moon"]
+    gang = [scene.make(gpu.NBodyIntegration, method) for _ in range(3)]
+    lead, other = gs.LaunchProbe(gang[0]), gs.LaunchProbe(gang[2])
+    gpu.advance_many(gang, L + 5)
+    for g in gang:
+        g.sync()
+    ms, launches = lead.after_call()
+    assert launches == 1 and ms > 0.0, f"{method}: the lead: {launches} launches, {ms} ms"
+    other.assert_ganged(f"{method}: fresh gang of 3, advance_many(L + 5), member 2")
+    want = oracle_play(scene, method, (L + 5,))[0][1]
+    for j, g in enumerate(gang):
+        ss.assert_same(ss.record(g), want, f"{method}: member {j} against the oracle")
+
+
 # ---- launch counts: what fails without the one-launch start-up
 class Counted:
     """the handles of the launch-count tests, made in the test-hooks library (the count is that library's own), and its count"""
