@@ -1090,4 +1090,4 @@ def apsides_join(lhs, rhs, at):
     return t[:n.value].copy(), d[:n.value].copy(), k[:n.value].copy(), b[:n.value].copy()
 
 
-from .convergence import ConvergenceError, convergence  # noqa: E402,F401  (needs NBodyIntegration above)
+from .convergence import ConvergenceError, convergence, convergence_gang  # noqa: E402,F401  (needs NBodyIntegration above)

@@ -133,6 +133,20 @@ int launch_srkn_double_small(int pv, hipStream_t s, const SrknSmallArgs &a, int6
     if (a.n > kGangMaxN || a.stages < 1 || a.stages > 32 || !a.YE || !a.VE) return EPH_ERR_UNSUPPORTED;
     return t->srkn_double_small(s, a, nsteps);
 }
+// (the blocks are in device memory: the caller has held each to the terms of the two launchers above, on their host twin -- the
+// assertion of NBodyIntegration::fill_srkn_gang_args)
+int launch_srkn_small_many(int pv, hipStream_t s, const SrknGangArgs *argv_dev, int count) {
+    const PairKernels *t = table(pv);
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
+    if (count <= 0) return EPH_OK;
+    return t->srkn_small_many(s, argv_dev, count);
+}
+int launch_srkn_double_small_many(int pv, hipStream_t s, const SrknGangArgs *argv_dev, int count) {
+    const PairKernels *t = table(pv);
+    if (!t) return EPH_ERR_BAD_ARGUMENT;
+    if (count <= 0) return EPH_OK;
+    return t->srkn_double_small_many(s, argv_dev, count);
+}
 static bool startup_small_sound(const LmStartupArgs &a) {
     return a.s.n >= 1 && a.s.n <= kGangMaxN && a.s.stages >= 1 && a.s.stages <= 32 && a.L >= 1 && a.L <= kMaxOrder && a.cur >= 0 &&
            a.cur < a.L && a.m >= 1 && a.substeps >= 1;

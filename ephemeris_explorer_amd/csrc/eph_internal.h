@@ -163,6 +163,16 @@ struct SrknSmallArgs {
 };
 int launch_srkn_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
 int launch_srkn_double_small(int pv, hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);
+// The gang form of the two (k_srkn_small_many): one workgroup per argument block of a device array, `count` of them. Every block
+// carries its own system, table, step and step count -- each member of an advance_many call stops at its own bound, so the count
+// cannot be a launch parameter as it is for k_lm_small's gang. One launch holds one state type (plain, or `<Double>`: YE / VE set
+// in every block) and one evaluation order.
+struct SrknGangArgs {
+    SrknSmallArgs s;
+    long long nsteps;          // >= 1
+};
+int launch_srkn_small_many(int pv, hipStream_t s, const SrknGangArgs *argv_dev, int count);
+int launch_srkn_double_small_many(int pv, hipStream_t s, const SrknGangArgs *argv_dev, int count);
 // a linear multistep handle's start-up in the same frame (k_lm_startup_small, step_srkn_small.hip): `m` macro steps of `substeps`
 // steps of the substepper's table `s` per launch, each closed by the force at the new front. s.Y / s.YE are the RING bases, s.starter_i
 // counts the substepper's steps (0: the force at the initial positions is evaluated first). The gang form runs one workgroup per
@@ -204,6 +214,8 @@ struct PairKernels {                        // one evaluation order's launchers 
     int (*lm_double_small)(hipStream_t, const LmDoubleArgs &, int64_t);
     int (*srkn_small)(hipStream_t, const SrknSmallArgs &, int64_t);
     int (*srkn_double_small)(hipStream_t, const SrknSmallArgs &, int64_t);
+    int (*srkn_small_many)(hipStream_t, const SrknGangArgs *, int);
+    int (*srkn_double_small_many)(hipStream_t, const SrknGangArgs *, int);
     int (*lm_startup_small)(hipStream_t, const LmStartupArgs &, bool);
     int (*lm_startup_small_many)(hipStream_t, const LmStartupArgs *, int);
     int (*lm_step_fast)(hipStream_t, const LmArgs &, double *, int, int, bool, float *, int, int, int, unsigned *);

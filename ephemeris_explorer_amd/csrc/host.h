@@ -275,8 +275,19 @@ public:
     // Either launch is one gang_frame: every member fills its block of the lead's argument array, the lead launches, every member
     // commits its bookkeeping under the kernel (fill_startup_args / commit_startup, fill_gang_args / commit_gang). No member's
     // advance() runs for a ganged launch.
+    // The symplectic members of the call are taken out first: those that srkn_gang_steps accepts, the plain ones and the `<Double>`
+    // ones apart, share ONE launch of k_srkn_small_many per kind when there are at least two (fill_srkn_gang_args /
+    // commit_srkn_gang), each with its own step count -- a member stops at its own bound and is left where its own advance(k)
+    // leaves it. A kind with one member, and every symplectic member that does not qualify, keeps its own advance. The call's
+    // status is the first other than EPH_OK in member order.
     static int advance_many(NBodyIntegration *const *igs, int count, int64_t k);
     bool gang_ready(int64_t k) const;          // advance(k) on this handle would be ONE launch of k_lm_small that takes all k steps
+    // A symplectic handle as a member of the SRKN gang: how many of the next k steps (at most 2^30 of them) one launch of the
+    // single-workgroup kernel takes -- steps_available -- and the status behind them; 0 where the handle keeps its own advance:
+    // not srkn_small_ready(), failed, or not one step to take.
+    int64_t srkn_gang_steps(int64_t k, int *status_after) const;
+    bool srkn_gang_ready(int64_t k) const { int after = EPH_OK; return k > 0 && k <= ((int64_t)1 << 30) && srkn_gang_steps(k, &after) == k; }
+    bool is_multistep() const { return is_multistep_; }
     // The one-launch start-up (k_lm_startup_small): how many of the next `want` steps it would take now -- min(want, macro steps
     // left) -- or 0 where the per-launch route has to run: started, not multistep, more than kGangMaxN bodies, sharded, a forced
     // per-launch path, between two substeps of an abandoned macro step, or one of the tests of startup_macro_step / srkn_step
@@ -296,11 +307,22 @@ private:
     static int startup_gang(NBodyIntegration *const *igs, int count, const int64_t *m, const double *t_after);
     void fill_gang_args(LmArgs &a) const;     // the steady gang's member, for k steps that gang_ready(k) has accepted: its launch arguments,
     void commit_gang(int64_t k);              // and the bookkeeping advance(k) would have left
+    // the SRKN gang's member, for k steps that srkn_gang_steps has accepted: srkn_batch(k) in the same two halves
+    void fill_srkn_gang_args(SrknGangArgs &g, int64_t k) const;
+    void commit_srkn_gang(int64_t k);
+    // the symplectic members of an advance_many call (all of igs, in member order): status[i] = what advance(k) on member i returns
+    static int advance_many_srkn(NBodyIntegration *const *igs, int count, int64_t k, int *status);
+    // the members of an advance_many call that are not symplectic: the start-up gang and the steady gang
+    static int advance_many_multistep(NBodyIntegration *const *igs, int count, int64_t k, int *status);
     // one launch for the members igs[0 .. count) on the stream of the lead igs[0], whose argument array `ga` is (nbody.cpp)
     template <typename Args, typename Fill, typename Launch, typename Commit>
     static int gang_frame(NBodyIntegration *const *igs, int count, GangArgs<Args> &ga, bool timed, Fill &&fill, Launch &&launch, Commit &&commit);
     // what the members of one gang launch share with its lead: the device, the ring length, the evaluation order
     bool shares_launch_with(const NBodyIntegration &lead) const { return device_ == lead.device_ && L_ == lead.L_ && pv_ == lead.pv_; }
+    // (the SRKN gang's: its blocks carry their own tables, and a symplectic handle's ring is its one working slot)
+    bool shares_srkn_launch_with(const NBodyIntegration &lead) const {
+        return device_ == lead.device_ && pv_ == lead.pv_ && compensated_ == lead.compensated_;
+    }
     int queued(int st, bool made = true) { if (!st && made && n_ > 0) count_launches(1); return st; }   // a launch that was made, for the hook's count
     int srkn_step(double h, double *y_slot);  // FixedRungeKuttaIntegrator::advance (SRKN)
     int srkn_batch(int64_t k);                // k of them in one launch of the single-workgroup kernel (step_srkn_small.hip)
@@ -348,6 +370,7 @@ private:
     DevBuf<float> posf_;                      // EPH_PATH_F32_PAIRS: the level's positions and mu as 4 floats per body
     GangArgs<LmArgs> gang_;                   // advance_many: the argument array of the steady gang this handle leads (its .dev is the buffer)
     GangArgs<LmStartupArgs> startup_;         // advance_many: the same for the start-up gang it leads
+    GangArgs<SrknGangArgs> srkn_gang_;        // advance_many: the same for the SRKN gang it leads (plain or `<Double>`, as the handle is)
     // state: allocated at creation, zeroed, copied by clone | scratch: allocated at creation, contents nobody's | lazy: allocated where
     // it is first used (lm_batch, advance_many), neither zeroed nor copied
     enum class Buf { state, scratch, lazy };
@@ -364,13 +387,14 @@ private:
                (st = f(EPH_NBODY_BUF(fast_partial_), fast_partial_doubles(g.npad_), Buf::lazy)) ||
                (st = f(EPH_NBODY_BUF(posf_), 4 * bodies, Buf::lazy)) ||
                (st = f(EPH_NBODY_BUF(gang_.dev), (size_t)0, Buf::lazy)) ||                 // (one LmArgs per system of the gang)
-               (st = f(EPH_NBODY_BUF(startup_.dev), (size_t)0, Buf::lazy)));
+               (st = f(EPH_NBODY_BUF(startup_.dev), (size_t)0, Buf::lazy)) ||
+               (st = f(EPH_NBODY_BUF(srkn_gang_.dev), (size_t)0, Buf::lazy)));
 #undef EPH_NBODY_BUF
         return st;
     }
 
     // gang_frame on the lead: the event that joins the members' streams to the lead's and releases them behind the launch, and the one
-    // behind the argument copy, which guards the pinned twins of gang_ and startup_ both
+    // behind the argument copy, which guards the pinned twins of gang_, startup_ and srkn_gang_ alike
     hipEvent_t gang_ev_ = nullptr, gang_copy_ev_ = nullptr;
 };
 

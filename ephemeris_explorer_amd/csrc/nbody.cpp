@@ -7,6 +7,7 @@
 //   FixedRungeKuttaIntegrator::advance + SRKN   integration/src/runge_kutta/mod.rs:106-126, nystrom/symplectic.rs:69-102
 // The host replays the reference's scalar bookkeeping (time, bound, step counters) with the reference's f64
 // operations; all vector arithmetic runs in the HIP kernels of step_wg.hip / step_wave.hip / step_small.hip / step_srkn_small.hip / fast.hip / solout.hip.
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -34,7 +35,7 @@ NBodyIntegration::~NBodyIntegration() {
         for (auto *v : {&ev_pending_, &ev_free_})
             for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
         if (gang_ev_) (void)hipEventDestroy(gang_ev_);
-        // (the pinned arrays of gang_ and startup_ go with the members, behind this wait for the last copy out of them)
+        // (the pinned arrays of gang_, startup_ and srkn_gang_ go with the members, behind this wait for the last copy out of them)
         if (gang_copy_ev_) { (void)hipEventSynchronize(gang_copy_ev_); (void)hipEventDestroy(gang_copy_ev_); }
         (void)hipStreamDestroy(stream_);
     }
@@ -594,12 +595,13 @@ bool NBodyIntegration::gang_ready(int64_t k) const {
 }
 
 // ---- The gangs of advance_many -------------------------------------------------------------------------------------------------
-// One gang launch, stated once for the start-up gang (LmStartupArgs, k_lm_startup_small) and the steady one (LmArgs, k_lm_small): the
+// One gang launch, stated once for the start-up gang (LmStartupArgs, k_lm_startup_small), the steady one (LmArgs, k_lm_small) and the
+// symplectic one (SrknGangArgs, k_srkn_small_many): the
 // members igs[0 .. count), all on the device of the lead igs[0], a workgroup each in ONE launch on the lead's stream. `ga` is the
 // lead's argument array of the gang's kind. fill(host[i], i) writes member i's launch arguments and moves nothing; launch(device
 // array) queues the kernel on the lead's stream; commit(i) is member i's host bookkeeping, which runs under the kernel. A `timed`
-// frame whose lead has enable_timing() on brackets the launch with the lead's event pair and waits for it (the steady gang; the
-// start-up gang is not timed: kernel_time counts steady-state kernels). Otherwise not synchronised: like eph_nbody_advance, the
+// frame whose lead has enable_timing() on brackets the launch with the lead's event pair and waits for it (the steady and the
+// symplectic gang; the start-up gang is not timed: kernel_time counts steady-state kernels). Otherwise not synchronised: like eph_nbody_advance, the
 // call only queues.
 template <typename Args, typename Fill, typename Launch, typename Commit>
 int NBodyIntegration::gang_frame(NBodyIntegration *const *igs, int count, GangArgs<Args> &ga, bool timed, Fill &&fill, Launch &&launch,
@@ -687,6 +689,85 @@ void NBodyIntegration::commit_gang(int64_t k) {
     for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;                 // behind the launch, under the kernel (steps_certain)
 }
 
+// The SRKN gang's member: what srkn_batch(k) comes to -- one launch of the single-workgroup kernel in batch_frame -- in two halves,
+// as the steady gang's above. The block carries the member's own k.
+int64_t NBodyIntegration::srkn_gang_steps(int64_t k, int *status_after) const {
+    *status_after = EPH_OK;
+    if (!srkn_small_ready() || failed_ || k <= 0) return 0;
+    return steps_available(std::min<int64_t>(k, (int64_t)1 << 30), status_after);
+}
+void NBodyIntegration::fill_srkn_gang_args(SrknGangArgs &g, int64_t k) const {
+    g = SrknGangArgs{};
+    fill_srkn_args(g.s, h_);
+    g.nsteps = (long long)k;
+    // the terms launch_srkn_small / launch_srkn_double_small hold their one block to: the gang's blocks are in device memory by the
+    // time dispatch.cpp sees them, so they are held to them here, on the host twin
+    assert(g.s.n >= 1 && g.s.n <= kGangMaxN && g.s.stages >= 1 && g.s.stages <= 32 && g.nsteps >= 1 && (!compensated_ || (g.s.YE && g.s.VE)));
+}
+void NBodyIntegration::commit_srkn_gang(int64_t k) {
+    evals_ += (uint64_t)k * srkn_step_evals() + (rk_.fsal && starter_i_ == 0 ? 1 : 0);
+    starter_i_ += (uint32_t)k;
+    if (timing_) kernel_launches_ += 1;                                 // as commit_gang: the lead alone times the shared launch
+    samp_ = SampleArgs{};
+    for (int64_t s = 0; s < k; ++s) time_ = time_ + h_;                 // behind the launch, under the kernel (steps_certain)
+}
+
+// The symplectic members of an advance_many call. Round by round (one round unless k exceeds 2^30) the members that can take steps
+// in one launch of the single-workgroup kernel split into the plain group and the `<Double>` group; a group of at least two is one
+// gang_frame on its first member, everybody else finishes in its own advance_from. A sampled member joins a launch in the first
+// round only (the kernel's countdown starts at the call's first step: advance_from's rule). status[i]: what advance(k) on member i
+// would have returned. The return value is a frame's failure, which ends the call.
+int NBodyIntegration::advance_many_srkn(NBodyIntegration *const *igs, int count, int64_t k, int *status) {
+    std::vector<int64_t> done((size_t)count, 0);
+    std::vector<char> open((size_t)count, 1), ganged((size_t)count, 0);
+    std::vector<NBodyIntegration *> mem;
+    std::vector<int> who, after;
+    std::vector<int64_t> ks;
+    std::vector<SampleArgs> samp;
+    for (int left = count, round = 0; left > 0; ++round) {
+        std::fill(ganged.begin(), ganged.end(), 0);
+        for (int kind = 0; kind < 2; ++kind) {                          // plain, then `<Double>`
+            mem.clear(); who.clear(); after.clear(); ks.clear(); samp.clear();
+            for (int i = 0; i < count; ++i) {
+                NBodyIntegration &ig = *igs[i];
+                if (!open[(size_t)i] || (int)ig.compensated_ != kind) continue;
+                int after_i = EPH_OK;
+                const int64_t k_i = round > 0 && ig.samp_.period ? 0 : ig.srkn_gang_steps(k - done[(size_t)i], &after_i);
+                if (k_i <= 0 || (!mem.empty() && !ig.shares_srkn_launch_with(*mem[0]))) continue;
+                mem.push_back(&ig); who.push_back(i); after.push_back(after_i); ks.push_back(k_i); samp.push_back(ig.samp_);
+            }
+            if (mem.size() < 2) continue;
+            NBodyIntegration &lead = *mem[0];
+            const int n = (int)mem.size();
+            const int st = gang_frame(mem.data(), n, lead.srkn_gang_, true,
+                                      [&](SrknGangArgs &g, int j) { mem[(size_t)j]->fill_srkn_gang_args(g, ks[(size_t)j]); },
+                                      [&](const SrknGangArgs *args) {
+                                          return kind ? launch_srkn_double_small_many(lead.pv_, lead.stream_, args, n)
+                                                      : launch_srkn_small_many(lead.pv_, lead.stream_, args, n);
+                                      },
+                                      [&](int j) { mem[(size_t)j]->commit_srkn_gang(ks[(size_t)j]); });
+            if (st) return st;
+            for (size_t j = 0; j < mem.size(); ++j) {
+                const size_t i = (size_t)who[j];
+                const int64_t want = std::min<int64_t>(k - done[i], (int64_t)1 << 30);
+                done[i] += ks[j];
+                ganged[i] = 1;
+                if (ks[j] < want) status[i] = after[j];                 // its bound, or t + h == t: where its own advance(k) stops
+                if (ks[j] < want || done[i] == k) { open[i] = 0; --left; }
+                else mem[j]->samp_ = samp[j];                            // it goes round again: the call's schedule is still its own
+            }
+        }
+        // whoever is not in a launch of this round finishes alone; what stays open took 2^30 steps in a launch and has more to take
+        for (int i = 0; i < count; ++i) {
+            if (!open[(size_t)i] || ganged[(size_t)i]) continue;
+            status[i] = igs[i]->advance_from(done[(size_t)i], k, nullptr);
+            open[(size_t)i] = 0;
+            --left;
+        }
+    }
+    return EPH_OK;
+}
+
 int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int64_t k) {
     if (count < 0 || (count > 0 && !igs) || k < 0) return EPH_ERR_BAD_ARGUMENT;
     if (count == 0 || k == 0) return EPH_OK;
@@ -695,6 +776,28 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
         for (int j = 0; j < i; ++j)
             if (igs[j] == igs[i]) return EPH_ERR_BAD_ARGUMENT;          // a system cannot be in the gang twice
     }
+    // The symplectic members first, then the others as a call that consists of them alone; the first status in member order.
+    std::vector<NBodyIntegration *> part[2];
+    std::vector<int> who[2];
+    for (int i = 0; i < count; ++i) {
+        part[igs[i]->is_multistep_ ? 1 : 0].push_back(igs[i]);
+        who[igs[i]->is_multistep_ ? 1 : 0].push_back(i);
+    }
+    std::vector<int> status((size_t)count, EPH_OK), sub;
+    for (int p = 0; p < 2; ++p) {
+        if (part[p].empty()) continue;
+        sub.assign(part[p].size(), EPH_OK);
+        const int st = p == 0 ? advance_many_srkn(part[p].data(), (int)part[p].size(), k, sub.data())
+                              : advance_many_multistep(part[p].data(), (int)part[p].size(), k, sub.data());
+        if (st) return st;
+        for (size_t j = 0; j < sub.size(); ++j) status[(size_t)who[p][j]] = sub[j];
+    }
+    for (int i = 0; i < count; ++i)
+        if (status[(size_t)i]) return status[(size_t)i];
+    return EPH_OK;
+}
+
+int NBodyIntegration::advance_many_multistep(NBodyIntegration *const *igs, int count, int64_t k, int *status) {
     // 1. The start-up. Every plain member that can take macro steps in one launch (startup_small_steps) takes m_i = min(k, macro
     // steps left) of them; at least two that can share a launch do. Anyone else -- a <Double> member too -- does its start-up in
     // its own advance below.
@@ -724,14 +827,12 @@ int NBodyIntegration::advance_many(NBodyIntegration *const *igs, int count, int6
         gang = taken[(size_t)i] == taken[0] && !(taken[(size_t)i] > 0 && igs[i]->samp_.period) && igs[i]->gang_ready(left) &&
                igs[i]->shares_launch_with(*igs[0]);
     if (!gang) {
-        // the plain meaning: each member finishes its own call, the first status other than EPH_OK is the call's
-        int first = EPH_OK;
+        // the plain meaning: each member finishes its own call (the first status other than EPH_OK is the call's: advance_many)
         for (int i = 0; i < count; ++i) {
             if (taken[(size_t)i] == k) { igs[i]->samp_ = SampleArgs{}; continue; }
-            const int st = igs[i]->advance_from(taken[(size_t)i], k, nullptr);
-            if (st && !first) first = st;
+            status[i] = igs[i]->advance_from(taken[(size_t)i], k, nullptr);
         }
-        return first;
+        return EPH_OK;
     }
     for (int i = 0; i < count; ++i)
         if (igs[i]->failed_) return igs[i]->failed_;

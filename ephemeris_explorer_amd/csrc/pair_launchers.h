@@ -12,6 +12,8 @@ int lm_small_many(hipStream_t s, const LmArgs *argv_dev, int count, int L, int64
 int lm_double_small(hipStream_t s, const LmDoubleArgs &d, int64_t nsteps);                                 // step_double_small.hip
 int srkn_small(hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);                                     // step_srkn_small.hip
 int srkn_double_small(hipStream_t s, const SrknSmallArgs &a, int64_t nsteps);                              // step_srkn_small.hip
+int srkn_small_many(hipStream_t s, const SrknGangArgs *argv_dev, int count);                               // step_srkn_small.hip
+int srkn_double_small_many(hipStream_t s, const SrknGangArgs *argv_dev, int count);                        // step_srkn_small.hip
 int lm_startup_small(hipStream_t s, const LmStartupArgs &a, bool compensated);                             // step_srkn_small.hip
 int lm_startup_small_many(hipStream_t s, const LmStartupArgs *argv_dev, int count);                        // step_srkn_small.hip
 int lm_step_fast(hipStream_t s, const LmArgs &a, double *partial, int S, int unroll, bool approx, float *posf, int f32_stage,

@@ -9,7 +9,8 @@ namespace EPH_PV_NS {
 // aggregate would be emitted for the device as well, where host functions do not exist.
 const PairKernels *pair_table() {
     static const PairKernels t = {accel_wave,      accel_wg,   lm_step_wave,      lm_step_wg,   lm_persistent, lm_small,    lm_small_many,
-                                  lm_double_small, srkn_small, srkn_double_small, lm_startup_small, lm_startup_small_many,
+                                  lm_double_small, srkn_small, srkn_double_small, srkn_small_many, srkn_double_small_many,
+                                  lm_startup_small, lm_startup_small_many,
                                   lm_step_fast,    craft_launch, kPairVariant};
     return &t;
 }

@@ -249,7 +249,8 @@ int NBodyPropagator::run_batch(int64_t k) {
 // step_n(k) on several propagators at once. Whatever advance_many would not take runs per propagator as usual; the steps of the
 // others share launches: every propagator still has `rem` steps to go, the gang advances min(rem, kmax) of them -- no further than
 // the end of a member's start-up -- in ONE launch with a workgroup per system (k_lm_startup_small for the members in their
-// start-up, k_lm_small for the others), then each fits and pushes its own windows. Results are those of step_n(k) on each.
+// start-up, k_lm_small for the others; the propagators on a symplectic method share a launch of k_srkn_small_many, whose sampling
+// countdown is each member's own), then each fits and pushes its own windows. Results are those of step_n(k) on each.
 int NBodyPropagator::step_n_many(NBodyPropagator *const *ps, int count, int64_t k) {
     if (count < 0 || (count > 0 && !ps) || k < 0) return EPH_ERR_BAD_ARGUMENT;
     std::vector<int64_t> rem((size_t)count, k);
@@ -281,7 +282,9 @@ int NBodyPropagator::step_n_many(NBodyPropagator *const *ps, int count, int64_t 
         if (act.empty()) return EPH_OK;
         bool gang = act.size() > 1;
         for (NBodyPropagator *p : act)
-            gang = gang && (p->integ_->started() ? p->integ_->gang_ready(chunk) : p->integ_->startup_small_steps(chunk) == chunk);
+            gang = gang && (!p->integ_->is_multistep() ? p->integ_->srkn_gang_ready(chunk)
+                            : p->integ_->started()     ? p->integ_->gang_ready(chunk)
+                                                       : p->integ_->startup_small_steps(chunk) == chunk);
         if (!gang) {                                                 // somebody cannot: everybody finishes alone
             for (int i = 0; i < count; ++i)
                 if (rem[i] > 0) { const int st = ps[i]->step_n(rem[i]); if (st) return st; }

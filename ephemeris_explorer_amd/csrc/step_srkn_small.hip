@@ -9,7 +9,8 @@
 // the stage's two coefficients are read from the kernel arguments by the wave-uniform stage index (scalar loads, no register array).
 // k_lm_startup_small, further down, runs the start-up of a linear multistep handle -- macro steps of four such steps, each closed
 // by a force evaluation into the history ring -- on the same stage loop (srkn_small_step), alone or as a gang of one workgroup per
-// system.
+// system. k_srkn_small_many<SrknPlain> / <SrknDouble> are the step kernels' own gang form: a workgroup per system, each with its
+// own step count.
 // Compiled once per evaluation order of the point-mass term (pair_ns.h).
 #include <initializer_list>
 #include <type_traits>
@@ -218,6 +219,17 @@ __global__ void __launch_bounds__(kSmallThreads) k_srkn_double_small(const SrknS
     __shared__ __attribute__((aligned(32))) Body4 sP[kTile];
     srkn_small_steps<SrknDouble>(U, Lw, sP, a, nsteps);
 }
+// The gang form of the two kernels above (eph_nbody_advance_many, eph_prop_step_n_many): one workgroup per SYSTEM on the same
+// srkn_small_steps, its arguments argv[blockIdx.x] -- the member's own system, table, step and STEP COUNT (every member stops at its
+// own bound); nothing is shared between workgroups, and a grid above the CU count queues
+template <typename State>
+__global__ void __launch_bounds__(kSmallThreads) k_srkn_small_many(const SrknGangArgs *__restrict__ argv) {
+    __shared__ __attribute__((aligned(16))) double U[kSmallRows][kSmallRow];
+    __shared__ __attribute__((aligned(16))) double Lw[kSmallRows][kSmallRow];
+    __shared__ __attribute__((aligned(32))) Body4 sP[kTile];
+    const SrknGangArgs &g = argv[blockIdx.x];
+    srkn_small_steps<State>(U, Lw, sP, g.s, g.nsteps);
+}
 // MANY: one workgroup per SYSTEM, its arguments argv[blockIdx.x] (eph_nbody_advance_many); nothing is shared between workgroups
 template <typename State, bool MANY>
 __global__ void __launch_bounds__(kSmallThreads) k_lm_startup_small(const LmStartupArgs a0, const LmStartupArgs *__restrict__ argv) {
@@ -236,6 +248,14 @@ int srkn_double_small(hipStream_t s, const SrknSmallArgs &a, int64_t nsteps) {
     if (a.n > kSmallMaxN) return EPH_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_srkn_double_small, dim3(1), dim3(kSmallThreads), 0, s, a, (long long)nsteps);
     return launched("k_srkn_double_small");
+}
+int srkn_small_many(hipStream_t s, const SrknGangArgs *argv_dev, int count) {
+    hipLaunchKernelGGL((k_srkn_small_many<SrknPlain>), dim3((unsigned)count), dim3(kSmallThreads), 0, s, argv_dev);
+    return launched("k_srkn_small_many");
+}
+int srkn_double_small_many(hipStream_t s, const SrknGangArgs *argv_dev, int count) {
+    hipLaunchKernelGGL((k_srkn_small_many<SrknDouble>), dim3((unsigned)count), dim3(kSmallThreads), 0, s, argv_dev);
+    return launched("k_srkn_small_many<Double>");
 }
 int lm_startup_small(hipStream_t s, const LmStartupArgs &a, bool compensated) {
     if (a.s.n > kSmallMaxN) return EPH_ERR_UNSUPPORTED;

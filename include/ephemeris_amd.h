@@ -122,7 +122,8 @@ int32_t eph_accel_eval(int32_t n, const double *pos_xyz, const double *mu, doubl
  *     bodies -- else EPH_ERR_UNSUPPORTED at the next steady step); 3-6 are EPH_ERR_UNSUPPORTED with an eph_last_error text;
  *   - eph_nbody_shard / eph_nbody_shard_peer are EPH_ERR_UNSUPPORTED (the handle stays usable), and so is eph_prop_create with
  *     a "<Double>" name: the reference has no solout on Double;
- *   - eph_nbody_advance_many advances it by the separate call, with the same results;
+ *   - eph_nbody_advance_many advances a tagged multistep member by the separate call, with the same results; tagged symplectic
+ *     members of at most 32 bodies share one launch among themselves, as the plain ones do (see there);
  *   - eph_ephemeris_interpolation_errors works exactly like stepping by hand and comparing the value parts;
  *   - eph_srkn_coeffs / eph_elm2_coeffs know base names only.
  * At most 32 bodies: a steady multistep advance is ONE launch whatever the step count, so are the start-up's macro steps
@@ -176,6 +177,18 @@ int32_t eph_nbody_sync(eph_nbody *h);
  * taken member by member otherwise. Same results as the separate calls; systems that do not qualify (more bodies, a sharded
  * handle, a forced per-launch path, a step that would return a StepError) simply make the call do those. Handles must be
  * distinct and on one device.
+ * The members on a symplectic (SRKN) method are taken apart from the multistep ones and change nothing for them. Those of at most
+ * 32 bodies (unsharded, path 0 or 2) that can take at least one step share ONE launch with a workgroup per system when there are
+ * at least two of a kind -- the plain ones one launch, the "<Double>" ones another. Table, body count, h and its sign may differ
+ * from member to member, and so may the number of steps taken: a member in front of its bound, or whose t + h == t, takes the
+ * steps its own eph_nbody_advance(h, n_steps) would take and is left exactly where that call leaves it. A kind with one member,
+ * and any symplectic member that does not qualify, is advanced by the separate call.
+ * The status is the first one other than EPH_OK in member order, as the separate calls in that order would give it; a member's
+ * own status is what its next eph_nbody_advance returns (EPH_BOUND_REACHED and EPH_STEP_SIZE_UNDERFLOW persist, and that call
+ * queues nothing).
+ * A call may make several shared launches (the plain symplectic group, the "<Double>" one, the multistep start-up, the multistep
+ * steady steps), in that order. A failure for lack of resources is returned before anything of THAT launch is queued and leaves
+ * that launch's members unmoved; the members of the launches before it have advanced, and the members behind it have not.
  * ASYNCHRONOUS, like eph_nbody_advance: the call queues the launch and returns; completion is eph_nbody_sync / get_state of a
  * member. A device failure AFTER the members' bookkeeping has moved (the shared launch itself) marks every member failed: all their
  * later calls -- and those of their clones -- return that status; kernel time of a timed gang accrues to the FIRST handle. */
@@ -249,7 +262,8 @@ int32_t eph_prop_shard(eph_prop *p, int32_t rank, int32_t world, const void *rcc
                        void *ctx);
 int32_t eph_prop_shard_peer(eph_prop *p, eph_peer *peer);
 /* eph_prop_step_n(p, n) on `count` propagators at once, their steady-state steps in shared launches
- * (eph_nbody_advance_many); each propagator samples, fits and pushes its own windows. Queues and returns like it: the fits are
+ * (eph_nbody_advance_many) -- the multistep ones', start-up included, and the symplectic ones' of at most 32 bodies, every chunk
+ * that all of them can take in one launch per kind; each propagator samples, fits and pushes its own windows. Queues and returns like it: the fits are
  * settled by the next call that needs them (eph_prop_time, has_reached, take_solution, get_state). */
 int32_t eph_prop_step_n_many(eph_prop *const *props, int32_t count, int64_t n);
 /* IncrementalPropagator::step  nbody.rs:200-207. Executed lazily: the reference's callers step in a loop and read
